@@ -8,7 +8,11 @@ With --gpus N > 1 (one process per GPU via torch.distributed.run) the frame's 8x
 sharded across ranks (TileScheduler order, interleaved) and gathered to rank 0 with a single
 RCCL gather at frame end: strong scaling (fixed total work).
 
-Prints ONE JSON line (rank 0) with roofline and cpu_baseline objects; see DESIGN.md §Measurement.
+A plain run sets up, warms up, times --steps frames, writes the last frame with --dump-outputs and
+prints ONE JSON line (rank 0) with the roofline object of the timed launches.  --full adds what
+takes CPU runs of its own after the timed region: the cpu_baseline object (N = 1: the reference's
+render path on a sample of the frame, and its thread scaling) and the parity object (the GPU frame,
+or the gathered frame at N > 1, against it); see DESIGN.md §Measurement.
 """
 from __future__ import annotations
 
@@ -56,8 +60,15 @@ SCENES = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed frames (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run the CPU baseline (N = 1, with its thread scaling) and the "
+                         "parity check of the frame against it (cpu_baseline / parity are null without it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames write what the last one computed as DIR/<name>.npy: "
+                         "radiance_tiles (float32 [tiles, 64, 3], the buffer the render call filled; the gathered "
+                         "frame at N > 1; a fixed seeded sample of the tiles above 64 MB) and render_stats (float64)")
     ap.add_argument("--scene", default="bunny", choices=sorted(SCENES),
                     help="bunny = configs[2] (default, the north-star workload); spheres = configs[1]; "
                          "lucy = configs[3]; elf = configs[4]")
@@ -80,7 +91,7 @@ def parse():
                          "run inside it -- rank 0's reference scene build and parity run after teardown")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="test hook: spawn the ranks like --gpus N does, join a gloo group, no GPU work")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline and parity out")
     ap.add_argument("--pipeline", default="auto", choices=["auto", "megakernel", "wavefront", "chunks"])
     ap.add_argument("--waves", type=int, default=0,
                     help="megakernel occupancy variant (sp_render_params.waves_per_simd; 0 = automatic)")
@@ -101,6 +112,8 @@ def parse():
                     help="tools/pmc_valu.py output of a PMC pass of this workload (VALU-issue roofline; default "
                          "profiles/pmc_valu_bench_<scene>[_shard<N>].json)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.sim_world > 1 and not -1 <= a.sim_rank < a.sim_world:
         ap.error("--sim-rank must be -1 or in [0, --sim-world)")
     # tools/gpu_pmc_*.sh output names (PMC passes profile rank 0's shard)
@@ -325,6 +338,8 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out[: len(my_tiles)] if frame is None else frame, stats[-1])
     stall = float(os.environ.get("SP_BENCH_POST_STALL_S", "0") or 0)  # test hook: a slow reference build
     if stall > 0:
         time.sleep(stall)
@@ -336,7 +351,7 @@ def main():
 
     cpu = None
     parity = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # the reference library logs to stdout (base/Logger.cpp); keep stdout for the JSON line
         sys.stdout.flush()
         saved = os.dup(1)
@@ -402,6 +417,25 @@ def main():
             line["test_post_stall_s"] = stall
     print(json.dumps(line), flush=True)
     os.dup2(2, 1)  # exit-time log summaries of the reference library go to stderr
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, tiles, st):
+    """--dump-outputs: what the last timed step handed its caller.  radiance_tiles.npy is the tile
+    buffer the render call filled (float32 [tiles, 64, 3], tiles in the order they were asked for;
+    at N > 1 the gathered frame); above 64 MB a fixed seeded sample of its tiles, in ascending
+    order, so two builds dump the same rows.  render_stats.npy holds the call's counts (float64:
+    rays, shadow rays, samples, RNG draws)."""
+    os.makedirs(directory, exist_ok=True)
+    t = tiles.detach().cpu().numpy()
+    keep = DUMP_MAX_BYTES // max(1, t[0].nbytes) if len(t) else 0
+    if len(t) > keep:
+        t = t[np.sort(np.random.default_rng(20240607).choice(len(t), size=keep, replace=False))]
+    np.save(os.path.join(directory, "radiance_tiles.npy"), np.ascontiguousarray(t, dtype=np.float32))
+    np.save(os.path.join(directory, "render_stats.npy"),
+            np.array([st.rays, st.shadow_rays, st.samples, st.rng_draws], dtype=np.float64))
 
 
 def sim_all_ranks(args, scene, integ, n_tiles, rdev):

@@ -19,7 +19,7 @@ def test_bench_two_ranks_gathered_frame():
     env = dict(os.environ, SP_BENCH_SHARED_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--width", "256", "--height", "160", "--spp", "4", "--parity-seconds", "2"],
+                        "--full", "--width", "256", "--height", "160", "--spp", "4", "--parity-seconds", "2"],
                        capture_output=True, text=True, timeout=380, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -41,7 +41,7 @@ def test_bench_eight_ranks_ragged_shards():
     env = dict(os.environ, SP_BENCH_SHARED_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--width", "260", "--height", "130", "--spp", "8", "--parity-seconds", "3"],
+                        "--full", "--width", "260", "--height", "130", "--spp", "8", "--parity-seconds", "3"],
                        capture_output=True, text=True, timeout=580, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

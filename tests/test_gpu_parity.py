@@ -213,20 +213,17 @@ def test_wavefront_rejects_other_integrators(scene_dir):
                                                       ("lucy_small.sp", 40, 56, "direct_lighting", 3),
                                                       ("elf_small.sp", 40, 56, "iterative_rrnee", 2)])
 def test_vs_reference_build_bitexact(scene_dir, scene, w, h, integrator, spp):
-    # the HIP path against the reference's own code (oracle/_ref, built from its sources)
+    # the HIP path against the reference's own code (oracle/_ref, built from its sources; where it
+    # is not built, the tiles it rendered for these cases, tests/golden/ref_tiles.npz, with the
+    # RSQRTSS of the CPU they were rendered on installed for the scene build and the device)
     from tests import test_oracle_vs_ref as R
-    if not os.path.exists(R.REF_LIB):
-        pytest.skip("oracle/_ref not built (reference sources were not available)")
-    import ctypes as C
-    L = C.CDLL(R.REF_LIB)
-    L.ref_render.restype = C.c_int
-    L.ref_render.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int32), C.c_int64,
-                             C.c_int, C.POINTER(C.c_float)]
-    L.ref_last_error.restype = C.c_char_p
-    s = load(scene_dir, scene, w, h, bvh=1)
-    g, _ = sp.render_tiles(s, integrator, spp)
+    L = R.open_ref()
+    with L.recorded_cpu():
+        s = load(scene_dir, scene, w, h, bvh=1)
+        g, _ = sp.render_tiles(s, integrator, spp)
     ids = np.arange(g.shape[0], dtype=np.int32)
-    r = R.ref_render(L, os.path.join(scene_dir, scene), w, h, sp.string_to_integrator_type(integrator), spp, ids)
+    r = R.ref_render(L, os.path.join(scene_dir, scene), w, h, sp.string_to_integrator_type(integrator), spp, ids,
+                     host_rsqrt=False)
     assert np.array_equal(g.view(np.uint32), r.view(np.uint32)), rel_l2(g, r)
 
 

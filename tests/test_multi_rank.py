@@ -108,7 +108,7 @@ def test_bench_rank0_reference_work_after_teardown(scene_dir):
     env = dict(os.environ, SP_BENCH_CPU_RENDER="1", SP_BENCH_POST_STALL_S="15", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--width", "40", "--height", "24", "--spp", "2", "--pg-timeout", "5",
+                        "--full", "--width", "40", "--height", "24", "--spp", "2", "--pg-timeout", "5",
                         "--parity-seconds", "1"],
                        capture_output=True, text=True, timeout=380, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,9 +7,13 @@ per-pixel loop.  The C oracle built against glibc's float libm (liboracle_glibc.
 semantics) must reproduce it bit for bit; the GPU is in turn checked bit-exact against the oracle
 (tests/test_gpu_parity.py), closing the chain reference == oracle == HIP path.
 
-The library exists only where the reference sources were available at build time (this
-container); elsewhere these tests skip.
+The library exists only where the reference sources were available at build time.  Its output for
+every case below is stored in tests/golden/ref_tiles.npz (written by this module with
+SP_WRITE_REF_GOLDEN=1 where the library exists), so elsewhere the oracle is checked against those
+recorded tiles; where the library exists it renders again and, on a CPU like the record's, must
+also reproduce the record (class Ref).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -23,29 +27,92 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libsp_ref.so")
 
 
-@pytest.fixture(scope="module")
-def ref():
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_tiles.npz")
+WRITE_GOLDEN = os.environ.get("SP_WRITE_REF_GOLDEN") == "1"
+
+
+class Ref:
+    """The reference's tiles: rendered by oracle/_ref/libsp_ref.so where it is built (and equal to
+    the record), read from the record elsewhere.
+
+    The reference normalises with RSQRTSS, whose results differ between CPU vendors, so the record
+    carries the RSQRTSS table of the CPU it was rendered on (as tests/golden/*_full_tiles.npz do).
+    The device path can emulate that CPU (recorded_cpu()); the C oracle executes the instruction,
+    so without the library it can be checked against the record only on a CPU with the same table."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        self.golden = dict(np.load(GOLDEN)) if os.path.exists(GOLDEN) and not WRITE_GOLDEN else {}
+        self.rendered = {}
+        self.host = sp.rsqrt_table()
+        self.same_cpu = bool(self.golden) and \
+            (int(self.golden["rsqrt_bits"]), int(self.golden["rsqrt_zero"]), int(self.golden["rsqrt_denorm"])) == \
+            (self.host["bits"], self.host["zero_result"], self.host["denorm_result"]) and \
+            np.array_equal(self.golden["rsqrt_entries"], self.host["entries"])
+
+    @contextlib.contextmanager
+    def recorded_cpu(self):
+        """Scenes built and rendered by simplepath_amd inside this block use the RSQRTSS of the CPU
+        the tiles render() returns come from: this host's with the library, else the record's."""
+        if self.lib is not None or self.same_cpu:
+            yield
+            return
+        g = self.golden
+        sp.set_rsqrt_table({"entries": g["rsqrt_entries"], "bits": int(g["rsqrt_bits"]),
+                            "zero_result": int(g["rsqrt_zero"]), "denorm_result": int(g["rsqrt_denorm"])})
+        try:
+            yield
+        finally:
+            sp.set_rsqrt_table(None)
+
+    def render(self, path, w, h, integrator, spp, ids, host_rsqrt=True):
+        """host_rsqrt: the caller compares with code that executes this host's RSQRTSS (the oracle)."""
+        key = f"{os.path.basename(path)}_{w}x{h}_i{integrator}_s{spp}_n{ids.size}"
+        if self.lib is None:
+            if host_rsqrt and not self.same_cpu:
+                pytest.skip("oracle/_ref is not built here and its recorded tiles come from a CPU with another RSQRTSS")
+            return self.golden[key].view(np.float32)
+        out = np.zeros((ids.size, 64, 3), dtype=np.float32)
+        rc = self.lib.ref_render(path.encode(), w, h, integrator, spp, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 ids.size, 8, out.ctypes.data_as(C.POINTER(C.c_float)))
+        assert rc == 0, self.lib.ref_last_error()
+        if WRITE_GOLDEN:
+            self.rendered[key] = out.view(np.uint32)  # bit patterns: the map's infinities and NaNs survive
+        elif self.same_cpu:
+            assert np.array_equal(out.view(np.uint32), self.golden[key]), f"{key}: the record is stale"
+        return out
+
+    def save(self):
+        t = self.host
+        np.savez_compressed(GOLDEN, rsqrt_entries=t["entries"], rsqrt_bits=t["bits"], rsqrt_zero=t["zero_result"],
+                            rsqrt_denorm=t["denorm_result"], **self.rendered)
+
+
+def open_ref():
     if not os.path.exists(REF_LIB):
         if os.path.isdir("/root/reference"):
             import subprocess
             subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref.sh")], check=True, timeout=1200)
-        else:
-            pytest.skip("reference sources not present: oracle/_ref not built")
-    L = C.CDLL(REF_LIB)
-    L.ref_render.restype = C.c_int
-    L.ref_render.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int32), C.c_int64,
-                             C.c_int, C.POINTER(C.c_float)]
-    L.ref_last_error.restype = C.c_char_p
-    return L
+    L = None
+    if os.path.exists(REF_LIB):
+        L = C.CDLL(REF_LIB)
+        L.ref_render.restype = C.c_int
+        L.ref_render.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int32), C.c_int64,
+                                 C.c_int, C.POINTER(C.c_float)]
+        L.ref_last_error.restype = C.c_char_p
+    return Ref(L)
 
 
-def ref_render(L, path, w, h, integrator, spp, ids):
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    out = np.zeros((ids.size, 64, 3), dtype=np.float32)
-    rc = L.ref_render(path.encode(), w, h, integrator, spp, ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.size, 8,
-                      out.ctypes.data_as(C.POINTER(C.c_float)))
-    assert rc == 0, L.ref_last_error()
-    return out
+@pytest.fixture(scope="module")
+def ref():
+    r = open_ref()
+    yield r
+    if WRITE_GOLDEN and r.rendered:
+        r.save()
+
+
+def ref_render(L, path, w, h, integrator, spp, ids, host_rsqrt=True):
+    return L.render(path, w, h, integrator, spp, np.ascontiguousarray(ids, dtype=np.int32), host_rsqrt)
 
 
 def oracle_render(path, w, h, integrator, spp, ids):
@@ -123,6 +190,20 @@ def test_figure_scenes(ref, scene_dir, scene, integrator, spp):
     ids = np.arange(sp.TileScheduler(40, 56).get_num_tiles(), dtype=np.int32)
     r = ref_render(ref, path, 40, 56, t, spp, ids)
     o = oracle_render(path, 40, 56, t, spp, ids)
+    assert same(r, o), (scene, integrator, float(np.abs(r - o).max()))
+    assert r.max() > 0.0
+
+
+@pytest.mark.parametrize("scene,w,h,integrator,spp", [("bunny.sp", 32, 24, "iterative_rrnee", 2),
+                                                      ("material_spheres_ibl.sp", 24, 48, "iterative_rrnee", 3)])
+def test_device_parity_cases(ref, scene_dir, scene, w, h, integrator, spp):
+    """The cases of tests/test_gpu_parity.py::test_vs_reference_build_bitexact that no test above
+    renders: the device test reads them from the same record where the library is not built."""
+    path = os.path.join(scene_dir, scene)
+    t = sp.string_to_integrator_type(integrator)
+    ids = np.arange(sp.TileScheduler(w, h).get_num_tiles(), dtype=np.int32)
+    r = ref_render(ref, path, w, h, t, spp, ids)
+    o = oracle_render(path, w, h, t, spp, ids)
     assert same(r, o), (scene, integrator, float(np.abs(r - o).max()))
     assert r.max() > 0.0
 

@@ -15,7 +15,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || { tail -20 "$out/smoke.log"; exit 1; }
   tail -1 "$out/smoke.log"
 fi
-timeout -k 10 300 python -u bench.py ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
 cat "$out/bench.json"
 if [ -n "${PROF:-}" ]; then
   (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out/rocprof -o run -- python3 $R/bench.py --no-cpu ${BENCH_ARGS:-} > $R/$out/rocprof_bench.json 2> $R/$out/rocprof.err) \

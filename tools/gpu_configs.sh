@@ -12,14 +12,14 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out/cfg
 declare -A A=(
-  [spheres]="--scene spheres --steps 3 --warmup 1"
-  [bunny_scan]="--scene bunny_scan --steps 3 --warmup 1"
-  [bunny_shard2]="--steps 3 --warmup 1 --sim-world 2"
-  [bunny_shard4]="--steps 3 --warmup 1 --sim-world 4"
-  [bunny_shard8]="--steps 3 --warmup 1 --sim-world 8"
-  [lucy1]="--scene lucy --steps 3 --warmup 1"
-  [lucy8]="--scene lucy --steps 3 --warmup 1 --sim-world 8"
-  [elf8]="--scene elf --steps 3 --warmup 0 --sim-world 8"
+  [spheres]="--scene spheres --steps 3 --warmup 1 --full"
+  [bunny_scan]="--scene bunny_scan --steps 3 --warmup 1 --full"
+  [bunny_shard2]="--steps 3 --warmup 1 --sim-world 2 --full"
+  [bunny_shard4]="--steps 3 --warmup 1 --sim-world 4 --full"
+  [bunny_shard8]="--steps 3 --warmup 1 --sim-world 8 --full"
+  [lucy1]="--scene lucy --steps 3 --warmup 1 --full"
+  [lucy8]="--scene lucy --steps 3 --warmup 1 --sim-world 8 --full"
+  [elf8]="--scene elf --steps 3 --warmup 0 --sim-world 8 --full"
 )
 for n in ${CONFIGS:-spheres bunny_scan bunny_shard2 bunny_shard4 bunny_shard8 lucy1 lucy8 elf8}; do
   timeout -k 10 1000 python -u bench.py ${A[$n]} ${BENCH_ARGS:-} > gpurun_out/cfg/$n.json 2> gpurun_out/cfg/$n.err || { tail -5 gpurun_out/cfg/$n.err; exit 1; }
