@@ -261,6 +261,88 @@ inline Image render_image(const Integrator& integrator, unsigned num_pixel_sampl
     return img;
 }
 
+// Resumable render (sp_progress): render_more(n) adds n samples per pixel; after calls with n1, n2,
+// ... samples image() is render_image's at n1 + n2 + ... samples, bit for bit.  Holds the pixels'
+// carried state on the device (2520 bytes per pixel slot) until destroyed; the Scene must outlive
+// it and stay uploaded as it is (set_resolution or an upload with other options invalidates it:
+// the next call throws).  tiles: ColumnMajor tile indices, empty = every tile.  Move-only.
+class ProgressiveRender {
+public:
+    ProgressiveRender(const Scene& scene, IntegratorType type, std::vector<int32_t> tiles = {})
+        : m_ids(std::move(tiles)), m_w(scene.image_width), m_h(scene.image_height)
+    {
+        if (sp_scene_bvh_info(scene.handle(), nullptr, nullptr, nullptr) != SP_OK) scene.upload(0, 0); // not resident yet
+        if (m_ids.empty()) {
+            ColumnMajorTileScheduler scheduler{ m_w, m_h, 1 };
+            while (auto t = scheduler.get_next_tile()) m_ids.push_back(t->index);
+        }
+        sp_progress_params p{};
+        p.struct_size = sizeof(p);
+        p.integrator  = static_cast<int32_t>(type);
+        p.tile_ids    = m_ids.data();
+        p.num_tiles   = static_cast<int64_t>(m_ids.size());
+        check(sp_progress_create(scene.handle(), &p, &m_p));
+        m_tiles.assign(m_ids.size() * 64 * 3, 0.0f);
+    }
+    ProgressiveRender(ProgressiveRender&& o) noexcept { *this = std::move(o); }
+    ProgressiveRender& operator=(ProgressiveRender&& o) noexcept
+    {
+        std::swap(m_p, o.m_p);
+        m_ids   = std::move(o.m_ids);
+        m_tiles = std::move(o.m_tiles);
+        m_w     = o.m_w;
+        m_h     = o.m_h;
+        return *this;
+    }
+    ProgressiveRender(const ProgressiveRender&)            = delete;
+    ProgressiveRender& operator=(const ProgressiveRender&) = delete;
+    ~ProgressiveRender() { sp_progress_free(m_p); }
+
+    // n more samples for every pixel; the statistics are this call's
+    sp_render_stats render_more(unsigned n)
+    {
+        sp_render_stats st{};
+        check(sp_progress_render_host(m_p, n, m_tiles.data(), &st));
+        return st;
+    }
+    unsigned samples() const
+    {
+        uint32_t n = 0;
+        check(sp_progress_samples(m_p, &n));
+        return n;
+    }
+    // the image of all samples so far (pixels of tiles not in the list stay 0)
+    Image image() const
+    {
+        Image img;
+        img.width  = m_w;
+        img.height = m_h;
+        img.rgb.assign(static_cast<size_t>(m_w) * m_h * 3, 0.0f);
+        check(sp_tiles_to_image(m_w, m_h, m_ids.data(), static_cast<int64_t>(m_ids.size()), m_tiles.data(), img.rgb.data()));
+        return img;
+    }
+    // checkpoint: tiles x 64 records (slot * 64 + morton); the samples they hold in *samples
+    std::vector<sp_pixel_state> export_state(unsigned* samples) const
+    {
+        std::vector<sp_pixel_state> st(m_ids.size() * 64);
+        uint32_t                    n = 0;
+        check(sp_progress_export(m_p, st.data(), static_cast<int64_t>(st.size()), &n));
+        if (samples) *samples = n;
+        return st;
+    }
+    void import_state(const std::vector<sp_pixel_state>& st, unsigned samples)
+    {
+        check(sp_progress_import(m_p, st.data(), static_cast<int64_t>(st.size()), samples));
+    }
+    sp_progress* handle() const noexcept { return m_p; }
+
+private:
+    sp_progress*         m_p = nullptr;
+    std::vector<int32_t> m_ids;
+    std::vector<float>   m_tiles; // tile-packed radiance of the last render_more
+    int                  m_w = 0, m_h = 0;
+};
+
 // render (main.cpp:109-141): integrate every pixel and write scene.output_file_name (PFM,
 // Image/Image.cpp:40).  num_threads is accepted for signature compatibility; the GPU does the work.
 inline void render(const Integrator& integrator, unsigned /*num_threads*/, unsigned num_pixel_samples, const Scene& scene)

@@ -360,6 +360,62 @@ int  sp_tiles_to_image(int32_t width, int32_t height, const int32_t* tile_ids, i
 /* Write an image as PFM exactly as Image/Image.cpp:40 write_pfm does. */
 int  sp_write_pfm(const char* path, int32_t width, int32_t height, const float* image);
 
+/* ---- progressive renders ------------------------------------------------------------------
+ * Render some samples, look at the image, render more: N calls of k samples give the image of one
+ * sp_render_tiles call with N x k samples, bit for bit (every integrator, light kind and BVH mode).
+ * A progress object keeps, per pixel slot of its tile list, what the reference's sample loop
+ * carries from one sample to the next (main.cpp:94-102): the sampler state, image(p) before the
+ * division, and the number of samples done (also the R2 index).  It owns that device memory
+ * (2520 bytes per pixel slot; the device_bytes call reports it) until it is freed; nothing is kept
+ * on the scene.  The scene must outlive the progress object, and a scene uploaded again with other
+ * options or given another resolution invalidates it: every later call returns SP_ERR_STATE.
+ * Calls run the megakernel, take the scene's lock and stream ordering like sp_render_tiles, and may
+ * be mixed with it. */
+#define SP_HAS_PROGRESS 1
+
+typedef struct sp_progress sp_progress;
+
+typedef struct sp_progress_params {     /* zero-initialise; struct_size = sizeof */
+    uint32_t       struct_size;         /* a size the library does not know => SP_ERR_ARG             */
+    int32_t        integrator;          /* as sp_render_params.integrator                              */
+    const int32_t* tile_ids;            /* host list, copied; NULL => d_tile_ids or all tiles          */
+    const int32_t* d_tile_ids;          /* device list, copied at creation                             */
+    int64_t        num_tiles;
+    int32_t        waves_per_simd;      /* as sp_render_params                                         */
+    float          tile_order_factor;   /* as sp_render_params, without its samples threshold; the
+                                           order is probed by the first call and kept                  */
+    int32_t        reserved[2];         /* must be 0                                                   */
+} sp_progress_params;
+
+/* One pixel's carried state, host format (export / import).  mt / mt_pos are std::mt19937_64's own
+ * _M_x / _M_p: streaming them into a std::mt19937_64 with operator>> continues the pixel's stream. */
+typedef struct sp_pixel_state {
+    uint64_t mt[312];
+    uint64_t mt_pos;     /* 0..312 */
+    uint64_t draws;      /* words drawn from the stream so far */
+    float    sum[3];     /* image(p) before /= samples */
+    uint32_t reserved;   /* 0 */
+} sp_pixel_state;        /* 2528 bytes */
+
+int  sp_progress_create(sp_scene* scene, const sp_progress_params* params, sp_progress** out);
+void sp_progress_free(sp_progress* progress);
+/* Adds more_samples (>= 1) to every pixel and writes the image of all samples so far, tile-packed as
+ * sp_render_tiles does, into d_out (may be NULL: accumulate only).  Stream-ordered like
+ * sp_render_tiles: with stats == NULL the call only enqueues work.  stats counts this call only. */
+int  sp_progress_render(sp_progress* progress, uint32_t more_samples, void* stream, float* d_out,
+                        sp_render_stats* stats);
+/* The same with a device buffer of its own, copied back into h_out (num_tiles * 64 * 3 floats). */
+int  sp_progress_render_host(sp_progress* progress, uint32_t more_samples, float* h_out, sp_render_stats* stats);
+int  sp_progress_samples(const sp_progress* progress, uint32_t* out);
+int  sp_progress_device_bytes(const sp_progress* progress, int64_t* out);
+/* Checkpoint: num_tiles * 64 records, record slot * 64 + morton; capacity in records.  Pixels of
+ * clipped border tiles outside the image export as zero records and are ignored on import.  Import
+ * takes what export wrote, into a progress object of the same tile list on the same scene file
+ * (another scene handle or process included); it checks mt_pos <= 312 and reserved == 0.  Both
+ * wait for the object's queued renders. */
+int  sp_progress_export(sp_progress* progress, sp_pixel_state* h_states, int64_t capacity, uint32_t* samples);
+int  sp_progress_import(sp_progress* progress, const sp_pixel_state* h_states, int64_t count, uint32_t samples);
+
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the
  * reference's images are those of the CPU it ran on.  By default scenes are built (host) and

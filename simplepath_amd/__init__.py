@@ -24,7 +24,7 @@ from ._abi import INTEGRATORS, SimplePathError, check, lib
 __all__ = [
     "Scene", "TileScheduler", "ColumnMajorTileScheduler", "RenderStats", "render", "render_tiles",
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
-    "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table",
+    "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -259,6 +259,100 @@ def render_tiles_device(scene: Scene, integrator, num_pixel_samples: int, tile_i
     st = _abi.sp_render_stats()
     check(lib().sp_render_tiles(scene.handle, C.byref(p), C.c_void_p(out_ptr), C.byref(st)))
     return _stats(st)
+
+
+# sp_pixel_state (include/simplepath_hip.h): one pixel's carried state in a checkpoint
+PIXEL_STATE_DTYPE = np.dtype([("mt", "<u8", (312,)), ("mt_pos", "<u8"), ("draws", "<u8"), ("sum", "<f4", (3,)),
+                              ("reserved", "<u4")])
+
+
+class Progressive:
+    """Resumable render of one tile list (sp_progress): render(n) adds n samples per pixel, and the
+    image after calls with n1, n2, ... samples is render_tiles' image at n1 + n2 + ... samples, bit
+    for bit.  Holds 2520 bytes of device memory per pixel slot until close().  The scene must stay
+    uploaded as it is: upload() with other options or set_resolution() invalidates the object.
+
+        prog = Progressive(scene, "direct_lighting")
+        while not good_enough(img):
+            tiles, stats = prog.render(16)
+            img = tiles_to_image(scene.width, scene.height, tiles)
+    """
+
+    def __init__(self, scene: Scene, integrator=None, tile_ids: Optional[Sequence[int]] = None, waves_per_simd: int = 0,
+                 tile_order_factor: float = 0.0, d_tile_ids: int = 0, num_tiles: int = 0):
+        if isinstance(integrator, str):
+            integrator = string_to_integrator_type(integrator)
+        p = _abi.sp_progress_params()
+        p.struct_size = C.sizeof(_abi.sp_progress_params)
+        p.integrator = int(integrator or 0)
+        keep = None
+        if tile_ids is not None:
+            keep = np.ascontiguousarray(np.asarray(tile_ids), dtype=np.int32)
+            p.tile_ids = keep.ctypes.data_as(C.POINTER(C.c_int32))
+            p.num_tiles = keep.size
+        elif d_tile_ids:
+            p.d_tile_ids = C.c_void_p(d_tile_ids)
+            p.num_tiles = int(num_tiles)
+        p.waves_per_simd = int(waves_per_simd)
+        p.tile_order_factor = float(tile_order_factor)
+        self._h = C.c_void_p()
+        self._scene = scene  # the scene outlives the progress object
+        check(lib().sp_progress_create(scene.handle, C.byref(p), C.byref(self._h)))
+        self.num_tiles = int(p.num_tiles) if (keep is not None or d_tile_ids) else \
+            TileScheduler(scene.width, scene.height).get_num_tiles()
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h and _abi._lib is not None:
+            _abi._lib.sp_progress_free(h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def samples(self) -> int:
+        n = C.c_uint32()
+        check(lib().sp_progress_samples(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def device_bytes(self) -> int:
+        b = C.c_int64()
+        check(lib().sp_progress_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def render(self, n: int, out_ptr: Optional[int] = None, stream=None, stats: bool = True):
+        """Add n samples per pixel; returns (tile-packed radiance of all samples so far [tiles, 64, 3],
+        RenderStats of this call).  out_ptr: a caller-owned device buffer of tiles * 64 * 3 floats
+        (e.g. a torch tensor's data_ptr()); the call then returns (None, stats), and with stats=False
+        it only enqueues the work on `stream` and returns (None, None).  Without out_ptr the image
+        comes back in host memory (sp_progress_render_host; `stream` is not used)."""
+        st = _abi.sp_render_stats() if stats else None
+        if out_ptr is not None:
+            check(lib().sp_progress_render(self._h, int(n), stream, C.c_void_p(out_ptr), C.byref(st) if stats else None))
+            return None, (_stats(st) if stats else None)
+        out = np.zeros((max(self.num_tiles, 1), 64, 3), dtype=np.float32)
+        check(lib().sp_progress_render_host(self._h, int(n), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                            C.byref(st) if stats else None))
+        return out[:self.num_tiles], (_stats(st) if stats else None)
+
+    def export_state(self):
+        """Checkpoint: (structured array of tiles * 64 PIXEL_STATE_DTYPE records, samples)."""
+        arr = np.zeros(self.num_tiles * 64, dtype=PIXEL_STATE_DTYPE)
+        n = C.c_uint32()
+        check(lib().sp_progress_export(self._h, C.c_void_p(arr.ctypes.data), arr.size, C.byref(n)))
+        return arr, n.value
+
+    def import_state(self, arr: np.ndarray, samples: int) -> None:
+        """Continue from a checkpoint export_state() wrote (same tile list, same scene file)."""
+        a = np.ascontiguousarray(arr, dtype=PIXEL_STATE_DTYPE)
+        check(lib().sp_progress_import(self._h, C.c_void_p(a.ctypes.data), a.size, int(samples)))
 
 
 def tiles_to_image(width: int, height: int, tiles: np.ndarray, tile_ids: Optional[np.ndarray] = None) -> np.ndarray:

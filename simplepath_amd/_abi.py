@@ -123,8 +123,27 @@ class sp_bvh_info(C.Structure):
                 ("stack_depth", C.c_int32), ("nodes", C.c_int64), ("slots", C.c_int64)]
 
 
+class sp_progress_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
+                ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
+                ("waves_per_simd", C.c_int32), ("tile_order_factor", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class sp_pixel_state(C.Structure):
+    _fields_ = [("mt", C.c_uint64 * 312), ("mt_pos", C.c_uint64), ("draws", C.c_uint64),
+                ("sum", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 # Every symbol declared in include/simplepath_hip.h, with its ctypes signature.
 SIGNATURES = {
+    "sp_progress_create": (C.c_int, [C.c_void_p, C.POINTER(sp_progress_params), C.POINTER(C.c_void_p)]),
+    "sp_progress_free": (None, [C.c_void_p]),
+    "sp_progress_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(sp_render_stats)]),
+    "sp_progress_render_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(sp_render_stats)]),
+    "sp_progress_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "sp_progress_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "sp_progress_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint32)]),
+    "sp_progress_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32]),
     "sp_version": (C.c_char_p, []),
     "sp_build_id": (C.c_char_p, []),
     "sp_last_error": (C.c_char_p, []),

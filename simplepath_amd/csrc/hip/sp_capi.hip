@@ -28,6 +28,10 @@ hipError_t launch_probe(const Scene& sc, const RenderArgs& args, int integ, int 
                         hipStream_t stream);
 hipError_t launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream);
 int        tail_blocks_per_cu(int variant, size_t lds_bytes);
+hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, int integ, int variant, int blocks,
+                         size_t lds_bytes, hipStream_t stream);
+int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
+size_t     resume_static_lds(int integ, int variant);
 } // namespace spd
 
 namespace {
@@ -261,6 +265,9 @@ struct sp_scene {
     hipEvent_t           ev_tiles[STAGE_RING]    = {};  // after each buffer's staged copy
     bool                 tiles_rec[STAGE_RING]   = {};
     int                  stage_next = 0;
+    // counts every change that invalidates a progress object made on this scene (sp_progress):
+    // a new upload (the device scene is rebuilt) and sp_scene_set_resolution
+    uint64_t             generation = 0;
 
     void release()
     {
@@ -332,6 +339,38 @@ struct sp_scene {
         *out = static_cast<const T*>(b.p);
         return SP_OK;
     }
+};
+
+// Progressive render (include/simplepath_hip.h): the carried per-pixel state of one tile list, in
+// device memory this object owns.  Layout: sp_device.hpp ResumeArgs.
+struct sp_progress {
+    sp_scene*            scene      = nullptr;
+    uint64_t             generation = 0; // the scene's when this was created
+    int                  device     = -1;
+    int32_t              integ      = 0;
+    int                  waves_req  = 0;
+    float                order_factor = 0.0f;
+    bool                 listed     = false;
+    int64_t              n_tiles    = 0;
+    int32_t              width = 0, height = 0;
+    std::vector<int32_t> h_ids;          // the list (host copy; empty: slot = tile)
+    int32_t*             d_ids   = nullptr;
+    spd::ResumeArgs      st{};           // gen / pos / draws / sum; n0 = samples done
+    float*               d_tile_time = nullptr; // tile order, probed by the first call and kept
+    int32_t*             d_order     = nullptr;
+    bool                 order_tried = false, ordered = false;
+    int64_t              bytes = 0;
+
+    void release()
+    {
+        if (device >= 0) (void)hipSetDevice(device);
+        for (void* p : { (void*)d_ids, (void*)st.gen, (void*)st.pos, (void*)st.draws, (void*)st.sum, (void*)d_tile_time,
+                         (void*)d_order })
+            if (p) (void)hipFree(p); // (waits for kernels that still use it)
+        d_ids = nullptr; d_tile_time = nullptr; d_order = nullptr;
+        st    = spd::ResumeArgs{};
+    }
+    ~sp_progress() { release(); }
 };
 
 namespace {
@@ -568,6 +607,7 @@ int sp_scene_set_resolution(sp_scene* scene, int32_t width, int32_t height)
     scene->host->image_width  = width;
     scene->host->image_height = height;
     scene->host->rebuild_camera();
+    ++scene->generation;
     fill_desc(scene);
     if (scene->device >= 0) {
         scene->dev.width  = width;
@@ -666,6 +706,7 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     if (device < 0 || device >= ndev) return fail(SP_ERR_ARG, "device out of range");
     if (s->device == device && s->opts == opts) return SP_OK;
     s->release();
+    ++s->generation;
     SP_HIP(hipSetDevice(device));
     s->device   = device;
     s->bvh_mode = bvh_mode;
@@ -1701,6 +1742,391 @@ int sp_render_tiles_host(sp_scene* s, const sp_render_params* p, float* h_out, s
     }
     (void)hipFree(d);
     return rc;
+}
+
+// ---- progressive renders (sp_progress) ---------------------------------------------------------
+
+// pixel (x, y) of record slot * 64 + m; false: outside the image (a clipped border tile, or a
+// device list's id outside the frame)
+static bool progress_pixel(const sp_progress* g, int64_t slot, uint32_t m, int32_t& x, int32_t& y)
+{
+    const int32_t tw    = (g->width + 7) / 8;
+    const int64_t total = (int64_t)tw * ((g->height + 7) / 8);
+    const int64_t t     = g->listed ? g->h_ids[(size_t)slot] : slot;
+    if (t < 0 || t >= total) return false;
+    uint32_t a = m & 0x55u, b = (m >> 1) & 0x55u;
+    a = (a | (a >> 1)) & 0x33u; a = (a | (a >> 2)) & 0x0fu;
+    b = (b | (b >> 1)) & 0x33u; b = (b | (b >> 2)) & 0x0fu;
+    x = (int32_t)(t % tw) * 8 + (int32_t)a;
+    y = (int32_t)(t / tw) * 8 + (int32_t)b;
+    return x < g->width && y < g->height;
+}
+
+static int progress_live(const sp_progress* g)
+{
+    const sp_scene* s = g->scene;
+    if (s->generation != g->generation || s->device != g->device)
+        return fail(SP_ERR_STATE, "the scene was uploaded again or resized after sp_progress_create");
+    return SP_OK;
+}
+
+static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_progress** out)
+{
+    if (p->struct_size != sizeof(sp_progress_params)) return fail(SP_ERR_ARG, "sp_progress_params.struct_size is not this library's");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_progress_params.reserved must be 0");
+    if (p->tile_ids && p->d_tile_ids) return fail(SP_ERR_ARG, "give tile_ids (host) or d_tile_ids (device), not both");
+    if (p->tile_order_factor != p->tile_order_factor) return fail(SP_ERR_ARG, "tile_order_factor is NaN");
+    const bool listed = p->tile_ids || p->d_tile_ids;
+    if (listed && p->num_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_progress_create");
+    int32_t integ = p->integrator;
+    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = s->host->integrator;
+    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = SP_INTEGRATOR_DIRECT_LIGHTING; // main.cpp:390
+    if (integ < SP_INTEGRATOR_MANDELBROT || integ > SP_INTEGRATOR_WHITTED) return fail(SP_ERR_ARG, "Unknown integrator type");
+    if (p->waves_per_simd != 0) {
+        const int  w  = p->waves_per_simd;
+        const bool ok = integ == SP_INTEGRATOR_DIRECT_LIGHTING ? (w >= 1 && w <= 4)
+                        : integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? (w >= 2 && w <= 4)
+                                                                  : false;
+        if (!ok) return fail(SP_ERR_ARG, "waves_per_simd: DirectLighting 1-4, IterativeRRNEE 2-4, else 0");
+    }
+    int64_t total;
+    sp_tile_count(s->dev.width, s->dev.height, &total);
+    const int64_t n_tiles = listed ? p->num_tiles : total;
+    if (p->tile_ids)
+        for (int64_t i = 0; i < n_tiles; ++i)
+            if (p->tile_ids[i] < 0 || p->tile_ids[i] >= total) return fail(SP_ERR_ARG, "tile id out of range");
+    SP_HIP(hipSetDevice(s->device));
+    std::unique_ptr<sp_progress> g(new sp_progress());
+    g->scene        = s;
+    g->generation   = s->generation;
+    g->device       = s->device;
+    g->integ        = integ;
+    g->waves_req    = p->waves_per_simd;
+    g->order_factor = p->tile_order_factor;
+    g->listed       = listed;
+    g->n_tiles      = n_tiles;
+    g->width        = s->dev.width;
+    g->height       = s->dev.height;
+    const size_t nt = (size_t)std::max<int64_t>(1, n_tiles);
+    if (listed) {
+        g->h_ids.assign(nt, 0);
+        if (p->tile_ids) std::memcpy(g->h_ids.data(), p->tile_ids, (size_t)n_tiles * sizeof(int32_t));
+        else if (n_tiles > 0)
+            SP_HIP(hipMemcpy(g->h_ids.data(), p->d_tile_ids, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost));
+        SP_HIP(hipMalloc(&g->d_ids, nt * sizeof(int32_t)));
+        SP_HIP(hipMemcpy(g->d_ids, g->h_ids.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice));
+        g->bytes += (int64_t)(nt * sizeof(int32_t));
+    }
+    const size_t b_gen = nt * (size_t)spd::MT_GEN_WORDS * 8, b_pos = nt * 64 * 4, b_draws = nt * 64 * 8, b_sum = nt * 192 * 4;
+    SP_HIP(hipMalloc(&g->st.gen, b_gen));
+    SP_HIP(hipMalloc(&g->st.pos, b_pos));
+    SP_HIP(hipMalloc(&g->st.draws, b_draws));
+    SP_HIP(hipMalloc(&g->st.sum, b_sum));
+    SP_HIP(hipMemset(g->st.gen, 0, b_gen)); // pixels outside the image stay zero: they export as zero records
+    SP_HIP(hipMemset(g->st.pos, 0, b_pos));
+    SP_HIP(hipMemset(g->st.draws, 0, b_draws));
+    SP_HIP(hipMemset(g->st.sum, 0, b_sum));
+    g->bytes += (int64_t)(b_gen + b_pos + b_draws + b_sum);
+    *out = g.release();
+    return SP_OK;
+}
+
+int sp_progress_create(sp_scene* s, const sp_progress_params* p, sp_progress** out)
+{
+    if (!s || !p || !out) return fail(SP_ERR_ARG, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    try {
+        return progress_create_impl(s, p, out);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_progress_create failed: ") + e.what());
+    }
+}
+
+void sp_progress_free(sp_progress* g) { delete g; }
+
+static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t stream, float* d_out, sp_render_stats* stats)
+{
+    sp_scene* s = g->scene;
+    if (int rc = progress_live(g)) return rc;
+    if (more == 0) return fail(SP_ERR_ARG, "more_samples must be > 0");
+    if ((uint64_t)g->st.n0 + more > UINT32_MAX) return fail(SP_ERR_ARG, "more than UINT32_MAX samples in all");
+    if (stats) *stats = sp_render_stats{};
+    SP_HIP(hipSetDevice(s->device));
+    const int64_t n_tiles = g->n_tiles;
+    if (n_tiles == 0) {
+        g->st.n0 += more;
+        return SP_OK;
+    }
+    // the scene's scratch (mt_state, counters) is shared with sp_render_tiles: same ordering
+    if (s->done_rec) SP_HIP(hipStreamWaitEvent(stream, s->ev_done, 0));
+    if (s->n_cu == 0) {
+        hipDeviceProp_t prop;
+        SP_HIP(hipGetDeviceProperties(&prop, s->device));
+        s->n_cu = prop.multiProcessorCount;
+    }
+    const int integ = g->integ;
+    // LDS, occupancy variant, persistent blocks: as the megakernel branch of render_tiles_impl
+    const int    rs_words  = spd::rsqrt_words(s->dev);
+    const size_t lds_bytes = (size_t)rs_words * 4 + (size_t)4 * s->dev.stack_words * 64 * 4;
+    size_t       lds_static = 0;
+    for (int v = 2; v <= 4; ++v) lds_static = std::max(lds_static, spd::resume_static_lds(integ, v));
+    const size_t lds_all = lds_bytes + lds_static;
+    if (lds_all > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    const int lds_waves = (int)std::min<size_t>(8, (160 * 1024) / lds_all);
+    int       variant   = integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? 3 : 4;
+    variant             = std::max(2, std::min(variant, lds_waves));
+    if (g->waves_req) variant = g->waves_req;
+    const int     per_cu = spd::resume_blocks_per_cu(integ, variant, lds_bytes);
+    const int     blocks = (int)std::max<int64_t>(1, std::min((int64_t)s->n_cu * per_cu, (n_tiles + 3) / 4));
+    const size_t  waves  = (size_t)blocks * 4;
+    if (waves > s->mt_waves) {
+        if (s->mt_state) (void)hipFree(s->mt_state);
+        s->mt_state = nullptr;
+        s->mt_waves = 0;
+        SP_HIP(hipMalloc(&s->mt_state, waves * 2 * (size_t)spd::MT_GEN_WORDS * sizeof(uint64_t)));
+        s->mt_waves = waves;
+    }
+    SP_HIP(hipMemsetAsync(s->counters, 0, 8 * sizeof(unsigned long long), stream));
+    SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
+    spd::Scene sc_run    = s->dev;
+    sc_run.merge_queries = 1;
+    spd::RenderArgs a{};
+    a.out          = d_out;
+    a.tile_ids     = g->d_ids;
+    a.num_tiles    = n_tiles;
+    a.tiles_x      = (s->dev.width + 7) / 8;
+    a.spp          = more;
+    a.integrator   = integ;
+    a.tile_counter = s->tile_counter;
+    a.mt_state     = s->mt_state;
+    a.counters     = s->counters;
+    if ((integ == SP_INTEGRATOR_BRUTE_FORCE || integ == SP_INTEGRATOR_WHITTED) && s->dev.max_depth > MAX_RECURSION) {
+        const size_t lanes = waves * 64;
+        const size_t bytes = lanes * ((size_t)s->dev.max_depth + 1) * 5 * sizeof(float);
+        if (bytes > s->deep_cap) {
+            if (s->deep_buf) (void)hipFree(s->deep_buf);
+            s->deep_buf = nullptr;
+            s->deep_cap = 0;
+            SP_HIP(hipMalloc(&s->deep_buf, bytes));
+            s->deep_cap = bytes;
+        }
+        a.deep        = static_cast<float*>(s->deep_buf);
+        a.deep_stride = lanes;
+    }
+    SP_HIP(hipEventRecord(s->ev0, stream));
+    int launches = 1;
+    // Tile order (render_tiles_impl): the one-sample probe runs in the first call and its order is
+    // kept -- it only permutes the tiles.  Automatic from the same tiles per wave as a one-shot
+    // render (whose samples threshold has no counterpart here: a call does not know the total).
+    if (!g->order_tried) {
+        g->order_tried = true;
+        const bool rrnee = integ == SP_INTEGRATOR_ITERATIVE_RRNEE;
+        float      hoist = n_tiles >= (rrnee ? 4 : 6) * (int64_t)waves ? 2.0f : 0.0f;
+        if (g->order_factor != 0.0f) hoist = std::max(0.0f, g->order_factor);
+        if (hoist > 0.0f && n_tiles > (int64_t)waves && spd::has_probe(integ)) {
+            SP_HIP(hipMalloc(&g->d_tile_time, (size_t)n_tiles * sizeof(float)));
+            SP_HIP(hipMalloc(&g->d_order, (size_t)n_tiles * sizeof(int32_t)));
+            g->bytes += (int64_t)n_tiles * 8;
+            if (!s->probe_counters) SP_HIP(hipMalloc(&s->probe_counters, 8 * sizeof(unsigned long long)));
+            spd::RenderArgs pr = a;
+            pr.out        = nullptr;
+            pr.spp        = 1;
+            pr.tile_time  = g->d_tile_time;
+            pr.counters   = s->probe_counters;
+            pr.probe_step = 1;
+            SP_HIP(spd::launch_probe(sc_run, pr, integ, variant, blocks, lds_bytes, stream));
+            sp_render_params np{};
+            np.tile_ids = g->listed ? g->h_ids.data() : nullptr;
+            SP_HIP(spd::launch_tile_order(g->d_tile_time, n_tiles, hoist, order_neighbours(&np, g->listed, n_tiles, a.tiles_x), 1,
+                                          g->d_order, stream));
+            SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
+            g->ordered = true;
+            launches += 2;
+        }
+    }
+    a.order = g->ordered ? g->d_order : nullptr;
+    SP_HIP(spd::launch_resume(sc_run, a, g->st, integ, variant, blocks, lds_bytes, stream));
+    SP_HIP(hipEventRecord(s->ev1, stream));
+    SP_HIP(hipEventRecord(s->ev_done, stream));
+    s->done_rec = true;
+    g->st.n0 += more;
+    if (stats) {
+        SP_HIP(hipEventSynchronize(s->ev1));
+        unsigned long long c[8];
+        SP_HIP(hipMemcpy(c, s->counters, sizeof(c), hipMemcpyDeviceToHost));
+        float ms = 0.0f;
+        SP_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        stats->rays        = c[0];
+        stats->shadow_rays = c[1];
+        stats->samples     = c[2];
+        stats->rng_draws   = c[3];
+        stats->kernel_ms   = ms;
+        stats->pipeline    = SP_PIPELINE_MEGAKERNEL;
+        stats->launches    = launches;
+        stats->parts       = 1;
+        stats->stack_depth = s->dev.stack_depth;
+    }
+    return SP_OK;
+}
+
+int sp_progress_render(sp_progress* g, uint32_t more_samples, void* stream, float* d_out, sp_render_stats* stats)
+{
+    if (!g) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return progress_render_impl(g, more_samples, static_cast<hipStream_t>(stream), d_out, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_progress_render failed: ") + e.what());
+    }
+}
+
+int sp_progress_render_host(sp_progress* g, uint32_t more_samples, float* h_out, sp_render_stats* stats)
+{
+    if (!g || !h_out) return fail(SP_ERR_ARG, "null argument");
+    if (g->scene->device < 0) return fail(SP_ERR_STATE, "the scene is no longer uploaded");
+    SP_HIP(hipSetDevice(g->scene->device));
+    const size_t bytes = (size_t)g->n_tiles * 64 * 3 * sizeof(float);
+    float*       d     = nullptr;
+    SP_HIP(hipMalloc(&d, std::max<size_t>(bytes, 4)));
+    int rc = sp_progress_render(g, more_samples, nullptr, d, stats);
+    if (rc == SP_OK && bytes) {
+        hipError_t e = hipMemcpy(h_out, d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int sp_progress_samples(const sp_progress* g, uint32_t* out)
+{
+    if (!g || !out) return fail(SP_ERR_ARG, "null argument");
+    *out = g->st.n0;
+    return SP_OK;
+}
+
+int sp_progress_device_bytes(const sp_progress* g, int64_t* out)
+{
+    if (!g || !out) return fail(SP_ERR_ARG, "null argument");
+    *out = g->bytes;
+    return SP_OK;
+}
+
+// Export / import move PROGRESS_BATCH tiles' generations at a time through a host buffer in the
+// device layout (160 KB per tile) and permute them on the host.
+static constexpr int64_t PROGRESS_BATCH = 128;
+
+static int progress_export_impl(sp_progress* g, sp_pixel_state* h, int64_t capacity, uint32_t* samples)
+{
+    sp_scene* s = g->scene;
+    if (int rc = progress_live(g)) return rc;
+    const int64_t n_px = g->n_tiles * 64;
+    if (capacity < n_px) return fail(SP_ERR_ARG, "capacity below num_tiles * 64 records");
+    *samples = g->st.n0;
+    if (n_px == 0) return SP_OK;
+    SP_HIP(hipSetDevice(s->device));
+    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    std::vector<uint32_t>           pos((size_t)n_px);
+    std::vector<unsigned long long> draws((size_t)n_px);
+    std::vector<float>              sum((size_t)g->n_tiles * 192);
+    SP_HIP(hipMemcpy(pos.data(), g->st.pos, pos.size() * 4, hipMemcpyDeviceToHost));
+    SP_HIP(hipMemcpy(draws.data(), g->st.draws, draws.size() * 8, hipMemcpyDeviceToHost));
+    SP_HIP(hipMemcpy(sum.data(), g->st.sum, sum.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> gen((size_t)std::min(PROGRESS_BATCH, g->n_tiles) * spd::MT_GEN_WORDS);
+    for (int64_t t0 = 0; t0 < g->n_tiles; t0 += PROGRESS_BATCH) {
+        const int64_t nb = std::min(PROGRESS_BATCH, g->n_tiles - t0);
+        if (g->st.n0 > 0)
+            SP_HIP(hipMemcpy(gen.data(), g->st.gen + (size_t)t0 * spd::MT_GEN_WORDS, (size_t)nb * spd::MT_GEN_WORDS * 8,
+                             hipMemcpyDeviceToHost));
+        for (int64_t sl = t0; sl < t0 + nb; ++sl)
+            for (uint32_t m = 0; m < 64; ++m) {
+                sp_pixel_state& r = h[sl * 64 + m];
+                std::memset(&r, 0, sizeof(r));
+                int32_t x, y;
+                if (!progress_pixel(g, sl, m, x, y)) continue;
+                if (g->st.n0 == 0) { // nothing rendered yet: the seeded engine (main.cpp:73), _M_p = n
+                    spm::Mt64 e;
+                    spm::mt_init(e, (((uint32_t)x << 16u) | (uint32_t)y) ^ 0xb0ae9d99u);
+                    std::memcpy(r.mt, e.x, sizeof(r.mt));
+                    r.mt_pos = spm::MT_N;
+                    continue;
+                }
+                const uint64_t* b = gen.data() + (size_t)(sl - t0) * spd::MT_GEN_WORDS + (size_t)m * spd::MT_BLK;
+                for (int k = 0; k < spm::MT_N; ++k) r.mt[k] = b[spd::mt_off(k)];
+                r.mt_pos = pos[(size_t)sl * 64 + m];
+                r.draws  = draws[(size_t)sl * 64 + m];
+                for (int c = 0; c < 3; ++c) r.sum[c] = sum[(size_t)sl * 192 + (size_t)c * 64 + m];
+            }
+    }
+    return SP_OK;
+}
+
+int sp_progress_export(sp_progress* g, sp_pixel_state* h_states, int64_t capacity, uint32_t* samples)
+{
+    if (!g || !h_states || !samples) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return progress_export_impl(g, h_states, capacity, samples);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_progress_export failed: ") + e.what());
+    }
+}
+
+static int progress_import_impl(sp_progress* g, const sp_pixel_state* h, int64_t count, uint32_t samples)
+{
+    sp_scene* s = g->scene;
+    if (int rc = progress_live(g)) return rc;
+    const int64_t n_px = g->n_tiles * 64;
+    if (count != n_px) return fail(SP_ERR_ARG, "count is not num_tiles * 64 records");
+    int32_t x, y;
+    for (int64_t i = 0; i < n_px; ++i) { // everything is checked before anything is written
+        if (!progress_pixel(g, i / 64, (uint32_t)(i % 64), x, y)) continue;
+        if (h[i].mt_pos > (uint64_t)spm::MT_N) return fail(SP_ERR_ARG, "sp_pixel_state.mt_pos above 312");
+        if (h[i].reserved != 0) return fail(SP_ERR_ARG, "sp_pixel_state.reserved must be 0");
+    }
+    if (n_px == 0) {
+        g->st.n0 = samples;
+        return SP_OK;
+    }
+    SP_HIP(hipSetDevice(s->device));
+    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    std::vector<uint32_t>           pos((size_t)n_px, 0u);
+    std::vector<unsigned long long> draws((size_t)n_px, 0ull);
+    std::vector<float>              sum((size_t)g->n_tiles * 192, 0.0f);
+    std::vector<uint64_t>           gen((size_t)std::min(PROGRESS_BATCH, g->n_tiles) * spd::MT_GEN_WORDS);
+    for (int64_t t0 = 0; t0 < g->n_tiles; t0 += PROGRESS_BATCH) {
+        const int64_t nb = std::min(PROGRESS_BATCH, g->n_tiles - t0);
+        std::fill(gen.begin(), gen.end(), 0ull);
+        for (int64_t sl = t0; sl < t0 + nb; ++sl)
+            for (uint32_t m = 0; m < 64; ++m) {
+                if (samples == 0 || !progress_pixel(g, sl, m, x, y)) continue; // (0 samples: the first call seeds)
+                const sp_pixel_state& r = h[sl * 64 + m];
+                uint64_t*             b = gen.data() + (size_t)(sl - t0) * spd::MT_GEN_WORDS + (size_t)m * spd::MT_BLK;
+                for (int k = 0; k < spm::MT_N; ++k) b[spd::mt_off(k)] = r.mt[k];
+                pos[(size_t)sl * 64 + m]   = (uint32_t)r.mt_pos;
+                draws[(size_t)sl * 64 + m] = r.draws;
+                for (int c = 0; c < 3; ++c) sum[(size_t)sl * 192 + (size_t)c * 64 + m] = r.sum[c];
+            }
+        SP_HIP(hipMemcpy(g->st.gen + (size_t)t0 * spd::MT_GEN_WORDS, gen.data(), (size_t)nb * spd::MT_GEN_WORDS * 8,
+                         hipMemcpyHostToDevice));
+    }
+    SP_HIP(hipMemcpy(g->st.pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    SP_HIP(hipMemcpy(g->st.draws, draws.data(), draws.size() * 8, hipMemcpyHostToDevice));
+    SP_HIP(hipMemcpy(g->st.sum, sum.data(), sum.size() * 4, hipMemcpyHostToDevice));
+    g->st.n0 = samples;
+    return SP_OK;
+}
+
+int sp_progress_import(sp_progress* g, const sp_pixel_state* h_states, int64_t count, uint32_t samples)
+{
+    if (!g || !h_states) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return progress_import_impl(g, h_states, count, samples);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_progress_import failed: ") + e.what());
+    }
 }
 
 int sp_tiles_to_image(int32_t width, int32_t height, const int32_t* tile_ids, int64_t num_tiles, const float* tiles,

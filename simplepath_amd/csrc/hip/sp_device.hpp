@@ -230,4 +230,16 @@ struct RenderArgs {
     int32_t         probe_step; // sp_probe_kernel: times every probe_step-th slot (the order kernel fills the rest)
 };
 
+// Progressive renders (sp_resume_kernel, sp_mega.hpp): what the reference's sample loop carries from
+// sample i to i + 1 (main.cpp:94-102), per pixel slot of the progress object's tile list.  A call
+// renders samples [n0, n0 + RenderArgs::spp); a third kernel argument, so RenderArgs and the
+// existing kernels stay as they are.
+struct ResumeArgs {
+    uint64_t*           gen;   // [slot] one generation, the wave slot's mt_off layout (MT_GEN_WORDS words)
+    uint32_t*           pos;   // [slot][64] next word of it, 0 .. 312
+    unsigned long long* draws; // [slot][64] words drawn from the stream so far
+    float*              sum;   // [slot][3][64] image(p) before the division
+    uint32_t            n0;    // samples done before this call (the R2 index of its first sample)
+};
+
 } // namespace spd

@@ -265,6 +265,87 @@ __device__ __forceinline__ void tail_chunk(const Scene& sc, const RenderArgs& ar
     draws_total += rng.draws;
 }
 
+// ------------------------------------------------------------------------ progressive renders
+// (ResumeArgs, sp_device.hpp; sp_resume_kernel below.)  A pixel's stream lives in its wave slot's
+// two-buffer ring only while its tile is being rendered; between calls one generation of it rests in
+// the progress object's store, in the wave slot's own layout, so both copies move whole rows: 32
+// contiguous bytes per lane, 2 KB per wave row.  The ring is reused tile after tile and stays in the
+// caches; a store consumed in place would stream every twist through HBM.
+
+// One generation, lane-blocked layout on both sides (src, dst: the lane's base in it).  Rows in
+// blocks of U, a block's loads all issued before its stores.
+__device__ __forceinline__ void resume_copy_gen(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst)
+{
+    constexpr int U = 6;
+    static_assert(MT_ROWS % U == 0, "whole blocks of rows");
+#pragma unroll 1
+    for (int r0 = 0; r0 < MT_ROWS; r0 += U) {
+        if constexpr (MT_BLK % 2 == 0) { // a lane's block is 16-byte aligned (rng_raw2)
+            ulonglong2 w[U][MT_BLK / 2];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int b = 0; b < MT_BLK / 2; ++b)
+                    w[j][b] = reinterpret_cast<const ulonglong2*>(src + (size_t)(r0 + j) * (64 * MT_BLK))[b];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int b = 0; b < MT_BLK / 2; ++b)
+                    reinterpret_cast<ulonglong2*>(dst + (size_t)(r0 + j) * (64 * MT_BLK))[b] = w[j][b];
+        } else {
+            uint64_t w[U][MT_BLK];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int b = 0; b < MT_BLK; ++b) w[j][b] = src[(size_t)(r0 + j) * (64 * MT_BLK) + b];
+#pragma unroll
+            for (int j = 0; j < U; ++j)
+#pragma unroll
+                for (int b = 0; b < MT_BLK; ++b) dst[(size_t)(r0 + j) * (64 * MT_BLK) + b] = w[j][b];
+        }
+    }
+}
+
+// Tile start of a pixel that has samples behind it: its generation into buffer 0 of the wave slot
+// -- every lane's, before the first sample, so IterativeRRNEE's served estimates find their owners'
+// words where (cur, idx) says -- and the running sum.  No read-ahead window, nothing served.
+__device__ __forceinline__ void resume_load(Rng& r, const ResumeArgs& ra, int64_t slot, int lane, rgb& acc)
+{
+    const size_t p = (size_t)slot * 64 + lane;
+    resume_copy_gen(ra.gen + (size_t)slot * MT_GEN_WORDS + (size_t)lane * MT_BLK, mt_buf(r, 0));
+    r.cur   = 0;
+    r.idx   = (int)ra.pos[p];
+    r.ready = 0;
+    r.draws = 0;
+    r.pfn   = 0;
+#if SP_SERVE_RHO
+    r.srv_on = 0;
+    r.srv_A  = false;
+    r.srv_B  = false;
+#endif
+    const float* s = ra.sum + (size_t)slot * 192 + lane;
+    acc            = mkc(s[0], s[64], s[128]);
+}
+
+// Tile end: the generation the NEXT draw reads.  With idx == 312 that is not buffer cur when the
+// other buffer is ready -- right after rng_seed_twisted buffer cur was never written (generation 1
+// sits in the other one), and the same shape arises when a pass ends on a generation's last word
+// after rng_prepare twisted ahead: then the other buffer from word 0.  With idx == 312 and nothing
+// ready, buffer cur at position 312 (the next draw twists it: std::mt19937_64's own _M_p == n).
+// Words read ahead (pf) are dropped: they are still in the buffer.
+__device__ __forceinline__ void resume_save(Rng& r, const ResumeArgs& ra, int64_t slot, int lane, rgb acc)
+{
+    const size_t p  = (size_t)slot * 64 + lane;
+    const bool   sw = r.idx >= MT_N && r.ready != 0;
+    resume_copy_gen(mt_buf(r, sw ? mt_next(r) : r.cur), ra.gen + (size_t)slot * MT_GEN_WORDS + (size_t)lane * MT_BLK);
+    ra.pos[p] = sw ? 0u : (uint32_t)r.idx;
+    ra.draws[p] += r.draws;
+    float* s = ra.sum + (size_t)slot * 192 + lane;
+    s[0]     = acc.r;
+    s[64]    = acc.g;
+    s[128]   = acc.b;
+}
+
 // Persistent kernel: 4 waves per block share the LDS RSQRTSS table; each wave independently
 // pulls 8x8 tiles from the queue (TileScheduler::get_next_tile) and owns one MT state slot.
 // One instantiation per integrator so each carries only its own live state; MINW is the
@@ -276,9 +357,12 @@ __device__ __forceinline__ void tail_chunk(const Scene& sc, const RenderArgs& ar
 // the same with an image light, its preps replaying Light::sample), 2 the sample-chunk pipeline's
 // fused form (preps from ck_camera's counts interleaved with the chunks, no whole tiles:
 // sp_fused_kernel).  One kernel per form, so each carries only its own code.
-template <int INTEG, bool PROBE, int TAIL = 0>
-__device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderArgs& args)
+// RESUME: a progressive call (sp_resume_kernel): samples [res->n0, res->n0 + spp) of every pixel, the
+// state before and after them in the progress object's store (resume_load / resume_save above).
+template <int INTEG, bool PROBE, int TAIL = 0, bool RESUME = false>
+__device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderArgs& args, const ResumeArgs* res = nullptr)
 {
+    static_assert(!RESUME || (!PROBE && TAIL == 0), "progressive calls run the plain megakernel form");
     extern __shared__ uint32_t lds[];
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
@@ -362,7 +446,10 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
         uint64_t       prof[4] = { 0, 0, 0, 0 };
         if (inside) {
             const uint32_t pix_seed = (px << 16u) | py;
-            if constexpr (!PROBE) { // get_integrator_sampler (main.cpp:73)
+            if constexpr (RESUME) { // the first call seeds as a one-shot render does
+                if (res->n0 == 0) rng_seed_twisted(rng, pix_seed ^ 0xb0ae9d99u);
+                else resume_load(rng, *res, slot, lane, acc);
+            } else if constexpr (!PROBE) { // get_integrator_sampler (main.cpp:73)
                 if (SP_SEED_FUSED) rng_seed_twisted(rng, pix_seed ^ 0xb0ae9d99u);
                 else rng_seed(rng, pix_seed ^ 0xb0ae9d99u);
             }
@@ -372,7 +459,12 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
                 c.deep    = args.deep + gwave * 64 + lane;
                 c.dstride = args.deep_stride;
             }
-            for (uint32_t i = 0; i < args.spp; ++i) {
+            uint32_t i_first = 0, i_end = args.spp;
+            if constexpr (RESUME) { // the R2 index runs on (Mandelbrot draws nothing but uses it)
+                i_first = res->n0;
+                i_end   = res->n0 + args.spp;
+            }
+            for (uint32_t i = i_first; i < i_end; ++i) {
                 rng_prepare(rng);
                 // RSequenceSampler::get_next_2D (math/Sampler.h:158) with count i
                 const float sx = rseq_component(seed2d, sc.alpha2_0, i);
@@ -388,7 +480,8 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
                 else
                     SP_WPROF(0, acc = cadd(acc, integrate<INTEG>(c, ray))); // image(p) += integrate(...)
             }
-            acc = cdivs(acc, (float)args.spp); // image(p) /= num_pixel_samples
+            if constexpr (RESUME) resume_save(rng, *res, slot, lane, acc); // undivided
+            acc = cdivs(acc, (float)i_end); // image(p) /= num_pixel_samples
 #ifdef SP_MEGA_PROF
             for (int k = 0; k < 4; ++k) prof[k] = c.prof[k];
 #endif
@@ -401,6 +494,8 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
             if (lane == 0) args.tile_time[slot] = (float)(__builtin_amdgcn_s_memrealtime() - t_start);
             continue;
         }
+        if constexpr (RESUME)
+            if (!args.out) continue; // accumulate only
         float* o = args.out + ((size_t)slot * 64 + lane) * 3;
         o[0]     = acc.r;
         o[1]     = acc.g;
@@ -442,6 +537,11 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_probe_kernel(Sc
 {
     render_tiles_body<INTEG, true>(sc, args);
 }
+template <int INTEG, int MINW>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_resume_kernel(Scene sc, RenderArgs args, ResumeArgs res)
+{
+    render_tiles_body<INTEG, false, 0, true>(sc, args, &res);
+}
 template <int MINW, bool REPLAY>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_tail_kernel(Scene sc, RenderArgs args)
 {
@@ -465,6 +565,16 @@ KernelFn probe_rrnee(int waves);
 KernelFn tail_direct(int variant, bool replay); // DirectLighting with tail chunks, 3 or 4 waves per SIMD
                                                  // (sp_mega_tail.hip; replay: an image light, 4 waves)
 KernelFn fused_chunks();           // the sample chunks' fused form, 4 waves per SIMD (sp_mega_tail.hip)
+// progressive calls (sp_mega_resume*.hip: each integrator with its one-shot kernel's sampler options)
+using ResumeFn = void (*)(Scene, RenderArgs, ResumeArgs);
+ResumeFn   resume_direct(int variant);
+ResumeFn   resume_mandelbrot();
+ResumeFn   resume_rrnee(int waves);
+ResumeFn   resume_path(int integ); // BruteForce, its iterative forms, Whitted
+hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, int integ, int variant, int blocks,
+                         size_t lds_bytes, hipStream_t stream);
+int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
+size_t     resume_static_lds(int integ, int variant);
 hipError_t launch_tile_order(float* tile_time, int64_t n_tiles, float factor, int tiles_x, int step, int32_t* order,
                              hipStream_t stream);
 
