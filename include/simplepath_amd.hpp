@@ -351,6 +351,55 @@ inline void render(const Integrator& integrator, unsigned /*num_threads*/, unsig
     check(sp_write_pfm(scene.output_file_name.c_str(), img.width, img.height, img.rgb.data()));
 }
 
+// Adaptive sampling (sp_adaptive_round): rounds of `step` samples on the tiles whose error is still
+// above `threshold` (or that have fewer than min_samples), never beyond max_samples, until no tile
+// is selected.  A tile that stopped at n samples holds render_image's pixels of that tile at n
+// samples, bit for bit.  tile_samples[t] is the count of tile t (row-major 8x8 tiles, sp_tile_origin).
+struct AdaptiveImage {
+    Image                 image;
+    std::vector<uint32_t> tile_samples;
+    unsigned              rounds = 0; // the last one rendered nothing
+    uint64_t              samples_total = 0;
+};
+
+inline AdaptiveImage render_adaptive(const Integrator& integrator, const Scene& scene, float threshold, unsigned min_samples,
+                                     unsigned max_samples, unsigned step)
+{
+    if (sp_scene_bvh_info(scene.handle(), nullptr, nullptr, nullptr) != SP_OK) scene.upload(0, 0); // not resident yet
+    sp_progress_params pp{};
+    pp.struct_size = sizeof(pp);
+    pp.integrator  = static_cast<int32_t>(integrator.type());
+    sp_progress* prog = nullptr;
+    check(sp_progress_create_adaptive(scene.handle(), &pp, &prog));
+    struct Free {
+        sp_progress* p;
+        ~Free() { sp_progress_free(p); }
+    } guard{ prog };
+    int64_t n_tiles = 0;
+    check(sp_tile_count(scene.image_width, scene.image_height, &n_tiles));
+    sp_adaptive_params ap{};
+    ap.struct_size = sizeof(ap);
+    ap.threshold   = threshold;
+    ap.min_samples = min_samples;
+    ap.max_samples = max_samples;
+    ap.step        = step;
+    AdaptiveImage      out;
+    std::vector<float> tiles(static_cast<size_t>(n_tiles) * 64 * 3);
+    sp_adaptive_result res{};
+    do {
+        check(sp_adaptive_round_host(prog, &ap, tiles.data(), nullptr, &res));
+        ++out.rounds;
+    } while (res.active_tiles > 0);
+    out.samples_total = res.samples_total;
+    out.tile_samples.assign(static_cast<size_t>(n_tiles), 0u);
+    check(sp_adaptive_tile_samples(prog, out.tile_samples.data(), n_tiles));
+    out.image.width  = scene.image_width;
+    out.image.height = scene.image_height;
+    out.image.rgb.assign(static_cast<size_t>(out.image.width) * out.image.height * 3, 0.0f);
+    check(sp_tiles_to_image(out.image.width, out.image.height, nullptr, 0, tiles.data(), out.image.rgb.data()));
+    return out;
+}
+
 } // namespace sp_amd
 
 #endif // SIMPLEPATH_AMD_HPP

@@ -416,6 +416,64 @@ int  sp_progress_device_bytes(const sp_progress* progress, int64_t* out);
 int  sp_progress_export(sp_progress* progress, sp_pixel_state* h_states, int64_t capacity, uint32_t* samples);
 int  sp_progress_import(sp_progress* progress, const sp_pixel_state* h_states, int64_t count, uint32_t samples);
 
+/* ---- adaptive sampling --------------------------------------------------------------------
+ * An adaptive progress object also carries, per pixel, the running mean and sum of squared
+ * deviations of its samples' luminance (the reference's RunningStats fed with relative_luminance),
+ * and per tile the number of samples done: the sample count becomes a per-tile quantity.  A round
+ * computes every tile's error, renders `step` more samples on the tiles that still need them and
+ * resolves the others, so d_out always holds the whole current image.  A tile that stopped after n
+ * samples holds the image of a one-shot render of that tile at n samples, bit for bit.
+ *
+ *   pixel error  e = sqrt((m2 / (n - 1)) / n) / (|mean| + floor),  +inf for n < 2 or a non-finite e
+ *   tile error   E = max of e over the tile's pixels inside the image
+ *   active       n < max_samples && (n < min_samples || !(E <= threshold)); gets min(step, max - n)
+ *
+ * 8 bytes per pixel slot and at most 16 per tile beyond a plain object's memory.  On an adaptive
+ * object sp_progress_render still adds more_samples to every tile (from its own count) and updates
+ * the statistics, sp_progress_samples returns the largest tile count, and sp_progress_export /
+ * _import carry the sampler and the sums as before; sp_progress_import sets every tile's count to
+ * `samples`.  A checkpoint is sp_progress_export + sp_adaptive_export, restored by
+ * sp_progress_import followed by sp_adaptive_import (the true per-tile counts and the statistics).
+ * The adaptive calls on a plain object return SP_ERR_STATE. */
+#define SP_HAS_ADAPTIVE 1
+
+int  sp_progress_create_adaptive(sp_scene* scene, const sp_progress_params* params, sp_progress** out);
+
+typedef struct sp_adaptive_params {   /* zero-initialise; struct_size = sizeof */
+    uint32_t struct_size;
+    float    threshold;      /* >= 0, finite */
+    uint32_t min_samples, max_samples, step;   /* step >= 1, min <= max, max >= 1 */
+    float    floor;          /* 0 = 0.01 */
+    uint32_t reserved[2];    /* must be 0 */
+} sp_adaptive_params;
+
+typedef struct sp_adaptive_result {
+    int64_t  active_tiles;   /* tiles rendered in this round; 0 = converged, only the image was resolved */
+    uint64_t samples_total;  /* sum over pixels of samples done */
+    uint32_t min_done, max_done;
+    float    max_error;      /* over tiles, before the round */
+    uint32_t reserved;
+} sp_adaptive_result;
+
+/* one round: error -> select -> render step samples on the active tiles -> resolve the rest.
+ * Stream-ordered: with stats == NULL and result == NULL the call only enqueues work (the active
+ * list and its length stay on the device).  stats counts this round's rendering only. */
+int  sp_adaptive_round(sp_progress* progress, const sp_adaptive_params* params, void* stream, float* d_out,
+                       sp_render_stats* stats, sp_adaptive_result* result);
+int  sp_adaptive_round_host(sp_progress* progress, const sp_adaptive_params* params, float* h_out,
+                            sp_render_stats* stats, sp_adaptive_result* result);
+/* Per tile slot: samples done, and the tile error at that state (floor 0 = 0.01).  capacity in
+ * entries, >= num_tiles.  Both wait for the object's queued work. */
+int  sp_adaptive_tile_samples(sp_progress* progress, uint32_t* h_out, int64_t capacity);
+int  sp_adaptive_tile_errors(sp_progress* progress, float floor, float* h_out, int64_t capacity);
+typedef struct sp_pixel_noise { float mean, m2; } sp_pixel_noise;
+/* The noise half of a checkpoint: num_tiles * 64 records (record slot * 64 + morton, zero outside the
+ * image) and num_tiles counts. */
+int  sp_adaptive_export(sp_progress* progress, sp_pixel_noise* h_noise, int64_t capacity,
+                        uint32_t* h_tile_samples, int64_t tiles);
+int  sp_adaptive_import(sp_progress* progress, const sp_pixel_noise* h_noise, int64_t count,
+                        const uint32_t* h_tile_samples, int64_t tiles);
+
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the
  * reference's images are those of the CPU it ran on.  By default scenes are built (host) and

@@ -24,7 +24,7 @@ from ._abi import INTEGRATORS, SimplePathError, check, lib
 __all__ = [
     "Scene", "TileScheduler", "ColumnMajorTileScheduler", "RenderStats", "render", "render_tiles",
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
-    "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE",
+    "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -266,6 +266,20 @@ PIXEL_STATE_DTYPE = np.dtype([("mt", "<u8", (312,)), ("mt_pos", "<u8"), ("draws"
                               ("reserved", "<u4")])
 
 
+# sp_pixel_noise: one pixel's luminance statistics in an adaptive checkpoint
+PIXEL_NOISE_DTYPE = np.dtype([("mean", "<f4"), ("m2", "<f4")])
+
+
+@dataclass
+class AdaptiveResult:
+    """sp_adaptive_result: what one round did."""
+    active_tiles: int    # tiles rendered in the round; 0: converged, the image was only resolved
+    samples_total: int   # sum over pixels of samples done
+    min_done: int
+    max_done: int
+    max_error: float     # over tiles, before the round
+
+
 class Progressive:
     """Resumable render of one tile list (sp_progress): render(n) adds n samples per pixel, and the
     image after calls with n1, n2, ... samples is render_tiles' image at n1 + n2 + ... samples, bit
@@ -276,10 +290,18 @@ class Progressive:
         while not good_enough(img):
             tiles, stats = prog.render(16)
             img = tiles_to_image(scene.width, scene.height, tiles)
+
+    adaptive=True (sp_progress_create_adaptive; 8 more bytes per pixel slot) also keeps every pixel's
+    luminance statistics and a sample count per tile: round() renders only the tiles whose error is
+    still above a threshold, converge() repeats it until none is, and a tile that stopped at n samples
+    holds render_tiles' image of that tile at n samples, bit for bit.
+
+        prog = Progressive(scene, "direct_lighting", adaptive=True)
+        tiles, rounds = prog.converge(threshold=0.02, min_samples=8, max_samples=256, step=16)
     """
 
     def __init__(self, scene: Scene, integrator=None, tile_ids: Optional[Sequence[int]] = None, waves_per_simd: int = 0,
-                 tile_order_factor: float = 0.0, d_tile_ids: int = 0, num_tiles: int = 0):
+                 tile_order_factor: float = 0.0, d_tile_ids: int = 0, num_tiles: int = 0, adaptive: bool = False):
         if isinstance(integrator, str):
             integrator = string_to_integrator_type(integrator)
         p = _abi.sp_progress_params()
@@ -297,7 +319,9 @@ class Progressive:
         p.tile_order_factor = float(tile_order_factor)
         self._h = C.c_void_p()
         self._scene = scene  # the scene outlives the progress object
-        check(lib().sp_progress_create(scene.handle, C.byref(p), C.byref(self._h)))
+        self.adaptive = bool(adaptive)
+        create = lib().sp_progress_create_adaptive if adaptive else lib().sp_progress_create
+        check(create(scene.handle, C.byref(p), C.byref(self._h)))
         self.num_tiles = int(p.num_tiles) if (keep is not None or d_tile_ids) else \
             TileScheduler(scene.width, scene.height).get_num_tiles()
 
@@ -353,6 +377,77 @@ class Progressive:
         """Continue from a checkpoint export_state() wrote (same tile list, same scene file)."""
         a = np.ascontiguousarray(arr, dtype=PIXEL_STATE_DTYPE)
         check(lib().sp_progress_import(self._h, C.c_void_p(a.ctypes.data), a.size, int(samples)))
+
+
+    # ---- adaptive objects (adaptive=True)
+
+    @staticmethod
+    def _adaptive_params(threshold, min_samples, max_samples, step, floor):
+        p = _abi.sp_adaptive_params()
+        p.struct_size = C.sizeof(_abi.sp_adaptive_params)
+        p.threshold, p.floor = float(threshold), float(floor)
+        p.min_samples, p.max_samples, p.step = int(min_samples), int(max_samples), int(step)
+        return p
+
+    def round(self, threshold: float, min_samples: int, max_samples: int, step: int, floor: float = 0.0,
+              out_ptr: Optional[int] = None, stream=None, stats: bool = True, result: bool = True):
+        """One round (sp_adaptive_round): tile errors, selection, `step` more samples on the tiles that
+        are below min_samples or above `threshold` (never beyond max_samples), the others resolved.
+        Returns (tile-packed image [tiles, 64, 3], RenderStats, AdaptiveResult).  out_ptr: a caller-owned
+        device buffer; the image is then None, and with stats=False and result=False the round is only
+        enqueued on `stream`.  floor: 0 = 0.01."""
+        p = self._adaptive_params(threshold, min_samples, max_samples, step, floor)
+        st = _abi.sp_render_stats() if stats else None
+        rs = _abi.sp_adaptive_result() if result else None
+        a_st, a_rs = (C.byref(st) if stats else None), (C.byref(rs) if result else None)
+        out = None
+        if out_ptr is not None:
+            check(lib().sp_adaptive_round(self._h, C.byref(p), stream, C.c_void_p(out_ptr), a_st, a_rs))
+        else:
+            out = np.zeros((max(self.num_tiles, 1), 64, 3), dtype=np.float32)
+            check(lib().sp_adaptive_round_host(self._h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_float)), a_st, a_rs))
+            out = out[:self.num_tiles]
+        res = AdaptiveResult(rs.active_tiles, rs.samples_total, rs.min_done, rs.max_done, rs.max_error) if result else None
+        return out, (_stats(st) if stats else None), res
+
+    def converge(self, threshold: float, min_samples: int, max_samples: int, step: int, floor: float = 0.0,
+                 max_rounds: Optional[int] = None):
+        """round() until no tile is active.  Returns (image, [(RenderStats, AdaptiveResult) per round]);
+        the last round rendered nothing and resolved the whole image."""
+        rounds = []
+        while True:
+            out, st, res = self.round(threshold, min_samples, max_samples, step, floor)
+            rounds.append((st, res))
+            if res.active_tiles == 0 or (max_rounds is not None and len(rounds) >= max_rounds):
+                return out, rounds
+
+    def tile_samples(self) -> np.ndarray:
+        """Samples done, per tile slot (uint32)."""
+        out = np.zeros(max(self.num_tiles, 1), dtype=np.uint32)
+        check(lib().sp_adaptive_tile_samples(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out[:self.num_tiles]
+
+    def tile_errors(self, floor: float = 0.0) -> np.ndarray:
+        """Tile error at the current state, per tile slot (float32; inf below 2 samples)."""
+        out = np.zeros(max(self.num_tiles, 1), dtype=np.float32)
+        check(lib().sp_adaptive_tile_errors(self._h, float(floor), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out[:self.num_tiles]
+
+    def export_noise(self):
+        """The noise half of a checkpoint: (tiles * 64 PIXEL_NOISE_DTYPE records, per-tile counts)."""
+        noise = np.zeros(self.num_tiles * 64, dtype=PIXEL_NOISE_DTYPE)
+        counts = np.zeros(max(self.num_tiles, 1), dtype=np.uint32)
+        check(lib().sp_adaptive_export(self._h, C.c_void_p(noise.ctypes.data), noise.size,
+                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size))
+        return noise, counts[:self.num_tiles]
+
+    def import_noise(self, noise: np.ndarray, counts: np.ndarray) -> None:
+        """After import_state(): the true per-tile counts and the statistics export_noise() wrote."""
+        a = np.ascontiguousarray(noise, dtype=PIXEL_NOISE_DTYPE)
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        keep = c if c.size else np.zeros(1, dtype=np.uint32)
+        check(lib().sp_adaptive_import(self._h, C.c_void_p(a.ctypes.data), a.size,
+                                       keep.ctypes.data_as(C.POINTER(C.c_uint32)), c.size))
 
 
 def tiles_to_image(width: int, height: int, tiles: np.ndarray, tile_ids: Optional[np.ndarray] = None) -> np.ndarray:

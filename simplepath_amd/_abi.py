@@ -134,8 +134,31 @@ class sp_pixel_state(C.Structure):
                 ("sum", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class sp_adaptive_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_float), ("min_samples", C.c_uint32),
+                ("max_samples", C.c_uint32), ("step", C.c_uint32), ("floor", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class sp_adaptive_result(C.Structure):
+    _fields_ = [("active_tiles", C.c_int64), ("samples_total", C.c_uint64), ("min_done", C.c_uint32),
+                ("max_done", C.c_uint32), ("max_error", C.c_float), ("reserved", C.c_uint32)]
+
+
+class sp_pixel_noise(C.Structure):
+    _fields_ = [("mean", C.c_float), ("m2", C.c_float)]
+
+
 # Every symbol declared in include/simplepath_hip.h, with its ctypes signature.
 SIGNATURES = {
+    "sp_progress_create_adaptive": (C.c_int, [C.c_void_p, C.POINTER(sp_progress_params), C.POINTER(C.c_void_p)]),
+    "sp_adaptive_round": (C.c_int, [C.c_void_p, C.POINTER(sp_adaptive_params), C.c_void_p, C.c_void_p,
+                                    C.POINTER(sp_render_stats), C.POINTER(sp_adaptive_result)]),
+    "sp_adaptive_round_host": (C.c_int, [C.c_void_p, C.POINTER(sp_adaptive_params), C.POINTER(C.c_float),
+                                         C.POINTER(sp_render_stats), C.POINTER(sp_adaptive_result)]),
+    "sp_adaptive_tile_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int64]),
+    "sp_adaptive_tile_errors": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_int64]),
+    "sp_adaptive_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint32), C.c_int64]),
+    "sp_adaptive_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint32), C.c_int64]),
     "sp_progress_create": (C.c_int, [C.c_void_p, C.POINTER(sp_progress_params), C.POINTER(C.c_void_p)]),
     "sp_progress_free": (None, [C.c_void_p]),
     "sp_progress_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(sp_render_stats)]),

@@ -32,6 +32,14 @@ hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeAr
                          size_t lds_bytes, hipStream_t stream);
 int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
 size_t     resume_static_lds(int integ, int variant);
+hipError_t launch_adapt(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, const AdaptArgs& ad, int integ,
+                        int variant, int blocks, size_t lds_bytes, hipStream_t stream);
+int        adapt_blocks_per_cu(int integ, int variant, size_t lds_bytes);
+size_t     adapt_static_lds(int integ, int variant);
+hipError_t launch_adapt_select(const AdaptArgs& ad, const SelectArgs& sa, float* err, uint32_t* flag, hipStream_t stream);
+hipError_t launch_adapt_compact(const AdaptArgs& ad, const int32_t* order, int64_t n_tiles, hipStream_t stream);
+hipError_t launch_adapt_resolve(const ResumeArgs& res, const AdaptArgs& ad, bool skip_active, int64_t n_tiles, float* out,
+                                hipStream_t stream);
 } // namespace spd
 
 namespace {
@@ -360,15 +368,22 @@ struct sp_progress {
     int32_t*             d_order     = nullptr;
     bool                 order_tried = false, ordered = false;
     int64_t              bytes = 0;
+    // adaptive objects (sp_progress_create_adaptive): per-tile counts and per-pixel noise statistics;
+    // st.n0 is then only an upper bound of the tile counts (the device holds the counts)
+    bool                 adaptive = false;
+    spd::AdaptArgs       ad{};
+    std::vector<uint8_t> h_inside;       // per slot, its pixels inside the image
 
     void release()
     {
         if (device >= 0) (void)hipSetDevice(device);
         for (void* p : { (void*)d_ids, (void*)st.gen, (void*)st.pos, (void*)st.draws, (void*)st.sum, (void*)d_tile_time,
-                         (void*)d_order })
+                         (void*)d_order, (void*)ad.mean, (void*)ad.m2, (void*)ad.done, (void*)ad.err, (void*)ad.flag,
+                         (void*)ad.active, (void*)ad.n_active })
             if (p) (void)hipFree(p); // (waits for kernels that still use it)
         d_ids = nullptr; d_tile_time = nullptr; d_order = nullptr;
         st    = spd::ResumeArgs{};
+        ad    = spd::AdaptArgs{};
     }
     ~sp_progress() { release(); }
 };
@@ -1770,7 +1785,7 @@ static int progress_live(const sp_progress* g)
     return SP_OK;
 }
 
-static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_progress** out)
+static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_progress** out, bool adaptive = false)
 {
     if (p->struct_size != sizeof(sp_progress_params)) return fail(SP_ERR_ARG, "sp_progress_params.struct_size is not this library's");
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_progress_params.reserved must be 0");
@@ -1828,6 +1843,29 @@ static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_pro
     SP_HIP(hipMemset(g->st.draws, 0, b_draws));
     SP_HIP(hipMemset(g->st.sum, 0, b_sum));
     g->bytes += (int64_t)(b_gen + b_pos + b_draws + b_sum);
+    if (adaptive) {
+        g->adaptive = true;
+        const size_t b_px = nt * 64 * 4, b_tile = nt * 4;
+        SP_HIP(hipMalloc(&g->ad.mean, b_px));
+        SP_HIP(hipMalloc(&g->ad.m2, b_px));
+        SP_HIP(hipMalloc(&g->ad.done, b_tile));
+        SP_HIP(hipMalloc(&g->ad.err, b_tile));
+        SP_HIP(hipMalloc(&g->ad.flag, b_tile));
+        SP_HIP(hipMalloc(&g->ad.active, b_tile));
+        SP_HIP(hipMalloc(&g->ad.n_active, sizeof(int32_t)));
+        SP_HIP(hipMemset(g->ad.mean, 0, b_px)); // as the sums: zero outside the image
+        SP_HIP(hipMemset(g->ad.m2, 0, b_px));
+        SP_HIP(hipMemset(g->ad.done, 0, b_tile));
+        SP_HIP(hipMemset(g->ad.err, 0, b_tile));
+        SP_HIP(hipMemset(g->ad.flag, 0, b_tile));
+        SP_HIP(hipMemset(g->ad.active, 0, b_tile));
+        SP_HIP(hipMemset(g->ad.n_active, 0, sizeof(int32_t)));
+        g->bytes += (int64_t)(2 * b_px + 4 * b_tile + sizeof(int32_t));
+        g->h_inside.assign(nt, 0);
+        int32_t x, y;
+        for (int64_t sl = 0; sl < n_tiles; ++sl)
+            for (uint32_t m = 0; m < 64; ++m) g->h_inside[(size_t)sl] += progress_pixel(g.get(), sl, m, x, y) ? 1 : 0;
+    }
     *out = g.release();
     return SP_OK;
 }
@@ -1844,19 +1882,63 @@ int sp_progress_create(sp_scene* s, const sp_progress_params* p, sp_progress** o
     }
 }
 
+int sp_progress_create_adaptive(sp_scene* s, const sp_progress_params* p, sp_progress** out)
+{
+    if (!s || !p || !out) return fail(SP_ERR_ARG, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(s->mu);
+    try {
+        return progress_create_impl(s, p, out, true);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_progress_create_adaptive failed: ") + e.what());
+    }
+}
+
 void sp_progress_free(sp_progress* g) { delete g; }
 
-static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t stream, float* d_out, sp_render_stats* stats)
+// After the object's queued work: the tile counts, and optionally the errors of the last selection.
+static int adaptive_fetch(sp_progress* g, std::vector<uint32_t>& done, std::vector<float>* err)
+{
+    sp_scene* s = g->scene;
+    SP_HIP(hipSetDevice(s->device));
+    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    done.assign((size_t)g->n_tiles, 0u);
+    if (g->n_tiles == 0) return SP_OK;
+    SP_HIP(hipMemcpy(done.data(), g->ad.done, done.size() * 4, hipMemcpyDeviceToHost));
+    if (err) {
+        err->assign((size_t)g->n_tiles, 0.0f);
+        SP_HIP(hipMemcpy(err->data(), g->ad.err, err->size() * 4, hipMemcpyDeviceToHost));
+    }
+    return SP_OK;
+}
+
+// A round's rule on an adaptive object (sp_adaptive_round); a uniform pass (sp_progress_render) is
+// the rule that selects every tile: min = max = UINT32_MAX, step = more_samples.
+struct AdaptRound {
+    float               threshold, floor;
+    uint32_t            min_samples, max_samples, step;
+    bool                uniform;
+    sp_adaptive_result* result;
+};
+
+// rd: nullptr on a plain object
+static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t stream, float* d_out, sp_render_stats* stats,
+                                const AdaptRound* rd = nullptr)
 {
     sp_scene* s = g->scene;
     if (int rc = progress_live(g)) return rc;
     if (more == 0) return fail(SP_ERR_ARG, "more_samples must be > 0");
-    if ((uint64_t)g->st.n0 + more > UINT32_MAX) return fail(SP_ERR_ARG, "more than UINT32_MAX samples in all");
+    if ((!rd || rd->uniform) && (uint64_t)g->st.n0 + more > UINT32_MAX)
+        return fail(SP_ERR_ARG, "more than UINT32_MAX samples in all");
     if (stats) *stats = sp_render_stats{};
+    if (rd && rd->result) *rd->result = sp_adaptive_result{};
     SP_HIP(hipSetDevice(s->device));
     const int64_t n_tiles = g->n_tiles;
+    // an adaptive object's count bound after this call (st.n0: no tile has more)
+    const uint32_t n0_after = !rd || rd->uniform ? g->st.n0 + more
+                                                 : std::max(g->st.n0, (uint32_t)std::min<uint64_t>((uint64_t)g->st.n0 + more, rd->max_samples));
     if (n_tiles == 0) {
-        g->st.n0 += more;
+        g->st.n0 = n0_after;
         return SP_OK;
     }
     // the scene's scratch (mt_state, counters) is shared with sp_render_tiles: same ordering
@@ -1871,14 +1953,15 @@ static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t strea
     const int    rs_words  = spd::rsqrt_words(s->dev);
     const size_t lds_bytes = (size_t)rs_words * 4 + (size_t)4 * s->dev.stack_words * 64 * 4;
     size_t       lds_static = 0;
-    for (int v = 2; v <= 4; ++v) lds_static = std::max(lds_static, spd::resume_static_lds(integ, v));
+    for (int v = 2; v <= 4; ++v)
+        lds_static = std::max(lds_static, rd ? spd::adapt_static_lds(integ, v) : spd::resume_static_lds(integ, v));
     const size_t lds_all = lds_bytes + lds_static;
     if (lds_all > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
     const int lds_waves = (int)std::min<size_t>(8, (160 * 1024) / lds_all);
     int       variant   = integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? 3 : 4;
     variant             = std::max(2, std::min(variant, lds_waves));
     if (g->waves_req) variant = g->waves_req;
-    const int     per_cu = spd::resume_blocks_per_cu(integ, variant, lds_bytes);
+    const int     per_cu = rd ? spd::adapt_blocks_per_cu(integ, variant, lds_bytes) : spd::resume_blocks_per_cu(integ, variant, lds_bytes);
     const int     blocks = (int)std::max<int64_t>(1, std::min((int64_t)s->n_cu * per_cu, (n_tiles + 3) / 4));
     const size_t  waves  = (size_t)blocks * 4;
     if (waves > s->mt_waves) {
@@ -1897,7 +1980,7 @@ static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t strea
     a.tile_ids     = g->d_ids;
     a.num_tiles    = n_tiles;
     a.tiles_x      = (s->dev.width + 7) / 8;
-    a.spp          = more;
+    a.spp          = more; // (an adaptive call: at most; a tile's own count decides, AdaptArgs)
     a.integrator   = integ;
     a.tile_counter = s->tile_counter;
     a.mt_state     = s->mt_state;
@@ -1947,11 +2030,54 @@ static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t strea
         }
     }
     a.order = g->ordered ? g->d_order : nullptr;
-    SP_HIP(spd::launch_resume(sc_run, a, g->st, integ, variant, blocks, lds_bytes, stream));
+    if (rd) {
+        // errors and the selection, the selected slots in the kept tile order, the render kernel on
+        // that list (its length stays on the device), then the image of the tiles it left alone
+        spd::SelectArgs sa{};
+        sa.tile_ids    = g->d_ids;
+        sa.num_tiles   = n_tiles;
+        sa.tiles_x     = a.tiles_x;
+        sa.width       = s->dev.width;
+        sa.height      = s->dev.height;
+        sa.threshold   = rd->threshold;
+        sa.floor       = rd->floor;
+        sa.min_samples = rd->min_samples;
+        sa.max_samples = rd->max_samples;
+        spd::AdaptArgs ad = g->ad;
+        ad.step           = rd->step;
+        ad.cap            = rd->max_samples;
+        SP_HIP(spd::launch_adapt_select(ad, sa, ad.err, ad.flag, stream));
+        SP_HIP(spd::launch_adapt_compact(ad, a.order, n_tiles, stream));
+        SP_HIP(spd::launch_adapt(sc_run, a, g->st, ad, integ, variant, blocks, lds_bytes, stream));
+        launches += 2;
+        if (d_out && !rd->uniform) {
+            SP_HIP(spd::launch_adapt_resolve(g->st, ad, true, n_tiles, d_out, stream));
+            launches += 1;
+        }
+    } else {
+        SP_HIP(spd::launch_resume(sc_run, a, g->st, integ, variant, blocks, lds_bytes, stream));
+    }
     SP_HIP(hipEventRecord(s->ev1, stream));
     SP_HIP(hipEventRecord(s->ev_done, stream));
     s->done_rec = true;
-    g->st.n0 += more;
+    g->st.n0 = n0_after;
+    if (rd && rd->result) {
+        sp_adaptive_result&   r = *rd->result;
+        std::vector<uint32_t> done;
+        std::vector<float>    err;
+        if (int rc = adaptive_fetch(g, done, &err)) return rc;
+        int32_t n_act = 0;
+        SP_HIP(hipMemcpy(&n_act, g->ad.n_active, sizeof(n_act), hipMemcpyDeviceToHost));
+        r.active_tiles = n_act;
+        r.min_done     = UINT32_MAX;
+        for (int64_t i = 0; i < n_tiles; ++i) {
+            r.samples_total += (uint64_t)done[(size_t)i] * g->h_inside[(size_t)i];
+            r.min_done  = std::min(r.min_done, done[(size_t)i]);
+            r.max_done  = std::max(r.max_done, done[(size_t)i]);
+            r.max_error = std::max(r.max_error, err[(size_t)i]);
+        }
+        g->st.n0 = r.max_done;
+    }
     if (stats) {
         SP_HIP(hipEventSynchronize(s->ev1));
         unsigned long long c[8];
@@ -1976,6 +2102,10 @@ int sp_progress_render(sp_progress* g, uint32_t more_samples, void* stream, floa
     if (!g) return fail(SP_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lock(g->scene->mu);
     try {
+        if (g->adaptive) { // every tile gets more_samples from its own count
+            const AdaptRound all{ 0.0f, 0.01f, UINT32_MAX, UINT32_MAX, more_samples, true, nullptr };
+            return progress_render_impl(g, more_samples, static_cast<hipStream_t>(stream), d_out, stats, &all);
+        }
         return progress_render_impl(g, more_samples, static_cast<hipStream_t>(stream), d_out, stats);
     } catch (const std::exception& e) {
         return fail(SP_ERR_HIP, std::string("sp_progress_render failed: ") + e.what());
@@ -2003,6 +2133,15 @@ int sp_progress_samples(const sp_progress* g, uint32_t* out)
 {
     if (!g || !out) return fail(SP_ERR_ARG, "null argument");
     *out = g->st.n0;
+    if (g->adaptive) { // the largest tile count (waits for the object's queued work)
+        std::lock_guard<std::mutex> lock(g->scene->mu);
+        std::vector<uint32_t>       done;
+        if (int rc = progress_live(g)) return rc;
+        if (int rc = adaptive_fetch(const_cast<sp_progress*>(g), done, nullptr)) return rc;
+        *out = 0;
+        for (uint32_t c : done) *out = std::max(*out, c);
+        if (g->n_tiles == 0) *out = g->st.n0;
+    }
     return SP_OK;
 }
 
@@ -2027,6 +2166,12 @@ static int progress_export_impl(sp_progress* g, sp_pixel_state* h, int64_t capac
     if (n_px == 0) return SP_OK;
     SP_HIP(hipSetDevice(s->device));
     if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    std::vector<uint32_t> tile_done; // an adaptive object: each tile has its own count
+    if (g->adaptive) {
+        if (int rc = adaptive_fetch(g, tile_done, nullptr)) return rc;
+        *samples = *std::max_element(tile_done.begin(), tile_done.end());
+    }
+    const uint32_t any_done = *samples;
     std::vector<uint32_t>           pos((size_t)n_px);
     std::vector<unsigned long long> draws((size_t)n_px);
     std::vector<float>              sum((size_t)g->n_tiles * 192);
@@ -2036,7 +2181,7 @@ static int progress_export_impl(sp_progress* g, sp_pixel_state* h, int64_t capac
     std::vector<uint64_t> gen((size_t)std::min(PROGRESS_BATCH, g->n_tiles) * spd::MT_GEN_WORDS);
     for (int64_t t0 = 0; t0 < g->n_tiles; t0 += PROGRESS_BATCH) {
         const int64_t nb = std::min(PROGRESS_BATCH, g->n_tiles - t0);
-        if (g->st.n0 > 0)
+        if (any_done > 0)
             SP_HIP(hipMemcpy(gen.data(), g->st.gen + (size_t)t0 * spd::MT_GEN_WORDS, (size_t)nb * spd::MT_GEN_WORDS * 8,
                              hipMemcpyDeviceToHost));
         for (int64_t sl = t0; sl < t0 + nb; ++sl)
@@ -2045,7 +2190,7 @@ static int progress_export_impl(sp_progress* g, sp_pixel_state* h, int64_t capac
                 std::memset(&r, 0, sizeof(r));
                 int32_t x, y;
                 if (!progress_pixel(g, sl, m, x, y)) continue;
-                if (g->st.n0 == 0) { // nothing rendered yet: the seeded engine (main.cpp:73), _M_p = n
+                if ((g->adaptive ? tile_done[(size_t)sl] : g->st.n0) == 0) { // nothing rendered yet: the seeded engine (main.cpp:73), _M_p = n
                     spm::Mt64 e;
                     spm::mt_init(e, (((uint32_t)x << 16u) | (uint32_t)y) ^ 0xb0ae9d99u);
                     std::memcpy(r.mt, e.x, sizeof(r.mt));
@@ -2091,6 +2236,12 @@ static int progress_import_impl(sp_progress* g, const sp_pixel_state* h, int64_t
     }
     SP_HIP(hipSetDevice(s->device));
     if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (g->adaptive) { // every tile at `samples`, no statistics: sp_adaptive_import brings both
+        const std::vector<uint32_t> all((size_t)g->n_tiles, samples);
+        SP_HIP(hipMemcpy(g->ad.done, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        SP_HIP(hipMemset(g->ad.mean, 0, (size_t)n_px * 4));
+        SP_HIP(hipMemset(g->ad.m2, 0, (size_t)n_px * 4));
+    }
     std::vector<uint32_t>           pos((size_t)n_px, 0u);
     std::vector<unsigned long long> draws((size_t)n_px, 0ull);
     std::vector<float>              sum((size_t)g->n_tiles * 192, 0.0f);
@@ -2126,6 +2277,172 @@ int sp_progress_import(sp_progress* g, const sp_pixel_state* h_states, int64_t c
         return progress_import_impl(g, h_states, count, samples);
     } catch (const std::exception& e) {
         return fail(SP_ERR_HIP, std::string("sp_progress_import failed: ") + e.what());
+    }
+}
+
+// ---- adaptive sampling (adaptive progress objects) ---------------------------------------------
+
+static int adaptive_object(const sp_progress* g)
+{
+    if (!g->adaptive) return fail(SP_ERR_STATE, "not an adaptive progress object (sp_progress_create_adaptive)");
+    return progress_live(g);
+}
+
+static int adaptive_round_params(const sp_adaptive_params* p, sp_adaptive_result* result, AdaptRound& rd)
+{
+    if (p->struct_size != sizeof(sp_adaptive_params)) return fail(SP_ERR_ARG, "sp_adaptive_params.struct_size is not this library's");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_adaptive_params.reserved must be 0");
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold)) return fail(SP_ERR_ARG, "threshold must be finite and >= 0");
+    if (!(p->floor >= 0.0f) || !std::isfinite(p->floor)) return fail(SP_ERR_ARG, "floor must be finite and >= 0");
+    if (p->step < 1) return fail(SP_ERR_ARG, "step must be >= 1");
+    if (p->max_samples < 1 || p->min_samples > p->max_samples) return fail(SP_ERR_ARG, "need 1 <= max_samples and min_samples <= max_samples");
+    rd = AdaptRound{ p->threshold, p->floor == 0.0f ? 0.01f : p->floor, p->min_samples, p->max_samples, p->step, false, result };
+    return SP_OK;
+}
+
+int sp_adaptive_round(sp_progress* g, const sp_adaptive_params* p, void* stream, float* d_out, sp_render_stats* stats,
+                      sp_adaptive_result* result)
+{
+    if (!g || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        if (int rc = adaptive_object(g)) return rc;
+        AdaptRound rd{};
+        if (int rc = adaptive_round_params(p, result, rd)) return rc;
+        return progress_render_impl(g, rd.step, static_cast<hipStream_t>(stream), d_out, stats, &rd);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_adaptive_round failed: ") + e.what());
+    }
+}
+
+int sp_adaptive_round_host(sp_progress* g, const sp_adaptive_params* p, float* h_out, sp_render_stats* stats,
+                           sp_adaptive_result* result)
+{
+    if (!g || !p || !h_out) return fail(SP_ERR_ARG, "null argument");
+    if (g->scene->device < 0) return fail(SP_ERR_STATE, "the scene is no longer uploaded");
+    SP_HIP(hipSetDevice(g->scene->device));
+    const size_t bytes = (size_t)g->n_tiles * 64 * 3 * sizeof(float);
+    float*       d     = nullptr;
+    SP_HIP(hipMalloc(&d, std::max<size_t>(bytes, 4)));
+    int rc = sp_adaptive_round(g, p, nullptr, d, stats, result);
+    if (rc == SP_OK && bytes) {
+        hipError_t e = hipMemcpy(h_out, d, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int sp_adaptive_tile_samples(sp_progress* g, uint32_t* h_out, int64_t capacity)
+{
+    if (!g || !h_out) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        if (int rc = adaptive_object(g)) return rc;
+        if (capacity < g->n_tiles) return fail(SP_ERR_ARG, "capacity below num_tiles");
+        std::vector<uint32_t> done;
+        if (int rc = adaptive_fetch(g, done, nullptr)) return rc;
+        std::copy(done.begin(), done.end(), h_out);
+        return SP_OK;
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_adaptive_tile_samples failed: ") + e.what());
+    }
+}
+
+static int adaptive_tile_errors_impl(sp_progress* g, float floor, float* h_out, int64_t capacity)
+{
+    sp_scene* s = g->scene;
+    if (int rc = adaptive_object(g)) return rc;
+    if (!(floor >= 0.0f) || !std::isfinite(floor)) return fail(SP_ERR_ARG, "floor must be finite and >= 0");
+    if (capacity < g->n_tiles) return fail(SP_ERR_ARG, "capacity below num_tiles");
+    if (g->n_tiles == 0) return SP_OK;
+    SP_HIP(hipSetDevice(s->device));
+    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    spd::SelectArgs sa{};
+    sa.tile_ids  = g->d_ids;
+    sa.num_tiles = g->n_tiles;
+    sa.tiles_x   = (g->width + 7) / 8;
+    sa.width     = g->width;
+    sa.height    = g->height;
+    sa.floor     = floor == 0.0f ? 0.01f : floor;
+    SP_HIP(spd::launch_adapt_select(g->ad, sa, g->ad.err, nullptr, nullptr)); // errors only: no selection
+    SP_HIP(hipMemcpy(h_out, g->ad.err, (size_t)g->n_tiles * 4, hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_adaptive_tile_errors(sp_progress* g, float floor, float* h_out, int64_t capacity)
+{
+    if (!g || !h_out) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return adaptive_tile_errors_impl(g, floor, h_out, capacity);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_adaptive_tile_errors failed: ") + e.what());
+    }
+}
+
+static int adaptive_export_impl(sp_progress* g, sp_pixel_noise* h, int64_t capacity, uint32_t* h_tiles, int64_t tiles)
+{
+    if (int rc = adaptive_object(g)) return rc;
+    const int64_t n_px = g->n_tiles * 64;
+    if (capacity < n_px) return fail(SP_ERR_ARG, "capacity below num_tiles * 64 records");
+    if (tiles < g->n_tiles) return fail(SP_ERR_ARG, "tiles below num_tiles");
+    std::vector<uint32_t> done;
+    if (int rc = adaptive_fetch(g, done, nullptr)) return rc;
+    std::copy(done.begin(), done.end(), h_tiles);
+    if (n_px == 0) return SP_OK;
+    std::vector<float> mean((size_t)n_px), m2((size_t)n_px);
+    SP_HIP(hipMemcpy(mean.data(), g->ad.mean, mean.size() * 4, hipMemcpyDeviceToHost));
+    SP_HIP(hipMemcpy(m2.data(), g->ad.m2, m2.size() * 4, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n_px; ++i) h[i] = sp_pixel_noise{ mean[(size_t)i], m2[(size_t)i] };
+    return SP_OK;
+}
+
+int sp_adaptive_export(sp_progress* g, sp_pixel_noise* h_noise, int64_t capacity, uint32_t* h_tile_samples, int64_t tiles)
+{
+    if (!g || !h_noise || !h_tile_samples) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return adaptive_export_impl(g, h_noise, capacity, h_tile_samples, tiles);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_adaptive_export failed: ") + e.what());
+    }
+}
+
+static int adaptive_import_impl(sp_progress* g, const sp_pixel_noise* h, int64_t count, const uint32_t* h_tiles, int64_t tiles)
+{
+    sp_scene* s = g->scene;
+    if (int rc = adaptive_object(g)) return rc;
+    const int64_t n_px = g->n_tiles * 64;
+    if (count != n_px) return fail(SP_ERR_ARG, "count is not num_tiles * 64 records");
+    if (tiles != g->n_tiles) return fail(SP_ERR_ARG, "tiles is not num_tiles");
+    if (n_px == 0) return SP_OK;
+    SP_HIP(hipSetDevice(s->device));
+    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    std::vector<float> mean((size_t)n_px, 0.0f), m2((size_t)n_px, 0.0f);
+    int32_t            x, y;
+    for (int64_t i = 0; i < n_px; ++i) {
+        if (!progress_pixel(g, i / 64, (uint32_t)(i % 64), x, y)) continue; // outside the image: stays zero
+        mean[(size_t)i] = h[i].mean;
+        m2[(size_t)i]   = h[i].m2;
+    }
+    uint32_t top = 0;
+    for (int64_t i = 0; i < tiles; ++i) top = std::max(top, h_tiles[i]);
+    SP_HIP(hipMemcpy(g->ad.mean, mean.data(), mean.size() * 4, hipMemcpyHostToDevice));
+    SP_HIP(hipMemcpy(g->ad.m2, m2.data(), m2.size() * 4, hipMemcpyHostToDevice));
+    SP_HIP(hipMemcpy(g->ad.done, h_tiles, (size_t)tiles * 4, hipMemcpyHostToDevice));
+    g->st.n0 = top;
+    return SP_OK;
+}
+
+int sp_adaptive_import(sp_progress* g, const sp_pixel_noise* h_noise, int64_t count, const uint32_t* h_tile_samples, int64_t tiles)
+{
+    if (!g || !h_noise || !h_tile_samples) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(g->scene->mu);
+    try {
+        return adaptive_import_impl(g, h_noise, count, h_tile_samples, tiles);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_adaptive_import failed: ") + e.what());
     }
 }
 

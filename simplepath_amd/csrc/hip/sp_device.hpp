@@ -242,4 +242,31 @@ struct ResumeArgs {
     uint32_t            n0;    // samples done before this call (the R2 index of its first sample)
 };
 
+// Adaptive progress objects (sp_adapt_kernel, sp_mega.hpp; sp_adaptive.hip): the sample count is a
+// per-tile quantity and every pixel carries the reference's RunningStats of its samples' luminance
+// (base/RunningStats.h, fed at Integrators/Integrator.cpp:444).  A fourth kernel argument of the
+// adaptive kernels only, so ResumeArgs and sp_resume_kernel stay as they are; ResumeArgs::n0 is not
+// read by them.
+struct AdaptArgs {
+    float*         mean;     // [slot][64] running mean of sample luminance
+    float*         m2;       // [slot][64] running sum of squared deviations
+    uint32_t*      done;     // [slot] samples done = the tile's next R2 index
+    float*         err;      // [slot] tile error of the last selection
+    uint32_t*      flag;     // [slot] 1: active in the last selection
+    int32_t*       active;   // [n_active] the flagged slots in the object's tile order
+    int32_t*       n_active; // device count: the render kernel's item limit
+    uint32_t       step;     // an active tile gets min(step, cap - done) samples
+    uint32_t       cap;      // max_samples
+};
+
+// The selection of a round (sp_adaptive.hip adapt_error_kernel): which lanes of a slot are pixels,
+// and the rule's parameters.  flag == nullptr: tile errors only.
+struct SelectArgs {
+    const int32_t* tile_ids; // nullptr => identity
+    int64_t        num_tiles;
+    int32_t        tiles_x, width, height;
+    float          threshold, floor;
+    uint32_t       min_samples, max_samples;
+};
+
 } // namespace spd

@@ -346,6 +346,22 @@ __device__ __forceinline__ void resume_save(Rng& r, const ResumeArgs& ra, int64_
     s[128]   = acc.b;
 }
 
+// Adaptive progress objects (AdaptArgs, sp_device.hpp): sample number n (1-based) of a pixel into its
+// running statistics -- relative_luminance (RGB.h:224) into RunningStats::push (base/RunningStats.h),
+// every operation rounded on its own.
+__device__ __forceinline__ void noise_push(float& mean, float& m2, rgb L, uint32_t n)
+{
+    const float y = ((0.2126f * L.r) + (0.7152f * L.g)) + (0.0722f * L.b);
+    if (n == 1) {
+        mean = y;
+        m2   = 0.0f;
+    } else {
+        const float d = y - mean;
+        mean          = mean + d / (float)n;
+        m2            = m2 + d * (y - mean);
+    }
+}
+
 // Persistent kernel: 4 waves per block share the LDS RSQRTSS table; each wave independently
 // pulls 8x8 tiles from the queue (TileScheduler::get_next_tile) and owns one MT state slot.
 // One instantiation per integrator so each carries only its own live state; MINW is the
@@ -359,10 +375,16 @@ __device__ __forceinline__ void resume_save(Rng& r, const ResumeArgs& ra, int64_
 // sp_fused_kernel).  One kernel per form, so each carries only its own code.
 // RESUME: a progressive call (sp_resume_kernel): samples [res->n0, res->n0 + spp) of every pixel, the
 // state before and after them in the progress object's store (resume_load / resume_save above).
-template <int INTEG, bool PROBE, int TAIL = 0, bool RESUME = false>
-__device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderArgs& args, const ResumeArgs* res = nullptr)
+// ADAPT: a progressive call on an adaptive object (sp_adapt_kernel): the queue is the active list
+// (its length read from the device count, so a round needs no host wait), a tile's first sample is
+// its own count done[slot], it gets min(step, cap - done) samples, and every sample is pushed into
+// the pixel's running statistics, which live in two registers across the sample loop.
+template <int INTEG, bool PROBE, int TAIL = 0, bool RESUME = false, bool ADAPT = false>
+__device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderArgs& args, const ResumeArgs* res = nullptr,
+                                                  const AdaptArgs* ad = nullptr)
 {
     static_assert(!RESUME || (!PROBE && TAIL == 0), "progressive calls run the plain megakernel form");
+    static_assert(!ADAPT || RESUME, "adaptive calls are progressive calls");
     extern __shared__ uint32_t lds[];
     const int tid  = threadIdx.x;
     const int lane = tid & 63;
@@ -391,11 +413,15 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
     if constexpr (PROBE) rng_seed(rng, (uint32_t)(gwave * 64 + lane) ^ 0xb0ae9d99u);
     const uint32_t dx = morton_decode_1((uint32_t)lane);
     const uint32_t dy = morton_decode_1((uint32_t)lane >> 1);
+    int64_t        n_active = 0;
+    if constexpr (ADAPT) n_active = *ad->n_active;
     while (true) {
         int grabbed = 0;
         if (lane == 0) grabbed = atomicAdd(args.tile_counter, 1);
         const int64_t item = __shfl(grabbed, 0, 64);
-        if constexpr (TAIL == 2) {
+        if constexpr (ADAPT) {
+            if (item >= n_active) break;
+        } else if constexpr (TAIL == 2) {
             { // every tile cut: [camera items] then the preps interleaved with the chunks
                 const int64_t NC = args.tail_cam;
                 if (item < NC) {
@@ -435,7 +461,9 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
         } else if (item * (PROBE ? (int64_t)args.probe_step : 1) >= args.num_tiles) {
             break;
         }
-        const int64_t  slot    = PROBE ? item * args.probe_step : (args.order ? args.order[item] : item);
+        int64_t slot;
+        if constexpr (ADAPT) slot = __builtin_amdgcn_readfirstlane(ad->active[item]);
+        else slot = PROBE ? item * args.probe_step : (args.order ? args.order[item] : item);
         const uint64_t t_start = (PROBE || args.tile_diag) ? __builtin_amdgcn_s_memrealtime() : 0;
         const int32_t  tile   = args.tile_ids ? args.tile_ids[slot] : (int32_t)slot;
         const uint32_t px     = (uint32_t)((tile % args.tiles_x) * 8) + dx;
@@ -444,9 +472,23 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
         const bool     inside = px < (uint32_t)sc.width && py < (uint32_t)sc.height;
         rgb            acc    = mkc(0, 0, 0);
         uint64_t       prof[4] = { 0, 0, 0, 0 };
+        uint32_t       a_n0 = 0, a_more = 0; // ADAPT: the tile's count and its samples in this call
+        if constexpr (ADAPT) {
+            a_n0   = __builtin_amdgcn_readfirstlane(ad->done[slot]);
+            a_more = a_n0 < ad->cap ? min(ad->step, ad->cap - a_n0) : 0u;
+        }
         if (inside) {
             const uint32_t pix_seed = (px << 16u) | py;
-            if constexpr (RESUME) { // the first call seeds as a one-shot render does
+            float nz_mean = 0.0f, nz_m2 = 0.0f;
+            if constexpr (ADAPT) {
+                if (a_n0 == 0) {
+                    rng_seed_twisted(rng, pix_seed ^ 0xb0ae9d99u);
+                } else {
+                    resume_load(rng, *res, slot, lane, acc);
+                    nz_mean = ad->mean[(size_t)slot * 64 + lane];
+                    nz_m2   = ad->m2[(size_t)slot * 64 + lane];
+                }
+            } else if constexpr (RESUME) { // the first call seeds as a one-shot render does
                 if (res->n0 == 0) rng_seed_twisted(rng, pix_seed ^ 0xb0ae9d99u);
                 else resume_load(rng, *res, slot, lane, acc);
             } else if constexpr (!PROBE) { // get_integrator_sampler (main.cpp:73)
@@ -460,7 +502,10 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
                 c.dstride = args.deep_stride;
             }
             uint32_t i_first = 0, i_end = args.spp;
-            if constexpr (RESUME) { // the R2 index runs on (Mandelbrot draws nothing but uses it)
+            if constexpr (ADAPT) {
+                i_first = a_n0;
+                i_end   = a_n0 + a_more;
+            } else if constexpr (RESUME) { // the R2 index runs on (Mandelbrot draws nothing but uses it)
                 i_first = res->n0;
                 i_end   = res->n0 + args.spp;
             }
@@ -475,21 +520,33 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
                 Ray ray;
                 ray.o = sc.camera.p;
                 ray.d = normalize(add(add(scale(fx, sc.camera.vx), scale(fy, sc.camera.vy)), sc.camera.vz), q);
-                if constexpr (INTEG == SP_INTEGRATOR_MANDELBROT)
+                if constexpr (ADAPT) {
+                    rgb L;
+                    if constexpr (INTEG == SP_INTEGRATOR_MANDELBROT) L = integrate_mandelbrot(fx, fy, sc.width, sc.height);
+                    else SP_WPROF(0, L = integrate<INTEG>(c, ray));
+                    acc = cadd(acc, L);
+                    noise_push(nz_mean, nz_m2, L, i + 1u);
+                } else if constexpr (INTEG == SP_INTEGRATOR_MANDELBROT)
                     acc = cadd(acc, integrate_mandelbrot(fx, fy, sc.width, sc.height));
                 else
                     SP_WPROF(0, acc = cadd(acc, integrate<INTEG>(c, ray))); // image(p) += integrate(...)
             }
             if constexpr (RESUME) resume_save(rng, *res, slot, lane, acc); // undivided
+            if constexpr (ADAPT) {
+                ad->mean[(size_t)slot * 64 + lane] = nz_mean;
+                ad->m2[(size_t)slot * 64 + lane]   = nz_m2;
+            }
             acc = cdivs(acc, (float)i_end); // image(p) /= num_pixel_samples
 #ifdef SP_MEGA_PROF
             for (int k = 0; k < 4; ++k) prof[k] = c.prof[k];
 #endif
             rays_total += c.rays;
             shadow_total += c.shadow;
-            samples_total += args.spp;
+            samples_total += ADAPT ? a_more : args.spp;
             draws_total += rng.draws;
         }
+        if constexpr (ADAPT)
+            if (lane == 0) ad->done[slot] = a_n0 + a_more; // after the tile's state: the next call's first index
         if constexpr (PROBE) { // probe pass (sp_mega.hip tile_order): how long this tile kept the wave
             if (lane == 0) args.tile_time[slot] = (float)(__builtin_amdgcn_s_memrealtime() - t_start);
             continue;
@@ -542,6 +599,11 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_resume_kernel(S
 {
     render_tiles_body<INTEG, false, 0, true>(sc, args, &res);
 }
+template <int INTEG, int MINW>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_adapt_kernel(Scene sc, RenderArgs args, ResumeArgs res, AdaptArgs ad)
+{
+    render_tiles_body<INTEG, false, 0, true, true>(sc, args, &res, &ad);
+}
 template <int MINW, bool REPLAY>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_tail_kernel(Scene sc, RenderArgs args)
 {
@@ -575,6 +637,16 @@ hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeAr
                          size_t lds_bytes, hipStream_t stream);
 int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
 size_t     resume_static_lds(int integ, int variant);
+// adaptive progress objects (sp_mega_adapt*.hip, the same split; sp_adaptive.hip: selection, list, resolve)
+using AdaptFn = void (*)(Scene, RenderArgs, ResumeArgs, AdaptArgs);
+AdaptFn    adapt_direct(int variant);
+AdaptFn    adapt_mandelbrot();
+AdaptFn    adapt_rrnee(int waves);
+AdaptFn    adapt_path(int integ);
+hipError_t launch_adapt(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, const AdaptArgs& ad, int integ,
+                        int variant, int blocks, size_t lds_bytes, hipStream_t stream);
+int        adapt_blocks_per_cu(int integ, int variant, size_t lds_bytes);
+size_t     adapt_static_lds(int integ, int variant);
 hipError_t launch_tile_order(float* tile_time, int64_t n_tiles, float factor, int tiles_x, int step, int32_t* order,
                              hipStream_t stream);
 
