@@ -15,6 +15,16 @@
 // tests/test_libm_exact.py.  The same source is compiled for the host and for gfx950 with
 // explicit fma() and no contraction, so the host verification carries over to the device.
 //
+// Shape: expf, logf and powf -- the functions the glossy estimate's loops call --
+// have one exit.  glibc tests for its special arguments first and returns early; on the GPU every
+// such return became a nested exec-mask region with a "this lane returned" flag, paid by waves in
+// which no lane is special.  Here the main path runs for every lane from the raw bits (it must be
+// harmless on any input: masked table indices, no float-to-int conversion, no shift by a data
+// value), and the special cases override its result afterwards in one region marked unlikely,
+// glibc's tests in reverse order so the first to hit wins.  Same results for every bit pattern.
+// erff, acosf, atanf, atan2f and the unbounded sinf / cosf keep fdlibm's / glibc's branch shape:
+// they run once per estimate or less, and the one-exit forms of erff and acosf measured slower.
+//
 // Attribution: the algorithms, polynomial coefficients and tables restated here are those of
 // the GNU C Library 2.35 (glibc, LGPL-2.1-or-later), whose expf/logf/powf/sinf/cosf come from
 // Arm's optimized-routines (Copyright (c) 2017-2018 Arm Ltd., MIT / LGPL as distributed with
@@ -101,13 +111,9 @@ SP_HD float lm_expf(float x)
     const uint32_t ix     = f2u(x);
     const uint32_t abstop = (ix >> 20) & 0x7ffu;
     const double   xd     = (double)x;
-    if (abstop > 0x42au) {
-        if (ix == 0xff800000u) return 0.0f;
-        if (abstop > 0x7f7u) return x86_add(x, x); // inf or nan
-        if (x > gf(EXPF_LIM, 0)) return __builtin_inff(); // __math_oflowf(0)
-        if (gf(EXPF_LIM, 1) > x) return 0.0f;             // __math_uflowf(0)
-        if (!(gf(EXPF_LIM, 2) <= x)) return u2f(0x00000001u); // __math_may_uflowf(0): 0x1.4p-75f^2
-    }
+    // Main path for every input: it reads the raw bits of kd (no float-to-int conversion) and
+    // masks its table index, so it is harmless on inf, NaN and out-of-range x; those lanes'
+    // results are replaced below.
     const double invln2n = gd(EXPF_K, 1), shift = gd(EXPF_K, 0);
     double       kd      = dfma(invln2n, xd, shift);
     const uint64_t ki    = d2u(kd);
@@ -120,25 +126,23 @@ SP_HD float lm_expf(float x)
     double       y  = dfma(r, gd(EXPF_K, 4), gd(ONE_D, 0));
     y               = dfma(z, r2, y);
     y               = y * s;
-    return (float)y;
+    float res       = (float)y;
+    if (__builtin_expect(abstop > 0x42au, 0)) { // |x| >= 88: glibc's tests, the first to hit applied last
+        if (!(gf(EXPF_LIM, 2) <= x)) res = u2f(0x00000001u); // __math_may_uflowf(0): 0x1.4p-75f^2
+        if (gf(EXPF_LIM, 1) > x) res = 0.0f;                 // __math_uflowf(0)
+        if (x > gf(EXPF_LIM, 0)) res = __builtin_inff();     // __math_oflowf(0)
+        if (abstop > 0x7f7u) res = is_nan_bits(x) ? x86_quiet(x) : x + x; // inf or nan: x + x
+        if (ix == 0xff800000u) res = 0.0f;
+    }
+    return res;
 }
 
 // ------------------------------------------------------------------------------------ logf
-SP_HD float lm_logf(float x)
+// logf's main path from the (normal, positive) argument's bits.  Integer operations on the bits and
+// a masked table index: harmless on any bit pattern.
+SP_HD float logf_core(uint32_t ix)
 {
-#if defined(SP_XP_FASTLIBM) && defined(__HIP_DEVICE_COMPILE__) // timing-only bound (sp_path.hpp SP_XP_*)
-    return __logf(x);
-#endif
     using namespace glibc;
-    uint32_t ix = f2u(x);
-    if (ix == 0x3f800000u) return 0.0f;
-    if (ix - 0x00800000u > 0x7effffffu) {
-        if (ix * 2u == 0u) return -__builtin_inff();                 // __math_divzerof(1)
-        if (ix == 0x7f800000u) return x;
-        if (ix * 2u > 0xfeffffffu) return x86_quiet(x);              // NaN: (x-x)/(x-x)
-        if (ix & 0x80000000u) return x86_default_nan();              // x < 0
-        ix = f2u(x * gf(TWO23_F, 0)) - (23u << 23);                  // subnormal
-    }
     const uint32_t tmp  = ix - 0x3f330000u;
     const uint32_t i    = (tmp >> 19) & 15u;
     const int32_t  k    = (int32_t)tmp >> 23;
@@ -152,6 +156,24 @@ SP_HD float lm_logf(float x)
     y                   = dfma(r2, gd(LOGF_K, 1), y);
     y                   = dfma(r2, y, r + y0);
     return (float)y;
+}
+SP_HD float lm_logf(float x)
+{
+#if defined(SP_XP_FASTLIBM) && defined(__HIP_DEVICE_COMPILE__) // timing-only bound (sp_path.hpp SP_XP_*)
+    return __logf(x);
+#endif
+    using namespace glibc;
+    const uint32_t ix = f2u(x);
+    float          res = logf_core(ix);
+    res                = (ix == 0x3f800000u) ? 0.0f : res;
+    if (__builtin_expect(ix - 0x00800000u > 0x7effffffu, 0)) { // glibc's tests, the first to hit applied last
+        res = logf_core(f2u(x * gf(TWO23_F, 0)) - (23u << 23));   // subnormal
+        if (ix & 0x80000000u) res = x86_default_nan();             // x < 0
+        if (ix * 2u > 0xfeffffffu) res = x86_quiet(x);             // NaN: (x-x)/(x-x)
+        if (ix == 0x7f800000u) res = x;
+        if (ix * 2u == 0u) res = -__builtin_inff();                // __math_divzerof(1)
+    }
+    return res;
 }
 
 // ------------------------------------------------------------------------------------ powf
@@ -167,41 +189,48 @@ SP_HD int powf_checkint(uint32_t iy)
 SP_HD bool powf_zeroinfnan(uint32_t ix) { return 2u * ix - 1u >= 2u * 0x7f800000u - 1u; }
 SP_HD bool issignalingf(uint32_t ix) { return ((ix & 0x7fffffffu) > 0x7f800000u) && !(ix & 0x00400000u); }
 
-SP_HD float lm_powf(float x, float y)
+// powf's tests on zero, inf, NaN, negative and subnormal arguments (glibc's order).  Returns true
+// with the result in *early, or false after folding the sign and the subnormal scaling into *ix and
+// *sign_bias.  Only ever entered from one rarely taken region, so its early returns cost the main
+// path nothing.
+SP_HD bool powf_special(float x, float y, uint32_t* ixp, uint32_t* sign_bias, float* early)
 {
-#if defined(SP_XP_FASTLIBM) && defined(__HIP_DEVICE_COMPILE__) // timing-only bound (sp_path.hpp SP_XP_*)
-    return __powf(x, y);
-#endif
     using namespace glibc;
-    uint32_t       sign_bias = 0;
-    uint32_t       ix = f2u(x);
+    uint32_t       ix = *ixp;
     const uint32_t iy = f2u(y);
-    if (ix - 0x00800000u >= 0x7f000000u || powf_zeroinfnan(iy)) {
-        if (powf_zeroinfnan(iy)) {
-            if (2u * iy == 0u) return issignalingf(ix) ? x86_add(x, y) : 1.0f;
-            if (ix == 0x3f800000u) return issignalingf(iy) ? x86_add(x, y) : 1.0f;
-            if (2u * ix > 2u * 0x7f800000u || 2u * iy > 2u * 0x7f800000u) return x86_add(x, y);
-            if (2u * ix == 2u * 0x3f800000u) return 1.0f;
-            if ((2u * ix < 2u * 0x3f800000u) == !(iy & 0x80000000u)) return 0.0f;
-            return y * y;
-        }
-        if (powf_zeroinfnan(ix)) {
-            float x2 = x * x;
-            if ((ix & 0x80000000u) && powf_checkint(iy) == 1) x2 = -x2;
-            return (iy & 0x80000000u) ? 1.0f / x2 : x2;
-        }
-        if (ix & 0x80000000u) {
-            const int yint = powf_checkint(iy);
-            if (yint == 0) return x86_default_nan(); // __math_invalidf(x): (x-x)/(x-x)
-            if (yint == 1) sign_bias = 1u << 16;
-            ix &= 0x7fffffffu;
-        }
-        if (ix < 0x00800000u) {
-            ix = f2u(x * gf(TWO23_F, 0)) & 0x7fffffffu;
-            ix -= 23u << 23;
-        }
+    if (powf_zeroinfnan(iy)) {
+        if (2u * iy == 0u) { *early = issignalingf(ix) ? x86_add(x, y) : 1.0f; return true; }
+        if (ix == 0x3f800000u) { *early = issignalingf(iy) ? x86_add(x, y) : 1.0f; return true; }
+        if (2u * ix > 2u * 0x7f800000u || 2u * iy > 2u * 0x7f800000u) { *early = x86_add(x, y); return true; }
+        if (2u * ix == 2u * 0x3f800000u) { *early = 1.0f; return true; }
+        if ((2u * ix < 2u * 0x3f800000u) == !(iy & 0x80000000u)) { *early = 0.0f; return true; }
+        *early = y * y;
+        return true;
     }
-    // log2_inline
+    if (powf_zeroinfnan(ix)) {
+        float x2 = x * x;
+        if ((ix & 0x80000000u) && powf_checkint(iy) == 1) x2 = -x2;
+        *early = (iy & 0x80000000u) ? 1.0f / x2 : x2;
+        return true;
+    }
+    if (ix & 0x80000000u) {
+        const int yint = powf_checkint(iy);
+        if (yint == 0) { *early = x86_default_nan(); return true; } // __math_invalidf(x): (x-x)/(x-x)
+        if (yint == 1) *sign_bias = 1u << 16;
+        ix &= 0x7fffffffu;
+    }
+    if (ix < 0x00800000u) {
+        ix = f2u(x * gf(TWO23_F, 0)) & 0x7fffffffu;
+        ix -= 23u << 23;
+    }
+    *ixp = ix;
+    return false;
+}
+// log2_inline from the (normal, positive) argument's bits: integer operations and a masked table
+// index, harmless on any bit pattern
+SP_HD double powf_log2(uint32_t ix)
+{
+    using namespace glibc;
     const uint32_t tmp  = ix - 0x3f330000u;
     const uint32_t i    = (tmp >> 19) & 15u;
     const uint32_t top  = tmp & 0xff800000u;
@@ -217,19 +246,13 @@ SP_HD float lm_powf(float x, float y)
     const double   r4   = r2 * r2;
     double         q    = dfma(r, gd(POWF_A, 4), y0);
     q                   = dfma(r2, p, q);
-    yy                  = dfma(yy, r4, q);
-    const double ylogx  = (double)y * yy;
-    if (((d2u(ylogx) >> 47) & 0xffffu) > 0x80beu) {
-        if (ylogx > gd(POWF_LIM, 0)) return sign_bias ? -__builtin_inff() : __builtin_inff(); // __math_oflowf
-        if (ylogx > gd(POWF_LIM, 1)) {
-            // may overflow: glibc checks the rounding direction; round-to-nearest keeps the value
-            const float one = gf(POWF_FLIM, 1) < 0.0f ? 1.0f : 1.0f;
-            (void)one;
-        }
-        if (!(gd(POWF_LIM, 2) < ylogx)) return sign_bias ? -0.0f : 0.0f;               // __math_uflowf
-        if (!(gd(POWF_LIM, 3) <= ylogx)) return u2f(sign_bias ? 0x80000001u : 0x00000001u); // may_uflow
-    }
-    // exp2_inline(ylogx, sign_bias)
+    return dfma(yy, r4, q);
+}
+// exp2_inline(ylogx, sign_bias): reads the raw bits of kd (no float-to-int conversion) and masks
+// its table index, harmless on any ylogx
+SP_HD float powf_exp2(double ylogx, uint32_t sign_bias)
+{
+    using namespace glibc;
     const double   shift = gd(EXP2F_K, 0);
     double         kd    = ylogx + shift;
     const uint64_t ki    = d2u(kd);
@@ -245,6 +268,54 @@ SP_HD float lm_powf(float x, float y)
     res              = dfma(zz, rr2, res);
     res              = res * s;
     return (float)res;
+}
+
+SP_HD float lm_powf(float x, float y)
+{
+#if defined(SP_XP_FASTLIBM) && defined(__HIP_DEVICE_COMPILE__) // timing-only bound (sp_path.hpp SP_XP_*)
+    return __powf(x, y);
+#endif
+    using namespace glibc;
+    uint32_t sign_bias = 0;
+    uint32_t ix        = f2u(x);
+    bool     done      = false;
+    float    early     = 0.0f;
+    if (__builtin_expect(ix - 0x00800000u >= 0x7f000000u || powf_zeroinfnan(f2u(y)), 0))
+        done = powf_special(x, y, &ix, &sign_bias, &early);
+    const double ylogx = (double)y * powf_log2(ix);
+    float        res   = powf_exp2(ylogx, sign_bias);
+    if (__builtin_expect(((d2u(ylogx) >> 47) & 0xffffu) > 0x80beu, 0)) { // glibc's tests, the first to hit applied last
+        // (between POWF_LIM 1 and 0 glibc checks the rounding direction: round-to-nearest keeps res)
+        if (!(gd(POWF_LIM, 3) <= ylogx)) res = u2f(sign_bias ? 0x80000001u : 0x00000001u); // may_uflow
+        if (!(gd(POWF_LIM, 2) < ylogx)) res = sign_bias ? -0.0f : 0.0f;                     // __math_uflowf
+        if (ylogx > gd(POWF_LIM, 0)) res = sign_bias ? -__builtin_inff() : __builtin_inff(); // __math_oflowf
+    }
+    return done ? early : res;
+}
+
+// powf(x, y) for the arguments of beckmann_sample11: lm_powf without its tests.
+//   x = 1 - max(U1, 1e-6f) with U1 in [0, 1 - 2^-24]: x in [2^-24, 1 - 1e-6f] -- normal, positive,
+//       below 1, so no zero / inf / NaN / negative / subnormal test can fire for x;
+//   y = fit(acosf(c)) for c in [0, .9999f]: y in [POWF_FIT_LO, POWF_FIT_HI] = [0x1.c7d2b8p-2,
+//       0x1.f9b33ap-1] (about [0.44514, 0.98769]; tools/libm_exhaustive.cpp fitrange evaluates
+//       every such c), finite and non-zero;
+//   |y * log2 x| <= 0.9877 * 24 < 126, so neither range test on ylogx can fire.
+// tools/libm_exhaustive.cpp powf_unit compares it with lm_powf for every x of the interval
+// (tests/test_libm_forms.py).  Outside the box lm_powf_unit_claims() describes, the entry promises
+// nothing: it is for that one call site.  (A fall-back to lm_powf for unclaimed arguments, in a
+// never-taken region, was measured: it cost the DirectLighting tail kernel 4 B of scratch.)
+constexpr uint32_t POWF_UNIT_X_LO = 0x33800000u, POWF_UNIT_X_HI = 0x3f7fffefu; // 2^-24, 1 - 1e-6f
+constexpr uint32_t POWF_FIT_LO = 0x3ee3e95cu, POWF_FIT_HI = 0x3f7cd99du;
+SP_HD bool lm_powf_unit_claims(float x, float y)
+{
+    return f2u(x) - POWF_UNIT_X_LO <= POWF_UNIT_X_HI - POWF_UNIT_X_LO && f2u(y) - POWF_FIT_LO <= POWF_FIT_HI - POWF_FIT_LO;
+}
+SP_HD float lm_powf_unit(float x, float y)
+{
+#if defined(SP_XP_FASTLIBM) && defined(__HIP_DEVICE_COMPILE__) // timing-only bound (sp_path.hpp SP_XP_*)
+    return __powf(x, y);
+#endif
+    return powf_exp2((double)y * powf_log2(f2u(x)), 0u);
 }
 
 // ------------------------------------------------------------------------------------ sinf / cosf

@@ -75,19 +75,9 @@ SP_HD float rsqrtss_emulated(float x, const RsqrtTable& t)
 {
     const uint32_t u = f2u(x);
     const uint32_t e = (u >> 23) & 0xffu;
-    if ((u >> 31) != 0u) {
-        if ((u & 0x7fffffffu) == 0u) return u2f(0xff800000u); // -0 -> -inf
-        if (e == 0xffu && (u & 0x7fffffu) != 0u) return u2f(u | 0x400000u); // NaN -> quiet
-        return u2f(0xffc00000u);                               // negative -> default NaN
-    }
-    if (e == 0xffu) {
-        if ((u & 0x7fffffu) != 0u) return u2f(u | 0x400000u);
-        return 0.0f;                                           // +inf -> +0
-    }
-    if (e == 0u) {
-        if (u == 0u) return u2f(t.zero_result);
-        return u2f(t.denorm_result);                           // RSQRTSS treats denormals as 0
-    }
+    // The table path for every input, the special classes overridden afterwards in one rarely
+    // taken region.  The index is (p << bits) | (23-bit mantissa >> (23 - bits)) with p 0 or 1:
+    // below 2 << bits for every bit pattern (negative, zero, denormal, inf and NaN included).
     const int32_t  ex   = (int32_t)e - 127;
     const int32_t  p    = ex & 1;
     const int32_t  q    = (ex - p) / 2;
@@ -95,7 +85,20 @@ SP_HD float rsqrtss_emulated(float x, const RsqrtTable& t)
     const uint32_t i    = ((uint32_t)p << t.bits) | m;
     const uint32_t r    = t.pack_shift ? (t.pack_hi | ((uint32_t)((const uint16_t*)t.entries)[i] << t.pack_shift)) : t.entries[i];
     const int32_t  re   = (int32_t)((r >> 23) & 0xffu) - q;
-    return u2f((r & 0x807fffffu) | ((uint32_t)re << 23));
+    uint32_t       res  = (r & 0x807fffffu) | ((uint32_t)re << 23);
+    if (__builtin_expect(u - 0x00800000u >= 0x7f000000u, 0)) { // negative, zero, denormal, inf or NaN
+        const bool nan = e == 0xffu && (u & 0x7fffffu) != 0u;
+        if ((u >> 31) != 0u) {
+            res = 0xffc00000u;                                 // negative -> default NaN
+            if (nan) res = u | 0x400000u;                      // NaN -> quiet
+            if ((u & 0x7fffffffu) == 0u) res = 0xff800000u;    // -0 -> -inf
+        } else if (e == 0xffu) {
+            res = nan ? (u | 0x400000u) : 0u;                  // +inf -> +0
+        } else {
+            res = (u == 0u) ? t.zero_result : t.denorm_result; // RSQRTSS treats denormals as 0
+        }
+    }
+    return u2f(res);
 }
 
 // math/Math.h:205 sp::rsqrt: r = RSQRTSS(a); c = 1.5*r + ((a*-0.5)*r)*(r*r)

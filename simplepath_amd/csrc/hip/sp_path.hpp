@@ -1897,11 +1897,13 @@ __device__ __forceinline__ float fresnel_dielectric(float cos_i, float eta_i, fl
     }
     const float sin_i = sqrt_unit(std_max(0.0f, 1.0f - cos_i * cos_i));
     const float sin_t = eta_i / eta_t * sin_i;
-    if (sin_t >= 1) return 1.0f;
+    // total internal reflection (sin_t >= 1) is a late override: such a lane computes on with
+    // cos_t = sqrt_unit(+0) (max(0, 1 - sin_t^2) is +0 there, for an infinite sin_t too)
     const float cos_t = sqrt_unit(std_max(0.0f, 1.0f - sin_t * sin_t));
     const float parl  = ((eta_t * cos_i) - (eta_i * cos_t)) / ((eta_t * cos_i) + (eta_i * cos_t));
     const float perp  = ((eta_i * cos_i) - (eta_t * cos_t)) / ((eta_i * cos_i) + (eta_t * cos_t));
-    return (parl * parl + perp * perp) / 2.0f;
+    const float f     = (parl * parl + perp * perp) / 2.0f;
+    return (sin_t >= 1) ? 1.0f : f;
 }
 
 // math/Math.h:230 erfinv
@@ -1954,7 +1956,7 @@ __device__ __forceinline__ P2 beckmann_sample11(float cos_theta_i, float U1, flo
     const float sample_x    = std_max(U1, 1e-6f);
     const float theta_i     = lm_acosf(cos_theta_i);
     const float fit         = 1.0f + theta_i * (-0.876f + theta_i * (0.4265f - 0.0594f * theta_i));
-    float       b           = c - (1.0f + c) * lm_powf(1.0f - sample_x, fit);
+    float       b           = c - (1.0f + c) * lm_powf_unit(1.0f - sample_x, fit);
     const float sqrt_pi_inv = 1.0f / sqrt_f(k_pi);
     const float normalization =
         1.0f / (1.0f + c + sqrt_pi_inv * tan_theta_i * lm_expf(-cot_theta_i * cot_theta_i));
@@ -1991,22 +1993,23 @@ __device__ __forceinline__ f3 beckmann_sample(f3 wi, float ax, float ay, float U
 // BeckmannDistribution (materials/Material.h:213)
 __device__ __forceinline__ float beck_D(const Material& m, f3 wh)
 {
+    // an infinite tan^2 is a late override: arithmetic and lm_expf (harmless on any input) only
     const float t2 = tan2_theta(wh);
-    if (__builtin_isinf(t2)) return 0.0f;
     const float c4 = cos2_theta(wh) * cos2_theta(wh);
     const float cp = cos_phi(wh), sp = sin_phi(wh);
-    return lm_expf(-t2 * ((cp * cp) / (m.alpha_x * m.alpha_x) + (sp * sp) / (m.alpha_y * m.alpha_y))) /
-           (k_pi * m.alpha_x * m.alpha_y * c4);
+    const float d  = lm_expf(-t2 * ((cp * cp) / (m.alpha_x * m.alpha_x) + (sp * sp) / (m.alpha_y * m.alpha_y))) /
+                    (k_pi * m.alpha_x * m.alpha_y * c4);
+    return __builtin_isinf(t2) ? 0.0f : d;
 }
 __device__ __forceinline__ float beck_lambda(const Material& m, f3 w)
 {
-    const float at = abs_f(tan_theta(w));
-    if (__builtin_isinf(at)) return 0.0f;
+    // an infinite tangent and a >= 1.6 are late overrides (arithmetic only in between)
+    const float at    = abs_f(tan_theta(w));
     const float cp    = cos_phi(w), sp = sin_phi(w);
     const float alpha = sqrt_f((cp * cp) * (m.alpha_x * m.alpha_x) + (sp * sp) * (m.alpha_y * m.alpha_y));
     const float a     = 1.0f / (alpha * at);
-    if (a >= 1.6f) return 0.0f;
-    return (1.0f - 1.259f * a + 0.396f * (a * a)) / (3.535f * a + 2.181f * (a * a));
+    const float l     = (1.0f - 1.259f * a + 0.396f * (a * a)) / (3.535f * a + 2.181f * (a * a));
+    return (__builtin_isinf(at) || a >= 1.6f) ? 0.0f : l;
 }
 __device__ __forceinline__ float beck_G1(const Material& m, f3 w) { return 1.0f / (1.0f + beck_lambda(m, w)); }
 __device__ __forceinline__ float beck_G(const Material& m, f3 wo, f3 wi) { return 1.0f / (1.0f + beck_lambda(m, wo) + beck_lambda(m, wi)); }
@@ -2030,19 +2033,24 @@ __device__ __forceinline__ f3 beck_sample_wh(const Material& m, f3 wo, Rng& rng,
 // MicrofacetReflection (materials/Material.h:386)
 __device__ __forceinline__ rgb mf_eval(const Material& m, f3 wo, f3 wi, const Rsq& q)
 {
+    // One exit: the black cases select the result.  A lane on one of them computes on through
+    // normalize -- whose RSQRTSS table index (p << bits) | (mantissa >> (23 - bits)) is below
+    // 2 << bits for every bit pattern, NaN included, and is the only memory index on this path
+    // besides lm_expf's masked one -- and through arithmetic.
     const float ao = abs_f(wo.y), ai = abs_f(wi.y);
-    if (ai == 0.0f || ao == 0.0f) return mkc(0, 0, 0);
-    f3 wh = add(wi, wo);
-    if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return mkc(0, 0, 0);
+    f3          wh = add(wi, wo);
+    const bool  black = ai == 0.0f || ao == 0.0f || (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f);
     wh            = normalize(wh, q);
     const float f = fresnel_dielectric(dot(wi, wh), 1.0f, m.microfacet_ior);
-    return cdivs(cscale(cscale(cscale(m.microfacet_r, beck_D(m, wh)), beck_G(m, wo, wi)), f), 4.0f * ai * ao);
+    const rgb   c = cdivs(cscale(cscale(cscale(m.microfacet_r, beck_D(m, wh)), beck_G(m, wo, wi)), f), 4.0f * ai * ao);
+    return mkc(black ? 0.0f : c.r, black ? 0.0f : c.g, black ? 0.0f : c.b);
 }
 __device__ __forceinline__ float mf_pdf(const Material& m, f3 wo, f3 wi, const Rsq& q)
 {
-    if (!same_hemisphere(wo, wi)) return 0.0f;
-    const f3 wh = normalize(add(wo, wi), q);
-    return beck_pdf(m, wo, wh) / (4.0f * dot(wo, wh));
+    // one exit (indices: as mf_eval)
+    const f3    wh = normalize(add(wo, wi), q);
+    const float p  = beck_pdf(m, wo, wh) / (4.0f * dot(wo, wh));
+    return same_hemisphere(wo, wi) ? p : 0.0f;
 }
 __device__ __forceinline__ MSample mf_sample(const Material& m, f3 wo, Rng& rng, const Rsq& q)
 {
@@ -2114,7 +2122,7 @@ __device__ __forceinline__ P2 beckmann_sample11_pre(const BeckPre& p, float U1, 
     float       a        = -1.0f;
     float       c        = p.c0;
     const float sample_x = std_max(U1, 1e-6f);
-    float       b        = c - (1.0f + c) * lm_powf(1.0f - sample_x, p.fit);
+    float       b        = c - (1.0f + c) * lm_powf_unit(1.0f - sample_x, p.fit);
     // erfinv(b) at the converged b is the last iteration's inv_erf (same b, same function), so
     // the final erfinv is only evaluated when the loop ran out of iterations (b moved after it)
     float inv_erf   = 0.0f;
@@ -2178,13 +2186,12 @@ struct MGeom {
 __device__ __forceinline__ MGeom mf_sample_geom(const Material& m, const BeckPre& p, f3 wo, uint64_t u2, uint64_t u1,
                                                 const Rsq& q)
 {
-    MGeom g;
-    g.dir   = mk(0, 0, 0);
-    g.pdf   = 0.0f;
-    g.D = g.G = g.F = 0.0f;
-    g.den   = 1.0f;
-    g.valid = false;
-    g.black = true;
+    // One exit.  A lane that mf_sample would have returned early computes on to the end and has
+    // dir / pdf / valid / black selected; D, G, F and den are read only where !black.  What such a
+    // lane runs through is arithmetic, lm_expf (harmless on any input) and normalize, whose
+    // RSQRTSS table index (p << bits) | (mantissa >> (23 - bits)) is below 2 << bits for every bit
+    // pattern, NaN included; there is no other LDS or memory index on the path.
+    MGeom       g;
     const float U2 = canonical_from_u64(u2);
     const float U1 = canonical_from_u64(u1);
     P2          sl = beckmann_sample11_pre(p, U1, U2);
@@ -2196,26 +2203,23 @@ __device__ __forceinline__ MGeom mf_sample_geom(const Material& m, const BeckPre
     f3 wh = normalize(mk(-sl.x, 1.0f, -sl.y), q);
     if (p.flip) wh = neg(wh);
     const float dp = dot(wo, wh);
-    if (dp < 0.0f) return g;
-    const f3 wi = add(neg(wo), scale(2.0f * dot(wo, wh), wh));
-    if (!same_hemisphere(wo, wi)) return g;
+    const f3    wi = add(neg(wo), scale(2.0f * dot(wo, wh), wh));
+    g.valid        = !(dp < 0.0f) && same_hemisphere(wo, wi);
     // beck_pdf(m, wo, wh) with G1(wo) = 1 / (1 + lambda(wo))
     const float bpdf = m.sample_visible_area ? beck_D(m, wh) * (1.0f / (1.0f + p.lam_wo)) * abs_f(dot(wo, wh)) / abs_f(wo.y)
                                              : beck_D(m, wh) * abs_f(wh.y);
-    g.pdf   = bpdf / (4.0f * dp);
-    g.dir   = wi;
-    g.valid = true;
+    const float pdf = bpdf / (4.0f * dp);
+    g.pdf   = g.valid ? pdf : 0.0f;
+    g.dir   = mk(g.valid ? wi.x : 0.0f, g.valid ? wi.y : 0.0f, g.valid ? wi.z : 0.0f);
     // mf_eval(m, wo, wi) with G = 1 / (1 + lambda(wo) + lambda(wi))
     const float ao = abs_f(wo.y), ai = abs_f(wi.y);
-    if (ai == 0.0f || ao == 0.0f) return g;
-    f3 h = add(wi, wo);
-    if (h.x == 0.0f && h.y == 0.0f && h.z == 0.0f) return g;
+    f3          h  = add(wi, wo);
+    g.black = !g.valid || ai == 0.0f || ao == 0.0f || (h.x == 0.0f && h.y == 0.0f && h.z == 0.0f);
     h       = normalize(h, q);
     g.F     = fresnel_dielectric(dot(wi, h), 1.0f, m.microfacet_ior);
     g.G     = 1.0f / (1.0f + p.lam_wo + beck_lambda(m, wi));
     g.D     = beck_D(m, h);
     g.den   = 4.0f * ai * ao;
-    g.black = false;
     return g;
 }
 // one channel of the sample's colour: cdivs(cscale(cscale(cscale(R, D), G), F), den) per channel
@@ -2240,12 +2244,15 @@ __device__ __forceinline__ MSample mf_sample_pre_u(const Material& m, const Beck
 // computes one channel -- the other two would repeat its operations on the same bits.
 __device__ __forceinline__ void rho_accumulate(rgb& r, const MGeom& g, rgb R, bool grey)
 {
-    if (!(g.pdf > 0.0f)) return;
-    const float ay = abs_f(g.dir.y);
-    r.r = r.r + (mf_geom_channel(g, R.r) * ay) / g.pdf;
+    const bool  take = g.pdf > 0.0f; // a sample without a pdf adds nothing: selected, not skipped
+    const float ay   = abs_f(g.dir.y);
+    const float sr   = r.r + (mf_geom_channel(g, R.r) * ay) / g.pdf;
+    r.r              = take ? sr : r.r;
     if (!grey) {
-        r.g = r.g + (mf_geom_channel(g, R.g) * ay) / g.pdf;
-        r.b = r.b + (mf_geom_channel(g, R.b) * ay) / g.pdf;
+        const float sg = r.g + (mf_geom_channel(g, R.g) * ay) / g.pdf;
+        const float sb = r.b + (mf_geom_channel(g, R.b) * ay) / g.pdf;
+        r.g            = take ? sg : r.g;
+        r.b            = take ? sb : r.b;
     }
 }
 // SP_RHO_ALIGNED: the estimate's 32 words (idx .. idx + 31, reserved: no twist) are read as one

@@ -1,7 +1,12 @@
 // Exhaustive bit-exactness check of spm::lm_* (simplepath_amd/csrc/common/sp_libm.h) against the
 // host glibc float libm.  Usage: libm_exhaustive <func> [stride] [threads]
-//   func: sinf cosf sincosf expf logf erff acosf atanf fmod1 roundf powf atan2f
+//   func: sinf cosf sincosf expf logf erff acosf atanf fmod1 roundf powf atan2f powf_unit fitrange
 // Prints "<func> checked=<n> mismatches=<m>" and up to 8 examples.
+//   powf_unit: spm::lm_powf_unit's main path against spm::lm_powf for every float x of its claimed
+//       interval (every stride-th) at both ends of the claimed y interval and 38 values between,
+//       and that arguments just outside the box (and the special values) are not claimed.
+//   fitrange: the smallest and largest beckmann_sample11 exponent fit(acosf(c)) over every float c
+//       in [0, .9999f] -- the y interval lm_powf_unit claims.
 #include "../simplepath_amd/csrc/common/sp_libm.h"
 #include <atomic>
 #include <cmath>
@@ -81,6 +86,62 @@ int main(int argc, char** argv)
                 bad += b;
             });
         for (auto& x : th) x.join();
+    } else if (fn == "fitrange") {
+        // sp_path.hpp beck_pre / beckmann_sample11: not steep means !(cos_t > .9999f), cos_t >= 0
+        std::vector<uint32_t> lo(nth, 0x7f800000u), hi(nth, 0u);
+        std::vector<std::thread> th;
+        const uint32_t c_hi = bits(.9999f);
+        for (int t = 0; t < nth; ++t)
+            th.emplace_back([&, t] {
+                uint64_t c = 0;
+                for (uint64_t u = (uint64_t)t * stride; u <= c_hi; u += (uint64_t)nth * stride) {
+                    const float theta = spm::lm_acosf(flt((uint32_t)u));
+                    const float fit   = 1.0f + theta * (-0.876f + theta * (0.4265f - 0.0594f * theta));
+                    lo[t] = std::min(lo[t], bits(fit)); // positive floats order like their bits
+                    hi[t] = std::max(hi[t], bits(fit));
+                    ++c;
+                }
+                checked += c;
+            });
+        for (auto& x : th) x.join();
+        uint32_t l = 0x7f800000u, h = 0u;
+        for (int t = 0; t < nth; ++t) { l = std::min(l, lo[t]); h = std::max(h, hi[t]); }
+        std::printf("fitrange lo=0x%08x (%a) hi=0x%08x (%a)\n", l, flt(l), h, flt(h));
+        if (l < spm::POWF_FIT_LO || h > spm::POWF_FIT_HI) ++bad; // a fit outside the claimed interval
+    } else if (fn == "powf_unit") {
+        std::vector<uint32_t> ys;
+        for (int j = 0; j < 40; ++j)
+            ys.push_back(spm::POWF_FIT_LO + (uint32_t)(((uint64_t)(spm::POWF_FIT_HI - spm::POWF_FIT_LO) * j) / 39));
+        std::vector<std::thread> th;
+        for (int t = 0; t < nth; ++t)
+            th.emplace_back([&, t] {
+                uint64_t c = 0, b = 0;
+                for (uint64_t u = spm::POWF_UNIT_X_LO + (uint64_t)t * stride; u <= spm::POWF_UNIT_X_HI; u += (uint64_t)nth * stride) {
+                    const float x = flt((uint32_t)u);
+                    for (uint32_t yb : ys) {
+                        const float y = flt(yb);
+                        const float got = spm::lm_powf_unit(x, y), want = spm::lm_powf(x, y);
+                        ++c;
+                        if (bits(want) != bits(got) || !spm::lm_powf_unit_claims(x, y)) { ++b; report(x, y, got, want); }
+                    }
+                }
+                checked += c;
+                bad += b;
+            });
+        for (auto& x : th) x.join();
+        // not claimed: one step outside each face of the box, and the values lm_powf tests for
+        uint64_t outside = 0;
+        const float xin = 0.5f, yin = flt(spm::POWF_FIT_LO);
+        const float xo[] = {flt(spm::POWF_UNIT_X_LO - 1u), flt(spm::POWF_UNIT_X_HI + 1u), 1.0f, 0.0f, -0.0f, -0.5f, 1e-40f, 2.0f, INFINITY, -INFINITY, NAN};
+        const float yo[] = {flt(spm::POWF_FIT_LO - 1u), flt(spm::POWF_FIT_HI + 1u), 1.0f, 0.0f, -0.0f, -flt(spm::POWF_FIT_LO), 1e-40f, 200.0f, INFINITY, -INFINITY, NAN};
+        for (float x : xo)
+            if (spm::lm_powf_unit_claims(x, yin)) ++outside;
+        for (float y : yo)
+            if (spm::lm_powf_unit_claims(xin, y)) ++outside;
+        if (!spm::lm_powf_unit_claims(xin, yin)) ++outside;
+        std::printf("powf_unit x=[0x%08x,0x%08x] y=[0x%08x,0x%08x] ys=%zu claimed_outside=%llu\n", spm::POWF_UNIT_X_LO, spm::POWF_UNIT_X_HI,
+                    spm::POWF_FIT_LO, spm::POWF_FIT_HI, ys.size(), (unsigned long long)outside);
+        bad += outside;
     } else if (fn == "sincosf") {  // the fused forms: bounded where abstop <= 0x42e (|x| < 120), general elsewhere
         std::vector<std::thread> th;
         const uint64_t total = 1ull << 32;
