@@ -3,9 +3,7 @@
 // the render kernel's queue (sp_adapt_kernel, sp_mega.hpp), and the resolve of the tiles the round
 // does not render.  One wave per tile where a tile is the unit; nothing here meets another wave's
 // address, so there is no atomic.
-#include "sp_device.hpp"
-
-#include <hip/hip_runtime.h>
+#include "sp_launch.hpp"
 
 namespace spd {
 namespace {

@@ -2,6 +2,8 @@
 #include "sp_device.hpp"
 #include "sp_wave.hpp"
 #include "sp_chunk.hpp"
+#include "sp_launch.hpp"
+#include "sp_plan.hpp"
 #include "../host/sp_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -15,32 +17,6 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
-
-namespace spd {
-hipError_t launch_render(const Scene& sc, const RenderArgs& args, int integ, int variant, int blocks, size_t lds_bytes,
-                         hipStream_t stream);
-int        render_blocks_per_cu(int integ, int variant, size_t lds_bytes);
-size_t     render_static_lds(int integ, int variant);
-hipError_t launch_tile_order(float* tile_time, int64_t n_tiles, float factor, int tiles_x, int step, int32_t* order,
-                             hipStream_t stream);
-bool       has_probe(int integ);
-hipError_t launch_probe(const Scene& sc, const RenderArgs& args, int integ, int variant, int blocks, size_t lds_bytes,
-                        hipStream_t stream);
-hipError_t launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream);
-int        tail_blocks_per_cu(int variant, size_t lds_bytes);
-hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, int integ, int variant, int blocks,
-                         size_t lds_bytes, hipStream_t stream);
-int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
-size_t     resume_static_lds(int integ, int variant);
-hipError_t launch_adapt(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, const AdaptArgs& ad, int integ,
-                        int variant, int blocks, size_t lds_bytes, hipStream_t stream);
-int        adapt_blocks_per_cu(int integ, int variant, size_t lds_bytes);
-size_t     adapt_static_lds(int integ, int variant);
-hipError_t launch_adapt_select(const AdaptArgs& ad, const SelectArgs& sa, float* err, uint32_t* flag, hipStream_t stream);
-hipError_t launch_adapt_compact(const AdaptArgs& ad, const int32_t* order, int64_t n_tiles, hipStream_t stream);
-hipError_t launch_adapt_resolve(const ResumeArgs& res, const AdaptArgs& ad, bool skip_active, int64_t n_tiles, float* out,
-                                hipStream_t stream);
-} // namespace spd
 
 namespace {
 thread_local std::string g_last_error;
@@ -213,6 +189,145 @@ struct DevBuf {
     void*  p     = nullptr;
     size_t bytes = 0;
 };
+
+static_assert(splan::MT_N == spm::MT_N && splan::MT_GEN_WORDS == spd::MT_GEN_WORDS && splan::WF_MAX_LIGHTS == spd::WF_MAX_LIGHTS,
+              "sp_plan.hpp's copies of the layout constants");
+
+// Grow-only scratch memory, device or pinned host.  reserve() does nothing when the capacity
+// suffices; otherwise it frees the old block BEFORE it allocates the new one -- the chunk and tail
+// budgets (free device memory + this buffer's capacity) count on that, and a 20 GB store must never
+// exist twice.  A failed allocation leaves the buffer empty (no pointer, no capacity: the next call
+// allocates again instead of trusting a stale size) and clears HIP's sticky error.
+template <bool PINNED>
+struct Scratch {
+    void*  ptr = nullptr;
+    size_t cap = 0; // bytes
+
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch(Scratch&& o) noexcept { *this = std::move(o); }
+    Scratch& operator=(Scratch&& o) noexcept // (o's destructor frees what this held)
+    {
+        std::swap(ptr, o.ptr);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~Scratch() { reset(); }
+    void reset()
+    {
+        if (ptr) (void)(PINNED ? hipHostFree(ptr) : hipFree(ptr));
+        ptr = nullptr;
+        cap = 0;
+    }
+    hipError_t reserve(size_t bytes)
+    {
+        if (bytes <= cap) return hipSuccess;
+        reset();
+        const hipError_t e = PINNED ? hipHostMalloc(&ptr, bytes, hipHostMallocDefault) : hipMalloc(&ptr, bytes);
+        if (e != hipSuccess) {
+            ptr = nullptr;
+            (void)hipGetLastError();
+            return e;
+        }
+        cap = bytes;
+        return hipSuccess;
+    }
+    template <typename T>
+    T* as() const { return static_cast<T*>(ptr); }
+};
+using DeviceScratch = Scratch<false>;
+using PinnedScratch = Scratch<true>;
+
+// The *_host forms: render n_tiles tiles into a temporary device image, then copy it to h_out
+template <typename Render>
+int render_to_host(int64_t n_tiles, float* h_out, Render&& render)
+{
+    const size_t  bytes = n_tiles > 0 ? (size_t)n_tiles * 64 * 3 * sizeof(float) : 0; // (< 0: the render refuses)
+    DeviceScratch d;
+    SP_HIP(d.reserve(std::max<size_t>(bytes, 4)));
+    int rc = render(d.as<float>());
+    if (rc == SP_OK && bytes) {
+        hipError_t e = hipMemcpy(h_out, d.ptr, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// N events or streams, created where they are first needed (a null entry: not yet) and destroyed with their owner
+template <typename H, hipError_t (*DESTROY)(H), int N = 1>
+struct Handles {
+    H h[N] = {};
+
+    Handles() = default;
+    Handles(const Handles&) = delete;
+    Handles(Handles&& o) noexcept { *this = std::move(o); }
+    Handles& operator=(Handles&& o) noexcept
+    {
+        std::swap(h, o.h);
+        return *this;
+    }
+    ~Handles()
+    {
+        for (H x : h)
+            if (x) (void)DESTROY(x);
+    }
+    operator H() const { return h[0]; }
+    H& operator[](int i) { return h[i]; }
+};
+template <int N = 1>
+using Events = Handles<hipEvent_t, hipEventDestroy, N>;
+template <int N = 1>
+using Streams = Handles<hipStream_t, hipStreamDestroy, N>;
+
+// a growing list of timing events (SP_RENDER_STAGE_TIMING)
+struct EventList {
+    std::vector<hipEvent_t> v;
+
+    EventList() = default;
+    EventList(const EventList&) = delete;
+    EventList& operator=(EventList&& o) noexcept
+    {
+        v.swap(o.v);
+        return *this;
+    }
+    ~EventList()
+    {
+        for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+};
+
+// Everything a scene's render calls keep on the device between calls.  Each member frees itself:
+// sp_scene::release() assigns an empty one, and a new member needs no second edit.
+struct RenderScratch {
+    static constexpr int STAGE_RING = 4; // sp_scene: the staging ring of host tile lists
+
+    DeviceScratch mt_state;     // the megakernel's generator store, per persistent wave
+    DeviceScratch tile_counter; // int32: the persistent queue's head
+    DeviceScratch counters;     // 8 x u64: rays, shadow rays, samples, draws, primary hits
+    DeviceScratch d_tiles;      // a host tile list's device copy
+    DeviceScratch wave_buf;     // wavefront pipeline state (sp_wave.hpp WaveArgs)
+    DeviceScratch ck_buf;       // sample-chunk pipeline: hits, radiance, snapshots
+    DeviceScratch ck_ctr;       // 2 x int32
+    DeviceScratch deep_buf;     // recursive integrators beyond MAX_RECURSION levels
+    // megakernel tile order: probe times, queue order -- a pair that grows together (order_tiles)
+    DeviceScratch d_tile_time, d_order;
+    DeviceScratch probe_counters;
+    DeviceScratch tail_buf;     // megakernel tail chunks: TailArgs, flags, hits, radiance, store
+    EventList     stage_ev;     // SP_RENDER_STAGE_TIMING
+    Streams<spd::WF_MAX_PARTS - 1> aux_stream; // parts 1.. of the wavefront pipeline
+    Events<>      ev_fork;
+    Events<spd::WF_MAX_PARTS - 1>  ev_join;
+    Events<spd::WF_MAX_PARTS>      ev_shade;
+    Events<>      ev0, ev1;
+    Events<>      ev_render;    // megakernel, stage timing: before the render launch
+    Events<>      ev_done;      // recorded at the end of every render call
+    bool          done_rec = false;
+    PinnedScratch h_tiles[STAGE_RING];    // pinned staging of host tile lists
+    Events<STAGE_RING> ev_tiles;          // after each buffer's staged copy
+    bool          tiles_rec[STAGE_RING] = {};
+    int           stage_next = 0;
+    int           n_cu = 0;     // the device's compute units (0: not asked yet)
+};
 } // namespace
 
 struct sp_scene {
@@ -228,35 +343,8 @@ struct sp_scene {
     spd::Scene           dev{};
     int                  geom_depth = 0, light_depth = 0;
     size_t               geom_nodes = 0, geom_slots = 0;
-    // render scratch
-    uint64_t*            mt_state     = nullptr;
-    size_t               mt_waves     = 0;
-    int32_t*             tile_counter = nullptr;
-    unsigned long long*  counters     = nullptr;
-    int32_t*             d_tiles      = nullptr;
-    size_t               d_tiles_cap  = 0;
-    void*                wave_buf     = nullptr; // wavefront pipeline state (sp_wave.hpp WaveArgs)
-    size_t               wave_cap     = 0;
-    std::vector<hipEvent_t> stage_ev;            // SP_RENDER_STAGE_TIMING
-    hipStream_t          aux_stream[spd::WF_MAX_PARTS - 1] = {}; // parts 1.. of the wavefront pipeline
-    hipEvent_t           ev_fork = nullptr, ev_join[spd::WF_MAX_PARTS - 1] = {};
-    hipEvent_t           ev_shade[spd::WF_MAX_PARTS] = {};
-    int                  n_cu         = 0;
-    hipEvent_t           ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t           ev_render = nullptr; // megakernel, stage timing: before the render launch
-    void*                ck_buf     = nullptr; // sample-chunk pipeline: hits, radiance, snapshots
-    size_t               ck_cap     = 0;
-    int32_t*             ck_ctr     = nullptr;
-    void*                deep_buf   = nullptr; // recursive integrators beyond MAX_RECURSION levels
-    size_t               deep_cap   = 0;
-    float*               d_tile_time = nullptr; // megakernel tile order: probe times, queue order
-    int32_t*             d_order     = nullptr;
-    size_t               order_cap   = 0;
-    unsigned long long*  probe_counters = nullptr;
-    void*                tail_buf    = nullptr; // megakernel tail chunks: TailArgs, flags, hits, radiance, store
-    size_t               tail_cap    = 0;
     // One scene, many host threads (the reference's render() shares one Scene across N threads,
-    // main.cpp:122-130): the render scratch above is per scene, so calls are serialised -- on the
+    // main.cpp:122-130): the render scratch is per scene, so calls are serialised -- on the
     // host by `mu`, and on the device by making each call's stream wait for the previous call's
     // last operation (ev_done), whichever stream that call used.  A host tile list is staged
     // through a ring of STAGE_RING pinned buffers (h_tiles), each rewritten only once its previous
@@ -264,15 +352,8 @@ struct sp_scene {
     // staged copy is queued behind the previous call's render (ev_done), so with one buffer a third
     // back-to-back call waited on the host for the first render; with the ring the host waits only
     // when STAGE_RING calls are queued ahead of the copy it needs.
-    static constexpr int STAGE_RING = 4;
     std::mutex           mu;
-    hipEvent_t           ev_done  = nullptr; // recorded at the end of every render call
-    bool                 done_rec = false;
-    int32_t*             h_tiles[STAGE_RING]     = {};  // pinned staging of host tile lists
-    size_t               h_tiles_cap[STAGE_RING] = {};
-    hipEvent_t           ev_tiles[STAGE_RING]    = {};  // after each buffer's staged copy
-    bool                 tiles_rec[STAGE_RING]   = {};
-    int                  stage_next = 0;
+    RenderScratch        scratch;
     // counts every change that invalidates a progress object made on this scene (sp_progress):
     // a new upload (the device scene is rebuilt) and sp_scene_set_resolution
     uint64_t             generation = 0;
@@ -282,54 +363,7 @@ struct sp_scene {
         if (device >= 0) (void)hipSetDevice(device);
         for (auto& b : bufs) (void)hipFree(b.p);
         bufs.clear();
-        if (mt_state) (void)hipFree(mt_state);
-        if (tile_counter) (void)hipFree(tile_counter);
-        if (counters) (void)hipFree(counters);
-        if (d_tiles) (void)hipFree(d_tiles);
-        if (wave_buf) (void)hipFree(wave_buf);
-        wave_buf = nullptr;
-        wave_cap = 0;
-        for (hipEvent_t e : stage_ev) (void)hipEventDestroy(e);
-        stage_ev.clear();
-        for (hipStream_t& a : aux_stream) {
-            if (a) (void)hipStreamDestroy(a);
-            a = nullptr;
-        }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        for (hipEvent_t& e : ev_join) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        for (hipEvent_t& e : ev_shade) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        ev_fork = nullptr;
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (ev_render) (void)hipEventDestroy(ev_render);
-        if (deep_buf) (void)hipFree(deep_buf);
-        if (ck_buf) (void)hipFree(ck_buf);
-        if (ck_ctr) (void)hipFree(ck_ctr);
-        ck_buf = nullptr; ck_ctr = nullptr; ck_cap = 0;
-        deep_buf = nullptr; deep_cap = 0;
-        if (d_tile_time) (void)hipFree(d_tile_time);
-        if (d_order) (void)hipFree(d_order);
-        if (probe_counters) (void)hipFree(probe_counters);
-        d_tile_time = nullptr; d_order = nullptr; order_cap = 0; probe_counters = nullptr;
-        if (tail_buf) (void)hipFree(tail_buf);
-        tail_buf = nullptr; tail_cap = 0;
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        ev_done = nullptr; done_rec = false;
-        for (int k = 0; k < STAGE_RING; ++k) {
-            if (ev_tiles[k]) (void)hipEventDestroy(ev_tiles[k]);
-            if (h_tiles[k]) (void)hipHostFree(h_tiles[k]);
-            ev_tiles[k] = nullptr; tiles_rec[k] = false; h_tiles[k] = nullptr; h_tiles_cap[k] = 0;
-        }
-        stage_next = 0;
-        mt_state = nullptr; tile_counter = nullptr; counters = nullptr; d_tiles = nullptr;
-        ev0 = ev1 = ev_render = nullptr;
-        mt_waves = 0; d_tiles_cap = 0;
+        scratch = RenderScratch{};
         device = -1; bvh_mode = -1;
     }
     ~sp_scene() { release(); }
@@ -373,19 +407,24 @@ struct sp_progress {
     bool                 adaptive = false;
     spd::AdaptArgs       ad{};
     std::vector<uint8_t> h_inside;       // per slot, its pixels inside the image
+    // every device array above comes from alloc() and lives here (freeing one waits for the kernels
+    // that still use it)
+    std::vector<DeviceScratch> mem;
 
-    void release()
+    // `bytes` of device memory this object owns, zeroed when asked
+    template <typename T>
+    hipError_t alloc(T** out, size_t n_bytes, bool zero = true)
+    {
+        mem.emplace_back();
+        if (hipError_t e = mem.back().reserve(n_bytes)) return e;
+        *out = mem.back().as<T>();
+        bytes += (int64_t)n_bytes;
+        return zero ? hipMemset(*out, 0, n_bytes) : hipSuccess;
+    }
+    ~sp_progress()
     {
         if (device >= 0) (void)hipSetDevice(device);
-        for (void* p : { (void*)d_ids, (void*)st.gen, (void*)st.pos, (void*)st.draws, (void*)st.sum, (void*)d_tile_time,
-                         (void*)d_order, (void*)ad.mean, (void*)ad.m2, (void*)ad.done, (void*)ad.err, (void*)ad.flag,
-                         (void*)ad.active, (void*)ad.n_active })
-            if (p) (void)hipFree(p); // (waits for kernels that still use it)
-        d_ids = nullptr; d_tile_time = nullptr; d_order = nullptr;
-        st    = spd::ResumeArgs{};
-        ad    = spd::AdaptArgs{};
     }
-    ~sp_progress() { release(); }
 };
 
 namespace {
@@ -951,12 +990,13 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     }
     d.stack_words     = d.stack_depth;
     d.any_stack_words = d.stackless ? 0 : std::max(wide.words.empty() ? bvh.max_depth : wide.depth, lbvh.max_depth) + 1;
-    SP_HIP(hipMalloc(&s->tile_counter, sizeof(int32_t)));
-    SP_HIP(hipMalloc(&s->counters, 8 * sizeof(unsigned long long)));
-    SP_HIP(hipEventCreate(&s->ev0));
-    SP_HIP(hipEventCreate(&s->ev1));
-    SP_HIP(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
-    for (hipEvent_t& e : s->ev_tiles) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    RenderScratch& r = s->scratch;
+    SP_HIP(r.tile_counter.reserve(sizeof(int32_t)));
+    SP_HIP(r.counters.reserve(8 * sizeof(unsigned long long)));
+    SP_HIP(hipEventCreate(&r.ev0[0]));
+    SP_HIP(hipEventCreate(&r.ev1[0]));
+    SP_HIP(hipEventCreateWithFlags(&r.ev_done[0], hipEventDisableTiming));
+    for (hipEvent_t& e : r.ev_tiles.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SP_OK;
 }
 
@@ -996,93 +1036,205 @@ int sp_render_tiles(sp_scene* s, const sp_render_params* p, float* d_out, sp_ren
     }
 }
 
-// Megakernel tail chunks (render_tiles_impl): the fraction of the tiles cut into sample chunks at
-// the end of the queue, and chunks per tile.
-#ifndef SP_TAIL_FRAC
-#define SP_TAIL_FRAC 0.12f
-#endif
-#ifndef SP_TAIL_CHUNKS
-#define SP_TAIL_CHUNKS 64
-#endif
-// The sample-chunk pipeline's fused form (render_tiles_impl): on, and the preps placed ahead of the
-// first chunks = persistent waves / SP_CK_FRONT_DIV
-#ifndef SP_CK_FUSED
-#define SP_CK_FUSED 1
-#endif
-#ifndef SP_CK_CAMFOLD
-#define SP_CK_CAMFOLD 1
-#endif
-#ifndef SP_CK_CAM_BLOCK
-#define SP_CK_CAM_BLOCK 32
-#endif
-#ifndef SP_CK_FRONT_DIV
-#define SP_CK_FRONT_DIV 8
-#endif
+using splan::ChunkPlan;
+using splan::RenderHooks;
 
-// Sample-chunk buffer plan (sp_chunk.hip): the same sizes decide AUTO and are allocated.
-struct ChunkPlan {
-    int64_t  chunks = 1;    // chunks per pixel
-    uint32_t len = 1;       // samples per chunk (the last may be short)
-    uint32_t gens = 0;      // generator-store generations per pixel
-    bool     known_draws = true;
-    size_t   b_hits = 0, b_L = 0, b_snap = 0, b_ctl = 0, b_draws = 0, total = 0;
+// ---- a request, resolved (sp_render_tiles, sp_render_tiles_host, sp_progress_create) -------------
+
+// The integrator: NOT_SPECIFIED falls back to the scene's, then to DirectLighting.  The megakernel
+// occupancy request with it: DirectLighting 1..4 waves per SIMD, IterativeRRNEE 2..4; the other
+// integrators have one variant each (0 = automatic)
+static int resolve_integrator(const sp_scene* s, int32_t requested, int waves_req, int32_t& integ)
+{
+    integ = requested;
+    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = s->host->integrator;
+    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = SP_INTEGRATOR_DIRECT_LIGHTING; // main.cpp:390
+    if (integ < SP_INTEGRATOR_MANDELBROT || integ > SP_INTEGRATOR_WHITTED) return fail(SP_ERR_ARG, "Unknown integrator type");
+    if (waves_req != 0) {
+        const bool ok = integ == SP_INTEGRATOR_DIRECT_LIGHTING ? (waves_req >= 1 && waves_req <= 4)
+                        : integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? (waves_req >= 2 && waves_req <= 4)
+                                                                  : false;
+        if (!ok) return fail(SP_ERR_ARG, "waves_per_simd: DirectLighting 1-4, IterativeRRNEE 2-4, else 0");
+    }
+    return SP_OK;
+}
+
+// The tiles: num_tiles entries of either list, or every tile of the frame
+struct TileList {
+    bool    listed = false;
+    int64_t n = 0, total = 0;
 };
-static ChunkPlan chunk_plan(const sp_scene* s, int64_t n_tiles, uint32_t spp, int64_t chunks_req)
+static TileList tile_list(const sp_scene* s, const int32_t* ids, const int32_t* d_ids, int64_t num_tiles)
 {
-    ChunkPlan c;
-    // chunks per pixel: the smallest power of two (<= 32) giving ~120K (tile, chunk) items (the
-    // best of the bunny 2/4/8-way shard sweep) unless the caller asks for a count
-    c.chunks = 1;
-    while (c.chunks < 32 && n_tiles * c.chunks < 120000) c.chunks *= 2;
-    if (chunks_req > 0) c.chunks = chunks_req;
-    c.chunks = std::min<int64_t>(c.chunks, spp);
-    c.len    = (uint32_t)((spp + c.chunks - 1) / c.chunks);
-    c.chunks = (spp + c.len - 1) / c.len;
-    // a DirectLighting sample draws at most 34 words per light (Light::sample 2 + glossy rho 32);
-    // +2 generations for the first twist and the one rng_prepare may twist ahead
-    const uint64_t max_draws = (uint64_t)spp * (uint64_t)std::max(1, s->dev.n_lights) * 34;
-    c.gens = (uint32_t)((max_draws + spm::MT_N - 1) / spm::MT_N + 2);
-    // per-sample draw counts from the camera pass unless an image light makes them depend on the
-    // drawn numbers (then ck_count replays Light::sample); SP_CHUNK_REPLAY=1 forces the replay (test)
-    c.known_draws = s->dev.n_lights <= 1000;
-    for (const auto& l : s->host->lights)
-        if (l.kind == SP_LIGHT_IMAGE_ENVIRONMENT) c.known_draws = false;
-    if (const char* v = std::getenv("SP_CHUNK_REPLAY")) c.known_draws = c.known_draws && std::atoi(v) == 0;
-    const size_t n_px = (size_t)n_tiles * 64;
-    c.b_hits  = n_px * spp * 16;
-    c.b_L     = n_px * spp * 12;
-    c.b_snap  = (size_t)n_tiles * c.gens * spd::MT_GEN_WORDS * 8;
-    c.b_ctl   = (size_t)c.chunks * n_px * 4;
-    c.b_draws = c.known_draws ? n_px * spp * 2 : 0;
-    c.total   = c.b_hits + c.b_L + c.b_snap + c.b_ctl + c.b_draws + 4 * 256;
-    return c;
+    TileList t;
+    sp_tile_count(s->dev.width, s->dev.height, &t.total);
+    t.listed = ids || d_ids;
+    t.n      = t.listed ? num_tiles : t.total;
+    return t;
+}
+static int check_tile_list(const TileList& t, const int32_t* ids)
+{
+    if (t.n < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
+    if (ids)
+        for (int64_t i = 0; i < t.n; ++i)
+            if (ids[i] < 0 || ids[i] >= t.total) return fail(SP_ERR_ARG, "tile id out of range");
+    return SP_OK;
 }
 
-// Queue neighbours of the tile-order kernel's cost estimate (sp_mega.hip tile_est): > 0 the queue
-// offset of the tile below, -1 the +-1 queue neighbours only, 0 none.  The tile ids are row-major
-// (base/TileScheduler.h:75-77: x = index % tiles_x), so for a whole frame (k = 1) the +-1 queue
-// neighbours are the tiles left and right.  For a host list with a constant stride k > 1 (a rank's
-// interleaved shard) they are the tiles k columns to the left and right -- the same row, not
-// adjacent -- and the tile below is tiles_x / k entries on when k divides tiles_x; otherwise
-// (-1) the rows of consecutive entries shift and only the +-1 entries are used.  SP_TILE_STRIDE_ROW
-// 0 drops the +-1 entries for k > 1 (the column blend alone, or the probe time alone when k does
-// not divide tiles_x).  Row blend kept for k > 1 by an A/B on elf's 8-way shard.
-#ifndef SP_TILE_STRIDE_ROW
-#define SP_TILE_STRIDE_ROW 1
-#endif
-static int order_neighbours(const sp_render_params* p, bool listed, int64_t n_tiles, int32_t tiles_x)
+static int device_cus(sp_scene* s)
 {
-    if (!listed) return tiles_x;
-    if (!p->tile_ids || n_tiles < 2) return 0;
-    const int64_t k = (int64_t)p->tile_ids[1] - p->tile_ids[0];
-    if (k <= 0) return 0;
-    for (int64_t i = 2; i < n_tiles; ++i)
-        if ((int64_t)p->tile_ids[i] - p->tile_ids[i - 1] != k) return 0;
-    if (k > 1 && !SP_TILE_STRIDE_ROW) return (tiles_x % k == 0) ? -(int)(tiles_x / k) - 1 : 0;
-    return (tiles_x % k == 0) ? (int)(tiles_x / k) : -1;
+    if (s->scratch.n_cu == 0) {
+        hipDeviceProp_t prop;
+        SP_HIP(hipGetDeviceProperties(&prop, s->device));
+        s->scratch.n_cu = prop.multiProcessorCount;
+    }
+    return SP_OK;
 }
 
-static int render_tiles_impl(sp_scene* s, const sp_render_params* p, float* d_out, sp_render_stats* stats)
+// dynamic LDS of a shading block: the RSQRTSS table and its four waves' traversal stacks
+static size_t shading_lds(const spd::Scene& d) { return (size_t)spd::rsqrt_words(d) * 4 + (size_t)4 * d.stack_words * 64 * 4; }
+
+// ---- the megakernel's launch setup (sp_render_tiles and calls on progress objects) --------------
+
+struct MegaSetup {
+    spd::MegaFamily family = spd::MegaFamily::Render;
+    int             integ = 0, variant = 0, blocks = 0;
+    size_t          lds_bytes = 0; // dynamic
+    size_t          waves = 0;     // persistent waves of the launch (4 per block)
+    spd::Scene      sc_run{};      // the resident scene with this render's options
+    spd::RenderArgs a{};           // all but out and spp
+};
+
+// Occupancy variant, persistent blocks, the generator store and the deep-recursion buffer (both in
+// the scene's scratch), and the launch arguments every kernel of the family takes.
+static int mega_setup(sp_scene* s, spd::MegaFamily family, int integ, int waves_req, const int32_t* d_ids, int64_t n_tiles,
+                      MegaSetup& m)
+{
+    RenderScratch& r = s->scratch;
+    m.family    = family;
+    m.integ     = integ;
+    m.lds_bytes = shading_lds(s->dev);
+    // the kernel's static LDS counts too (the largest over the variants this call may pick)
+    size_t lds_static = 0;
+    for (int v = 2; v <= 4; ++v) lds_static = std::max(lds_static, spd::kernel_static_lds(spd::mega_kernel(family, integ, v)));
+    const size_t lds_all = m.lds_bytes + lds_static;
+    if (lds_all > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    // waves per SIMD the kernel is compiled for (SP_KERNEL_VARIANT): DirectLighting 4,
+    // IterativeRRNEE 3 -- but never more than the LDS lets run (one 4-wave block per wave per
+    // SIMD): a deep BVH's stacks (lucy: 3 blocks per CU) would leave the extra occupancy's
+    // register budget paid for in spills and unused (lucy 1080p @ 256 spp: 2007 Mrays/s at 3
+    // waves, 1879 at 4; profiles/r02/s5)
+    const int lds_waves = (int)std::min<size_t>(8, (160 * 1024) / lds_all);
+    m.variant           = integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? 3 : 4;
+    m.variant           = std::max(2, std::min(m.variant, lds_waves));
+    if (waves_req) m.variant = waves_req;
+    const int per_cu = spd::kernel_blocks_per_cu(spd::mega_kernel(family, integ, m.variant), m.lds_bytes);
+    m.blocks         = (int)std::max<int64_t>(1, std::min((int64_t)r.n_cu * per_cu, (n_tiles + 3) / 4));
+    m.waves          = (size_t)m.blocks * 4;
+    SP_HIP(r.mt_state.reserve(m.waves * 2 * (size_t)spd::MT_GEN_WORDS * sizeof(uint64_t)));
+    m.sc_run         = s->dev;
+    m.a              = spd::RenderArgs{};
+    m.a.tile_ids     = d_ids;
+    m.a.num_tiles    = n_tiles;
+    m.a.tiles_x      = (s->dev.width + 7) / 8;
+    m.a.integrator   = integ;
+    m.a.tile_counter = r.tile_counter.as<int32_t>();
+    m.a.mt_state     = r.mt_state.as<uint64_t>();
+    m.a.counters     = r.counters.as<unsigned long long>();
+    // BruteForce / Whitted recursion deeper than the in-register arrays: global level records
+    if ((integ == SP_INTEGRATOR_BRUTE_FORCE || integ == SP_INTEGRATOR_WHITTED) && s->dev.max_depth > MAX_RECURSION) {
+        const size_t lanes = m.waves * 64;
+        SP_HIP(r.deep_buf.reserve(lanes * ((size_t)s->dev.max_depth + 1) * 5 * sizeof(float)));
+        m.a.deep        = r.deep_buf.as<float>();
+        m.a.deep_stride = lanes;
+    }
+    return SP_OK;
+}
+
+// Tile order (sp_mega.hip tile_order): a one-sample probe pass times every tile into tile_time, and
+// the queue order is written to `order` (the scene's scratch, or a progress object's own arrays).
+// Part of the render (timed with it); stream-ordered, no host wait.  Leaves the queue head at zero.
+static int order_tiles(sp_scene* s, const MegaSetup& m, float* probe_out, float* tile_time, int32_t* order, float hoist,
+                       int probe_step, int neighbours, hipStream_t stream)
+{
+    RenderScratch& r = s->scratch;
+    SP_HIP(r.probe_counters.reserve(8 * sizeof(unsigned long long)));
+    spd::RenderArgs pr = m.a;
+    pr.out        = probe_out;
+    pr.spp        = 1; // 2 or 4 probe samples measured no better (profiles/r03/ab_tile_order.txt, r04/tile_classes)
+    pr.tile_time  = tile_time;
+    pr.counters   = r.probe_counters.as<unsigned long long>(); // the probe's rays are not the render's
+    pr.tile_diag  = nullptr;
+    pr.probe_step = probe_step;
+    SP_HIP(spd::launch_probe(m.sc_run, pr, m.integ, m.variant, m.blocks, m.lds_bytes, stream));
+    SP_HIP(spd::launch_tile_order(tile_time, m.a.num_tiles, hoist, neighbours, probe_step, order, stream));
+    SP_HIP(hipMemsetAsync(r.tile_counter.ptr, 0, sizeof(int32_t), stream));
+    return SP_OK;
+}
+
+// The end of every call on a scene's scratch: ev1 closes the timed span, ev_done orders the next call
+static int end_call(sp_scene* s, hipStream_t stream)
+{
+    RenderScratch& r = s->scratch;
+    SP_HIP(hipEventRecord(r.ev1, stream));
+    SP_HIP(hipEventRecord(r.ev_done, stream));
+    r.done_rec = true;
+    return SP_OK;
+}
+
+// the host waits for the last call queued on the scene's scratch
+static int wait_done(sp_scene* s)
+{
+    if (s->scratch.done_rec) SP_HIP(hipEventSynchronize(s->scratch.ev_done));
+    return SP_OK;
+}
+
+// Waits for the call (ev1) and fills the statistics every call reports; c: the device counters
+static int read_stats(sp_scene* s, int pipeline, int launches, sp_render_stats* stats, unsigned long long (&c)[8])
+{
+    RenderScratch& r = s->scratch;
+    SP_HIP(hipEventSynchronize(r.ev1));
+    SP_HIP(hipMemcpy(c, r.counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    SP_HIP(hipEventElapsedTime(&ms, r.ev0, r.ev1));
+    stats->rays        = c[0];
+    stats->shadow_rays = c[1];
+    stats->samples     = c[2];
+    stats->rng_draws   = c[3];
+    stats->kernel_ms   = ms;
+    stats->pipeline    = pipeline;
+    stats->launches    = launches;
+    stats->parts       = 1;
+    stats->stack_depth = s->dev.stack_depth;
+    return SP_OK;
+}
+
+// ---- sp_render_tiles ------------------------------------------------------------------------------
+
+// One call, resolved: what its steps share and what they report
+struct RenderCall {
+    sp_scene*               s;
+    const sp_render_params* p;
+    float*                  d_out;
+    hipStream_t             stream;
+    RenderHooks             hooks;
+    int32_t                 integ = 0;
+    TileList                tiles;
+    const int32_t*          d_ids = nullptr; // device tile list (nullptr: slot = tile)
+    bool                    timing = false;
+    double                  ck_max_gb = 0.0; // the caller's cap on the chunk and tail buffers
+    size_t                  free_b = 0;      // free device memory at the top of the call
+    double                  ck_budget = 0.0;
+    bool                    image_light = false;
+    splan::Plan             plan;
+    // for the statistics
+    int     launches = 0, parts_used = 1;
+    int64_t tail_k = 0; // megakernel tail chunks: tiles cut (tail_ch chunks each)
+    int     tail_ch = 0;
+    float   stage[4] = { 0, 0, 0, 0 };
+};
+
+static int validate_render(const sp_scene* s, const sp_render_params* p, const float* d_out)
 {
     if (!s || !p || !d_out) return fail(SP_ERR_ARG, "null argument");
     if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_render_tiles");
@@ -1094,648 +1246,513 @@ static int render_tiles_impl(sp_scene* s, const sp_render_params* p, float* d_ou
     if (!(p->chunk_max_gb >= 0.0f)) return fail(SP_ERR_ARG, "chunk_max_gb < 0");
     if (p->tile_order_factor != p->tile_order_factor) return fail(SP_ERR_ARG, "tile_order_factor is NaN");
     if ((p->flags & ~(3 | SP_RENDER_STAGE_TIMING | SP_RENDER_PER_LANE_QUERIES)) != 0) return fail(SP_ERR_ARG, "unknown flags");
-    SP_HIP(hipSetDevice(s->device));
-    int32_t integ = p->integrator;
-    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = s->host->integrator;
-    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = SP_INTEGRATOR_DIRECT_LIGHTING; // main.cpp:390
-    if (integ < SP_INTEGRATOR_MANDELBROT || integ > SP_INTEGRATOR_WHITTED) return fail(SP_ERR_ARG, "Unknown integrator type");
-    // megakernel occupancy request: DirectLighting 1..4 waves per SIMD, IterativeRRNEE 2..4;
-    // the other integrators have one variant each (0 = automatic)
-    const int waves_req = p->waves_per_simd;
-    if (waves_req != 0) {
-        const bool ok = integ == SP_INTEGRATOR_DIRECT_LIGHTING ? (waves_req >= 1 && waves_req <= 4)
-                        : integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? (waves_req >= 2 && waves_req <= 4)
-                                                                  : false;
-        if (!ok) return fail(SP_ERR_ARG, "waves_per_simd: DirectLighting 1-4, IterativeRRNEE 2-4, else 0");
-    }
-    int64_t total;
-    sp_tile_count(s->dev.width, s->dev.height, &total);
-    const bool    listed  = p->tile_ids || p->d_tile_ids;
-    const int64_t n_tiles = listed ? p->num_tiles : total;
-    if (n_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
-    if (p->tile_ids)
-        for (int64_t i = 0; i < n_tiles; ++i)
-            if (p->tile_ids[i] < 0 || p->tile_ids[i] >= total) return fail(SP_ERR_ARG, "tile id out of range");
-    hipStream_t stream = static_cast<hipStream_t>(p->stream);
-    if (stats) *stats = sp_render_stats{};
-    if (n_tiles == 0) return SP_OK;
-    // the previous call on this scene may have used another stream: its work on the shared
-    // scratch comes first (sp_scene::mu)
-    if (s->done_rec) SP_HIP(hipStreamWaitEvent(stream, s->ev_done, 0));
-    const int32_t* d_ids = p->d_tile_ids; // device tile list (nullptr: slot = tile)
-    if (p->tile_ids) {
-        if ((size_t)n_tiles > s->d_tiles_cap) {
-            if (s->d_tiles) (void)hipFree(s->d_tiles);
-            s->d_tiles = nullptr;
-            SP_HIP(hipMalloc(&s->d_tiles, (size_t)n_tiles * sizeof(int32_t)));
-            s->d_tiles_cap = (size_t)n_tiles;
-        }
-        // staged through the next pinned buffer of the ring, so the caller's array is free once this
-        // returns; the host waits only if that buffer's copy (STAGE_RING calls back) has not run
-        const int k = s->stage_next;
-        s->stage_next = (k + 1) % sp_scene::STAGE_RING;
-        if (s->tiles_rec[k]) SP_HIP(hipEventSynchronize(s->ev_tiles[k]));
-        if ((size_t)n_tiles > s->h_tiles_cap[k]) {
-            if (s->h_tiles[k]) (void)hipHostFree(s->h_tiles[k]);
-            s->h_tiles[k]     = nullptr;
-            s->h_tiles_cap[k] = 0;
-            SP_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_tiles[k]), (size_t)n_tiles * sizeof(int32_t), hipHostMallocDefault));
-            s->h_tiles_cap[k] = (size_t)n_tiles;
-        }
-        std::memcpy(s->h_tiles[k], p->tile_ids, (size_t)n_tiles * sizeof(int32_t));
-        SP_HIP(hipMemcpyAsync(s->d_tiles, s->h_tiles[k], (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        SP_HIP(hipEventRecord(s->ev_tiles[k], stream));
-        s->tiles_rec[k] = true;
-        d_ids = s->d_tiles;
-    }
-    if (s->n_cu == 0) {
-        hipDeviceProp_t prop;
-        SP_HIP(hipGetDeviceProperties(&prop, s->device));
-        s->n_cu = prop.multiProcessorCount;
-    }
-    const bool timing   = (p->flags & SP_RENDER_STAGE_TIMING) != 0;
-    float      stage[4] = { 0, 0, 0, 0 };
-    const int  asked    = p->flags & 3;
-    int        pipeline = asked;
-    if (pipeline == SP_PIPELINE_SAMPLE_CHUNKS && integ != SP_INTEGRATOR_DIRECT_LIGHTING)
+    return SP_OK;
+}
+
+// A host tile list goes to the device through the next pinned buffer of the ring, so the caller's
+// array is free once the call returns; the host waits only if that buffer's copy (STAGE_RING calls
+// back) has not run
+static int stage_tile_list(RenderCall& c)
+{
+    RenderScratch& r     = c.s->scratch;
+    const size_t   bytes = (size_t)c.tiles.n * sizeof(int32_t);
+    SP_HIP(r.d_tiles.reserve(bytes));
+    const int k  = r.stage_next;
+    r.stage_next = (k + 1) % RenderScratch::STAGE_RING;
+    if (r.tiles_rec[k]) SP_HIP(hipEventSynchronize(r.ev_tiles[k]));
+    SP_HIP(r.h_tiles[k].reserve(bytes));
+    std::memcpy(r.h_tiles[k].ptr, c.p->tile_ids, bytes);
+    SP_HIP(hipMemcpyAsync(r.d_tiles.ptr, r.h_tiles[k].ptr, bytes, hipMemcpyHostToDevice, c.stream));
+    SP_HIP(hipEventRecord(r.ev_tiles[k], c.stream));
+    r.tiles_rec[k] = true;
+    c.d_ids        = r.d_tiles.as<int32_t>();
+    return SP_OK;
+}
+
+// Which pipeline (sp_plan.hpp plan_render), and the sample chunks' buffers when it is theirs
+static int plan_call(RenderCall& c)
+{
+    sp_scene*      s = c.s;
+    RenderScratch& r = s->scratch;
+    const int asked  = c.p->flags & 3;
+    if (asked == SP_PIPELINE_SAMPLE_CHUNKS && c.integ != SP_INTEGRATOR_DIRECT_LIGHTING)
         return fail(SP_ERR_UNSUPPORTED, "the sample-chunk pipeline implements DirectLighting");
-    const bool wave_ok = integ == SP_INTEGRATOR_DIRECT_LIGHTING && s->dev.n_lights <= spd::WF_MAX_LIGHTS;
-    if (pipeline == SP_PIPELINE_WAVEFRONT && !wave_ok)
+    if (asked == SP_PIPELINE_WAVEFRONT && !splan::wave_ok(c.integ, s->dev.n_lights))
         return fail(SP_ERR_UNSUPPORTED, "the wavefront pipeline implements DirectLighting (<= 32 lights)");
-    // AUTO (measurements: DESIGN.md §3, §6).  The megakernel renders the 1-GPU frame fastest
-    // (bunny 1080p @ 256 spp: 2974 Mrays/s, wavefront 2305).  Below SP_CHUNK_MAX_TILES = 24000
-    // tiles (the 2-8-GPU shards) one pixel's sample chain bounds the megakernel and the sample
-    // chunks win (8-way shard 2444 against 823), when their buffers fit the budget.  With an image
-    // light ck_count replays Light::sample, so the chunks pay off only below half that (spheres
-    // 1024^2 @ 64 spp, 16384 tiles: chunks 2902, megakernel 2973).  The wavefront runs on request,
-    // or from SP_WAVE_MIN_TILES tiles (test hook).
-    int64_t wave_min = INT64_MAX, chunk_max = 24000;
-    if (const char* v = std::getenv("SP_WAVE_MIN_TILES")) wave_min = std::atoll(v);
-    if (const char* v = std::getenv("SP_CHUNK_MAX_TILES")) chunk_max = std::atoll(v);
-    const uint32_t spp_u = p->samples_per_pixel;
-    int64_t chunks_req = p->chunks_per_pixel;
-    if (chunks_req == 0)
-        if (const char* v = std::getenv("SP_CHUNKS")) chunks_req = std::max<int64_t>(1, std::atoll(v)); // test hook
-    const ChunkPlan cp = chunk_plan(s, n_tiles, spp_u, chunks_req);
-    double ck_max_gb = p->chunk_max_gb > 0.0f ? (double)p->chunk_max_gb : 96.0;
-    if (p->chunk_max_gb == 0.0f)
-        if (const char* v = std::getenv("SP_CHUNK_MAX_GB")) ck_max_gb = std::atof(v); // test hook
+    c.ck_max_gb = c.p->chunk_max_gb > 0.0f ? (double)c.p->chunk_max_gb : c.hooks.chunk_max_gb;
     // budget: the caller's cap, and never more than the device can still give (the buffer held
     // from an earlier call is freed first)
-    size_t free_b = 0, total_b = 0;
-    SP_HIP(hipMemGetInfo(&free_b, &total_b));
-    const double ck_budget = std::min(ck_max_gb * 1e9, (double)free_b + (double)s->ck_cap);
-    bool image_light = false;
-    for (const auto& l : s->host->lights) image_light = image_light || l.kind == SP_LIGHT_IMAGE_ENVIRONMENT;
-    // Megakernel tail chunks (below): DirectLighting from 2.5 tiles per persistent wave (16 per CU
-    // at full occupancy) and 128 spp, where the draw counts are known from the camera hits.  There
-    // the megakernel with its tile order and tail chunks beats the sample chunks (bunny 2-way shard
-    // 16200 tiles: 3620-3640 against 3170 Mrays/s, lucy 2-way 3227 against 2885; 3-way, 2.6 tiles
-    // per wave: 3398-3412 at a fraction of 0.4 against the fused chunks' 3321-3344; 4-way, 2 per
-    // wave: 2820-2980 against 3297 -- profiles/r06/tail/ab_shards*.log, ab_fused*.log).
-    // With an image light the preps replay Light::sample (TailArgs::replay): material_spheres with its
-    // image light, 1024^2 @ 64 spp (4 tiles per wave), 3814-3826 -> 3890-3895 Mrays/s (ab_spheres.log),
-    // so from 64 spp at 4 tiles per wave as well.
-    const int64_t tail_waves = (int64_t)std::max(1, s->n_cu) * 16;
-    const bool    tail_auto  = integ == SP_INTEGRATOR_DIRECT_LIGHTING && s->dev.n_lights <= 1000 && p->tail_fraction >= 0.0f &&
-                           ((spp_u >= 128 && 2 * n_tiles >= 5 * tail_waves) || (spp_u >= 64 && n_tiles >= 4 * tail_waves));
-    if (pipeline == SP_PIPELINE_AUTO) {
-        if (wave_ok && n_tiles >= wave_min) pipeline = SP_PIPELINE_WAVEFRONT;
-        else if (tail_auto) pipeline = SP_PIPELINE_MEGAKERNEL;
-        else if (integ == SP_INTEGRATOR_DIRECT_LIGHTING && n_tiles < (image_light ? chunk_max / 2 : chunk_max) &&
-                 (double)cp.total <= ck_budget)
-            pipeline = SP_PIPELINE_SAMPLE_CHUNKS;
-        else pipeline = SP_PIPELINE_MEGAKERNEL; // also when the chunk buffers would not fit the budget
-    }
-    if (pipeline == SP_PIPELINE_SAMPLE_CHUNKS && cp.total > s->ck_cap) {
-        if ((double)cp.total > ck_budget)
+    size_t total_b = 0;
+    SP_HIP(hipMemGetInfo(&c.free_b, &total_b));
+    c.ck_budget = std::min(c.ck_max_gb * 1e9, (double)c.free_b + (double)r.ck_buf.cap);
+    for (const auto& l : s->host->lights) c.image_light = c.image_light || l.kind == SP_LIGHT_IMAGE_ENVIRONMENT;
+    splan::PlanIn in;
+    in.integ         = c.integ;
+    in.n_tiles       = c.tiles.n;
+    in.spp           = c.p->samples_per_pixel;
+    in.n_lights      = s->dev.n_lights;
+    in.image_light   = c.image_light;
+    in.n_cu          = r.n_cu;
+    in.tail_fraction = c.p->tail_fraction;
+    in.chunks_req    = c.p->chunks_per_pixel;
+    in.ck_budget     = c.ck_budget;
+    in.asked         = asked;
+    c.plan           = splan::plan_render(in, c.hooks);
+    if (c.plan.pipeline == SP_PIPELINE_SAMPLE_CHUNKS && c.plan.cp.total > r.ck_buf.cap) {
+        if ((double)c.plan.cp.total > c.ck_budget)
             return fail(SP_ERR_UNSUPPORTED, "sample-chunk pipeline: buffers exceed the budget (chunk_max_gb / free "
                                             "device memory; render fewer tiles per call)");
-        if (s->ck_buf) (void)hipFree(s->ck_buf);
-        s->ck_buf = nullptr;
-        s->ck_cap = 0;
-        const hipError_t e = hipMalloc(&s->ck_buf, cp.total);
+        const hipError_t e = r.ck_buf.reserve(c.plan.cp.total);
         if (e != hipSuccess) {
-            s->ck_buf = nullptr;
-            (void)hipGetLastError();
             if (asked != SP_PIPELINE_AUTO) return fail(SP_ERR_HIP, std::string("sample-chunk buffers: ") + hipGetErrorString(e));
-            pipeline = SP_PIPELINE_MEGAKERNEL; // AUTO: the megakernel needs no per-sample buffers
-        } else {
-            s->ck_cap = cp.total;
+            c.plan.pipeline = SP_PIPELINE_MEGAKERNEL; // AUTO: the megakernel needs no per-sample buffers
         }
     }
-    SP_HIP(hipMemsetAsync(s->counters, 0, 8 * sizeof(unsigned long long), stream));
-    int launches = 0, parts_used = 1;
-    int64_t tail_k = 0;  // megakernel tail chunks: tiles cut (tail_ch chunks each)
-    int     tail_ch = 0;
-    if (pipeline == SP_PIPELINE_WAVEFRONT) {
-        const size_t stack_lds = (size_t)4 * s->dev.stack_words * 64 * 4;
-        if (stack_lds > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
-        // Pixels in flight per pass: all requested tiles unless the state would exceed the budget
-        // (SP_WAVE_MAX_GB, default 64 GB of the 288 GB HBM); larger jobs run in tile chunks.
-        double budget_gb = 64.0;
-        if (const char* v = std::getenv("SP_WAVE_MAX_GB")) budget_gb = std::atof(v);
-        const size_t  per_pix   = spd::wave_bytes_per_pixel(s->dev.n_lights);
-        // queue items pack the pixel slot in 27 bits (sp_wave.hip wf_shade)
-        const int64_t max_tiles = std::min<int64_t>((int64_t)1 << 21,
-                                                    std::max<int64_t>(1, (int64_t)(budget_gb * 1e9 / (double)(per_pix * 64))));
-        const int64_t chunk     = std::min<int64_t>(n_tiles, max_tiles);
-        const size_t  n         = (size_t)chunk * 64;
-        const size_t  need      = n * per_pix + spd::wave_stat_bytes((int64_t)n) + spd::wave_queue_bytes((int64_t)n, s->dev.n_lights) +
-                                  n * (size_t)std::max(1, s->dev.n_lights) + 256 * 12;
-        if (need > s->wave_cap) {
-            if (s->wave_buf) (void)hipFree(s->wave_buf);
-            s->wave_buf = nullptr;
-            s->wave_cap = 0;
-            SP_HIP(hipMalloc(&s->wave_buf, need));
-            s->wave_cap = need;
+    return SP_OK;
+}
+
+static int run_wavefront(RenderCall& c)
+{
+    sp_scene*      s = c.s;
+    RenderScratch& r = s->scratch;
+    const int64_t  n_tiles = c.tiles.n;
+    const size_t stack_lds = (size_t)4 * s->dev.stack_words * 64 * 4;
+    if (stack_lds > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    // Pixels in flight per pass: all requested tiles unless the state would exceed the budget
+    // (SP_WAVE_MAX_GB, default 64 GB of the 288 GB HBM); larger jobs run in tile chunks.
+    const size_t  per_pix   = spd::wave_bytes_per_pixel(s->dev.n_lights);
+    // queue items pack the pixel slot in 27 bits (sp_wave.hip wf_shade)
+    const int64_t max_tiles = std::min<int64_t>((int64_t)1 << 21,
+                                                std::max<int64_t>(1, (int64_t)(c.hooks.wave_max_gb * 1e9 / (double)(per_pix * 64))));
+    const int64_t chunk     = std::min<int64_t>(n_tiles, max_tiles);
+    const size_t  n         = (size_t)chunk * 64;
+    const size_t  need      = n * per_pix + spd::wave_stat_bytes((int64_t)n) + spd::wave_queue_bytes((int64_t)n, s->dev.n_lights) +
+                              n * (size_t)std::max(1, s->dev.n_lights) + 256 * 12;
+    SP_HIP(r.wave_buf.reserve(need));
+    // carve: every array 256-byte aligned (n is a multiple of 64)
+    char* b    = r.wave_buf.as<char>();
+    auto  take = [&](size_t bytes) { char* p = b; b += (bytes + 255) & ~(size_t)255; return p; };
+    spd::WaveArgs w{};
+    w.n        = (int64_t)n;
+    w.tiles_x  = (s->dev.width + 7) / 8;
+    w.spp      = c.p->samples_per_pixel;
+    w.mt_state = reinterpret_cast<uint64_t*>(take(n / 64 * 2 * spd::MT_GEN_WORDS * 8));
+    w.sh       = reinterpret_cast<float4*>(take(n * (size_t)std::max(1, s->dev.n_lights) * 32));
+    w.hit      = reinterpret_cast<float4*>(take(n * 16));
+    w.shp      = reinterpret_cast<float4*>(take(n * 16));
+    w.acc      = reinterpret_cast<float*>(take(n * 12));
+    w.rstate   = reinterpret_cast<uint32_t*>(take(n * 4));
+    w.queue    = reinterpret_cast<uint32_t*>(take(spd::wave_queue_bytes((int64_t)n, s->dev.n_lights)));
+    w.qcount   = nullptr; // per part (wave_render)
+    w.vis      = reinterpret_cast<uint8_t*>(take(n * (size_t)std::max(1, s->dev.n_lights)));
+    w.wstat    = reinterpret_cast<unsigned long long*>(take(spd::wave_stat_bytes((int64_t)n)));
+    w.counters = r.counters.as<unsigned long long>();
+    // SP_WAVE_DIAG=<file>: per-wave timeline of one sample's primary + shadow launches
+    DeviceScratch diag;
+    const size_t  diag_n = 2 * (n / 64) * 4;
+    if (c.hooks.wave_diag) {
+        SP_HIP(diag.reserve(diag_n * 8));
+        SP_HIP(hipMemsetAsync(diag.ptr, 0, diag_n * 8, c.stream));
+    }
+    w.diag = diag.as<unsigned long long>();
+    const int per_cu = spd::wave_traverse_blocks_per_cu(s->dev);
+    // two halves of the tile list on two streams, their shading kernels alternating (+11 %;
+    // 3 or 4 parts measured 1988 / 1821 against 2068 Mrays/s)
+    const int n_parts = std::min(2, spd::WF_MAX_PARTS);
+    if (!r.ev_fork) {
+        SP_HIP(hipEventCreateWithFlags(&r.ev_fork[0], hipEventDisableTiming));
+        for (auto& e : r.ev_shade.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    for (int k = 0; k + 1 < n_parts; ++k)
+        if (!r.aux_stream[k]) {
+            SP_HIP(hipStreamCreateWithFlags(&r.aux_stream[k], hipStreamNonBlocking));
+            SP_HIP(hipEventCreateWithFlags(&r.ev_join[k], hipEventDisableTiming));
         }
-        // carve: every array 256-byte aligned (n is a multiple of 64)
-        char* b    = static_cast<char*>(s->wave_buf);
-        auto  take = [&](size_t bytes) { char* r = b; b += (bytes + 255) & ~(size_t)255; return r; };
-        spd::WaveArgs w{};
-        w.n        = (int64_t)n;
-        w.tiles_x  = (s->dev.width + 7) / 8;
-        w.spp      = p->samples_per_pixel;
-        w.mt_state = reinterpret_cast<uint64_t*>(take(n / 64 * 2 * spd::MT_GEN_WORDS * 8));
-        w.sh       = reinterpret_cast<float4*>(take(n * (size_t)std::max(1, s->dev.n_lights) * 32));
-        w.hit      = reinterpret_cast<float4*>(take(n * 16));
-        w.shp      = reinterpret_cast<float4*>(take(n * 16));
-        w.acc      = reinterpret_cast<float*>(take(n * 12));
-        w.rstate   = reinterpret_cast<uint32_t*>(take(n * 4));
-        w.queue    = reinterpret_cast<uint32_t*>(take(spd::wave_queue_bytes((int64_t)n, s->dev.n_lights)));
-        w.qcount   = nullptr; // per part (wave_render)
-        w.vis      = reinterpret_cast<uint8_t*>(take(n * (size_t)std::max(1, s->dev.n_lights)));
-        w.wstat    = reinterpret_cast<unsigned long long*>(take(spd::wave_stat_bytes((int64_t)n)));
-        w.counters = s->counters;
-        // SP_WAVE_DIAG=<file>: per-wave timeline of one sample's primary + shadow launches
-        const char*         diag_path = std::getenv("SP_WAVE_DIAG");
-        unsigned long long* d_diag    = nullptr;
-        const size_t        diag_n    = 2 * (n / 64) * 4;
-        if (diag_path) {
-            SP_HIP(hipMalloc(&d_diag, diag_n * 8));
-            SP_HIP(hipMemsetAsync(d_diag, 0, diag_n * 8, stream));
+    std::vector<hipEvent_t>& stage_ev = r.stage_ev.v;
+    const size_t             n_ev     = c.timing ? 3 * (size_t)w.spp + 3 : 0;
+    while (stage_ev.size() < n_ev) {
+        hipEvent_t e;
+        SP_HIP(hipEventCreate(&e));
+        stage_ev.push_back(e);
+    }
+    SP_HIP(hipEventRecord(r.ev0, c.stream));
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += chunk) {
+        const int64_t nt = std::min<int64_t>(chunk, n_tiles - t0);
+        w.n        = nt * 64;
+        w.tile_ids = c.d_ids ? c.d_ids + t0 : nullptr;
+        if (!c.d_ids && t0 > 0) {
+            // identity ids beyond the first chunk: materialise them
+            std::vector<int32_t> ids((size_t)nt);
+            for (int64_t i = 0; i < nt; ++i) ids[(size_t)i] = (int32_t)(t0 + i);
+            SP_HIP(r.d_tiles.reserve((size_t)chunk * sizeof(int32_t)));
+            SP_HIP(hipMemcpyAsync(r.d_tiles.ptr, ids.data(), (size_t)nt * 4, hipMemcpyHostToDevice, c.stream));
+            SP_HIP(hipStreamSynchronize(c.stream));
+            w.tile_ids = r.d_tiles.as<int32_t>();
         }
-        w.diag = d_diag;
-        const int per_cu = spd::wave_traverse_blocks_per_cu(s->dev);
-        // two halves of the tile list on two streams, their shading kernels alternating (+11 %;
-        // 3 or 4 parts measured 1988 / 1821 against 2068 Mrays/s)
-        const int n_parts = std::min(2, spd::WF_MAX_PARTS);
-        if (!s->ev_fork) {
-            SP_HIP(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-            for (auto& e : s->ev_shade) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        for (int k = 0; k + 1 < n_parts; ++k)
-            if (!s->aux_stream[k]) {
-                SP_HIP(hipStreamCreateWithFlags(&s->aux_stream[k], hipStreamNonBlocking));
-                SP_HIP(hipEventCreateWithFlags(&s->ev_join[k], hipEventDisableTiming));
-            }
-        const size_t n_ev = timing ? 3 * (size_t)w.spp + 3 : 0;
-        while (s->stage_ev.size() < n_ev) {
-            hipEvent_t e;
-            SP_HIP(hipEventCreate(&e));
-            s->stage_ev.push_back(e);
-        }
-        SP_HIP(hipEventRecord(s->ev0, stream));
-        for (int64_t t0 = 0; t0 < n_tiles; t0 += chunk) {
-            const int64_t nt = std::min<int64_t>(chunk, n_tiles - t0);
-            w.n        = nt * 64;
-            w.tile_ids = d_ids ? d_ids + t0 : nullptr;
-            if (!d_ids && t0 > 0) {
-                // identity ids beyond the first chunk: materialise them
-                std::vector<int32_t> ids((size_t)nt);
-                for (int64_t i = 0; i < nt; ++i) ids[(size_t)i] = (int32_t)(t0 + i);
-                if ((size_t)nt > s->d_tiles_cap) {
-                    if (s->d_tiles) (void)hipFree(s->d_tiles);
-                    s->d_tiles = nullptr;
-                    SP_HIP(hipMalloc(&s->d_tiles, (size_t)chunk * sizeof(int32_t)));
-                    s->d_tiles_cap = (size_t)chunk;
-                }
-                SP_HIP(hipMemcpyAsync(s->d_tiles, ids.data(), (size_t)nt * 4, hipMemcpyHostToDevice, stream));
-                SP_HIP(hipStreamSynchronize(stream));
-                w.tile_ids = s->d_tiles;
-            }
-            w.pb = 0;
-            w.pe = w.n;
-            SP_HIP(spd::wave_render(s->dev, w, d_out + (size_t)t0 * 64 * 3, per_cu, s->n_cu, stream,
-                                    timing ? s->stage_ev.data() : nullptr, s->aux_stream, n_parts - 1,
-                                    s->ev_fork, s->ev_join, s->ev_shade, &parts_used));
-            launches += 3 + 4 * (int)w.spp;
-            if (d_diag) {
-                std::vector<unsigned long long> h(diag_n);
-                SP_HIP(hipStreamSynchronize(stream));
-                SP_HIP(hipMemcpy(h.data(), d_diag, diag_n * 8, hipMemcpyDeviceToHost));
-                if (FILE* f = std::fopen(diag_path, "wb")) {
-                    std::fwrite(h.data(), 8, diag_n, f);
-                    std::fclose(f);
-                }
-                (void)hipFree(d_diag);
-                d_diag = nullptr;
-                w.diag = nullptr;
-            }
-            if (timing) {
-                SP_HIP(hipEventSynchronize(s->stage_ev[n_ev - 1]));
-                auto el = [&](size_t a, size_t b) {
-                    float ms = 0.0f;
-                    (void)hipEventElapsedTime(&ms, s->stage_ev[a], s->stage_ev[b]);
-                    return ms;
-                };
-                stage[0] += el(0, 1) + el(n_ev - 2, n_ev - 1);
-                for (uint32_t i = 0; i < w.spp; ++i) {
-                    const size_t b = 1 + 3 * (size_t)i;
-                    stage[1] += el(b, b + 1);
-                    stage[2] += el(b + 1, b + 2);
-                    stage[3] += el(b + 2, b + 3);
-                }
-            }
-        }
-    } else if (pipeline == SP_PIPELINE_SAMPLE_CHUNKS) {
-        // sp_chunk.hip: camera rays for all (pixel, sample) at once, a per-pixel replay of the
-        // stream positions into the generator store, then every (tile, chunk) shaded in parallel,
-        // and the in-order sum (buffers: chunk_plan above)
-        const int    rs_words  = spd::rsqrt_words(s->dev);
-        const size_t lds_bytes = (size_t)rs_words * 4 + (size_t)4 * s->dev.stack_words * 64 * 4;
-        if (lds_bytes > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
-        const size_t n_px   = (size_t)n_tiles * 64;
-        if (!s->ck_ctr) SP_HIP(hipMalloc(&s->ck_ctr, 2 * sizeof(int32_t)));
-        const int per_cu = spd::chunk_blocks_per_cu(lds_bytes);
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)s->n_cu * per_cu, (n_tiles * cp.chunks + 3) / 4));
-        char*          base = static_cast<char*>(s->ck_buf);
-        spd::ChunkArgs a{};
-        a.tile_ids    = d_ids;
-        a.num_tiles   = n_tiles;
-        a.tiles_x     = (s->dev.width + 7) / 8;
-        a.spp         = spp_u;
-        a.chunks      = (uint32_t)cp.chunks;
-        a.chunk_len   = cp.len;
-        a.n_px        = n_px;
-        a.hits        = reinterpret_cast<float4*>(base);
-        a.L           = reinterpret_cast<float*>(base + cp.b_hits);
-        a.gens        = reinterpret_cast<uint64_t*>(base + cp.b_hits + cp.b_L);
-        a.gens_per_px = cp.gens;
-        a.snap_ctl    = reinterpret_cast<uint32_t*>(base + cp.b_hits + cp.b_L + cp.b_snap);
-        a.draws       = cp.known_draws ? reinterpret_cast<uint16_t*>(base + cp.b_hits + cp.b_L + cp.b_snap + cp.b_ctl) : nullptr;
-        a.n_lights    = s->dev.n_lights;
-        a.counter     = s->ck_ctr;
-        a.counters    = s->counters;
-        a.out         = d_out;
-        // Fused form (known draw counts): ck_camera, then the counts and the shading in ONE persistent
-        // queue of the megakernel's tail kernel (sp_mega.hpp, RenderArgs::tail_front): each tile's
-        // prep (stream positions, generations into the store) runs P tiles ahead of its chunks, so the
-        // HBM-bound twists overlap the shading instead of running as a phase of their own (ck_count).
-        // Same store contents and chunk starts, same image.  SP_CK_FUSED=0: the four-kernel form.
-        bool fused = cp.known_draws && SP_CK_FUSED;
-        if (const char* v = std::getenv("SP_CK_FUSED")) fused = cp.known_draws && std::atoi(v) != 0;
-        SP_HIP(hipMemsetAsync(s->ck_ctr, 0, 2 * sizeof(int32_t), stream));
-        if (fused) {
-            // the tail kernel's LDS (the megakernel's: RSQRTSS table + per-wave stacks) and occupancy
-            size_t lds_static = spd::render_static_lds(SP_INTEGRATOR_DIRECT_LIGHTING, 4);
-            if (lds_bytes + lds_static > 160 * 1024) fused = false;
-        }
-        if (fused) {
-            const size_t a_hdr = 256, a_rdy = ((size_t)n_tiles * 4 + 255) / 256 * 256, need = a_hdr + 2 * a_rdy;
-            if (need > s->tail_cap) {
-                if (s->tail_buf) (void)hipFree(s->tail_buf);
-                s->tail_buf = nullptr;
-                s->tail_cap = 0;
-                SP_HIP(hipMalloc(&s->tail_buf, need));
-                s->tail_cap = need;
-            }
-            char*         tb = static_cast<char*>(s->tail_buf);
-            spd::TailArgs ta{};
-            ta.n_prep      = n_tiles;
-            ta.n_items     = n_tiles * cp.chunks;
-            ta.chunks      = (uint32_t)cp.chunks;
-            ta.chunk_len   = cp.len;
-            ta.gens_per_px = cp.gens;
-            ta.n_px        = n_px;
-            ta.hits        = a.hits;
-            ta.L           = a.L;
-            ta.gens        = a.gens;
-            ta.snap_ctl    = a.snap_ctl;
-            ta.draws       = a.draws;
-            ta.ready       = reinterpret_cast<uint32_t*>(tb + a_hdr);
-            // the camera pass as the queue's first items (SP_CK_CAMFOLD; blocks of SP_CK_CAM_BLOCK
-            // samples per item) instead of the ck_camera kernel before it
-            bool cam_fold = SP_CK_CAMFOLD;
-            if (const char* v = std::getenv("SP_CK_CAMFOLD")) cam_fold = std::atoi(v) != 0;
-            if (cam_fold) {
-                ta.cam_block = SP_CK_CAM_BLOCK;
-                if (const char* v = std::getenv("SP_CK_CAM_BLOCK")) ta.cam_block = (uint32_t)std::max(1, std::atoi(v));
-                ta.n_cam     = n_tiles * (int64_t)((spp_u + ta.cam_block - 1) / ta.cam_block);
-                ta.cam_done  = reinterpret_cast<uint32_t*>(tb + a_hdr + a_rdy);
-                ta.draws_out = a.draws;
-            }
-            SP_HIP(hipMemcpyAsync(tb, &ta, sizeof(ta), hipMemcpyHostToDevice, stream));
-            SP_HIP(hipMemsetAsync(ta.ready, 0, 2 * a_rdy, stream));
-            spd::RenderArgs ra{};
-            ra.out          = d_out;
-            ra.tile_ids     = d_ids;
-            ra.num_tiles    = n_tiles;
-            ra.tiles_x      = a.tiles_x;
-            ra.spp          = spp_u;
-            ra.integrator   = integ;
-            ra.tile_counter = s->ck_ctr;
-            ra.counters     = s->counters;
-            ra.tail_prep    = ta.n_prep;
-            ra.tail_items   = ta.n_items;
-            const int     t_per_cu = spd::tail_blocks_per_cu(0, lds_bytes); // 0: sp_fused_kernel
-            const int64_t t_waves  = (int64_t)s->n_cu * t_per_cu * 4;
-            // P: the preps ahead of the first chunks; the rest are dealt one per tile's chunks
-            int64_t front = std::max<int64_t>(1, t_waves / SP_CK_FRONT_DIV);
-            if (const char* v = std::getenv("SP_CK_FRONT_DIV")) front = std::max<int64_t>(1, t_waves / std::max(1, std::atoi(v)));
-            ra.tail_front = front;
-            ra.tail_cam   = ta.n_cam;
-            ra.tail       = reinterpret_cast<const spd::TailArgs*>(tb);
-            const int t_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)s->n_cu * t_per_cu,
-                                                                               (n_tiles * (cp.chunks + 1) + 3) / 4));
-            SP_HIP(hipEventRecord(s->ev0, stream));
-            if (!cam_fold) SP_HIP(spd::chunk_camera(s->dev, a, s->n_cu, stream));
-            SP_HIP(spd::launch_tail(s->dev, ra, 0, t_blocks, lds_bytes, stream));
-            SP_HIP(spd::chunk_sum(s->dev, a, stream));
-            launches = cam_fold ? 2 : 3;
-        } else {
-            SP_HIP(hipEventRecord(s->ev0, stream));
-            SP_HIP(spd::chunk_render(s->dev, a, blocks, s->n_cu, stream));
-            launches = 4;
-        }
-    } else {
-        const int    rs_words  = spd::rsqrt_words(s->dev);
-        const size_t lds_bytes = (size_t)rs_words * 4 + (size_t)4 * s->dev.stack_words * 64 * 4;
-        // the kernel's static LDS counts too (the largest over the variants this call may pick)
-        size_t lds_static = 0;
-        for (int v = 2; v <= 4; ++v) lds_static = std::max(lds_static, spd::render_static_lds(integ, v));
-        const size_t lds_all = lds_bytes + lds_static;
-        if (lds_all > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
-        // waves per SIMD the kernel is compiled for (SP_KERNEL_VARIANT): DirectLighting 4,
-        // IterativeRRNEE 3 -- but never more than the LDS lets run (one 4-wave block per wave per
-        // SIMD): a deep BVH's stacks (lucy: 3 blocks per CU) would leave the extra occupancy's
-        // register budget paid for in spills and unused (lucy 1080p @ 256 spp: 2007 Mrays/s at 3
-        // waves, 1879 at 4; profiles/r02/s5)
-        const int lds_waves = (int)std::min<size_t>(8, (160 * 1024) / lds_all);
-        int       variant   = integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? 3 : 4;
-        variant             = std::max(2, std::min(variant, lds_waves));
-        if (waves_req) variant = waves_req;
-        const int     per_cu  = spd::render_blocks_per_cu(integ, variant, lds_bytes);
-        const int64_t max_blk = (int64_t)s->n_cu * per_cu;
-        const int64_t need    = (n_tiles + 3) / 4;
-        const int     blocks  = (int)std::max<int64_t>(1, std::min(max_blk, need));
-        const size_t  waves   = (size_t)blocks * 4;
-        if (waves > s->mt_waves) {
-            if (s->mt_state) (void)hipFree(s->mt_state);
-            s->mt_state = nullptr;
-            SP_HIP(hipMalloc(&s->mt_state, waves * 2 * (size_t)spd::MT_GEN_WORDS * sizeof(uint64_t)));
-            s->mt_waves = waves;
-        }
-        SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
-        spd::Scene sc_run    = s->dev; // the resident scene with this render's options
-        sc_run.merge_queries = (p->flags & SP_RENDER_PER_LANE_QUERIES) ? 0 : 1;
-        spd::RenderArgs a{};
-        a.out          = d_out;
-        a.tile_ids     = d_ids;
-        a.num_tiles    = n_tiles;
-        a.tiles_x      = (s->dev.width + 7) / 8;
-        a.spp          = p->samples_per_pixel;
-        a.integrator   = integ;
-        a.tile_counter = s->tile_counter;
-        a.mt_state     = s->mt_state;
-        a.counters     = s->counters;
-        // BruteForce / Whitted recursion deeper than the in-register arrays: global level records
-        a.deep        = nullptr;
-        a.deep_stride = 0;
-        if ((integ == SP_INTEGRATOR_BRUTE_FORCE || integ == SP_INTEGRATOR_WHITTED) && s->dev.max_depth > MAX_RECURSION) {
-            const size_t lanes = waves * 64; // persistent waves of this launch (4 per block)
-            const size_t bytes = lanes * ((size_t)s->dev.max_depth + 1) * 5 * sizeof(float);
-            if (bytes > s->deep_cap) {
-                if (s->deep_buf) (void)hipFree(s->deep_buf);
-                s->deep_buf = nullptr;
-                s->deep_cap = 0;
-                SP_HIP(hipMalloc(&s->deep_buf, bytes));
-                s->deep_cap = bytes;
-            }
-            a.deep        = static_cast<float*>(s->deep_buf);
-            a.deep_stride = lanes;
-        }
-        SP_HIP(hipEventRecord(s->ev0, stream));
-        // SP_TILE_DIAG=<file>: per-tile timeline {t0, t1, wave, item} (u64, s_memrealtime 100 MHz) and,
-        // in a -DSP_MEGA_PROF build, shader clocks in trace / light sample / eval / occlusion
-        const char*         tdiag_path = std::getenv("SP_TILE_DIAG");
-        unsigned long long* tdiag      = nullptr;
-        if (tdiag_path) {
-            // the -DSP_WAVE_PROF / -DSP_TRAFFIC_DIAG builds add their totals into words 0..47
-            const size_t words = std::max<size_t>((size_t)n_tiles * 8, 48);
-            SP_HIP(hipMalloc(&tdiag, words * sizeof(unsigned long long)));
-            SP_HIP(hipMemsetAsync(tdiag, 0, words * sizeof(unsigned long long), stream));
-        }
-        a.tile_diag = tdiag;
-        a.order     = nullptr;
-        a.tile_time = nullptr;
-        // Tile order (sp_mega.hip tile_order): a one-sample probe pass times every tile, and the
-        // queue is ordered by cost class (slower than `hoist` x the mean first, the cheapest last),
-        // so the frame does not end with a few waves finishing expensive tiles alone.  Part of the
-        // render (timed with it); stream-ordered, no host wait.  Used where it measured faster
-        // (profiles/r03/ab_tile_order.txt, profiles/r04/tile_classes/): DirectLighting with many
-        // tiles per persistent wave and a probe that costs little of the frame (bunny 1080p @ 256
-        // spp, 7.9 tiles per wave; lucy; spheres 1024^2 @ 64 spp, 4 tiles per wave, loses 1 %);
-        // IterativeRRNEE, whose tile costs spread wider (paths end at any depth), from 4 tiles per
-        // wave and 16 spp (elf 1024^2 @ 16 spp +1.7 %; elf's 8-way shard +3 % with two classes, +5 % more with six).  DirectLighting and
-        // IterativeRRNEE have probe kernels (sp_probe_*.hip); the other integrators render in queue
-        // order.  sp_render_params.tile_order_factor > 0 forces it with that factor, < 0 turns it off.
-        const bool rrnee = integ == SP_INTEGRATOR_ITERATIVE_RRNEE;
-        // (DirectLighting with tail chunks: from 3 tiles per wave, tail_auto above)
-        float hoist = (n_tiles >= (rrnee ? 4 : 6) * (int64_t)waves && p->samples_per_pixel >= (rrnee ? 16u : 128u)) ? 2.0f : 0.0f;
-        if (tail_auto && 2 * n_tiles >= 5 * (int64_t)waves) hoist = 2.0f; // the tail chunks need the order
-        if (p->tile_order_factor != 0.0f) hoist = std::max(0.0f, p->tile_order_factor);
-        if (hoist > 0.0f && n_tiles > (int64_t)waves && spd::has_probe(integ)) {
-            if ((size_t)n_tiles > s->order_cap) {
-                if (s->d_tile_time) (void)hipFree(s->d_tile_time);
-                if (s->d_order) (void)hipFree(s->d_order);
-                s->d_tile_time = nullptr;
-                s->d_order     = nullptr;
-                s->order_cap   = 0;
-                SP_HIP(hipMalloc(&s->d_tile_time, (size_t)n_tiles * sizeof(float)));
-                SP_HIP(hipMalloc(&s->d_order, (size_t)n_tiles * sizeof(int32_t)));
-                s->order_cap = (size_t)n_tiles;
-            }
-            if (!s->probe_counters) SP_HIP(hipMalloc(&s->probe_counters, 8 * sizeof(unsigned long long)));
-            spd::RenderArgs pr = a;
-            pr.spp       = 1; // 2 or 4 probe samples measured no better (profiles/r03/ab_tile_order.txt, r04/tile_classes)
-            pr.tile_time = s->d_tile_time;
-            pr.counters  = s->probe_counters; // the probe's rays are not the render's
-            pr.tile_diag = nullptr;
-            // every 2nd slot timed where tail chunks follow and a wave takes 6 tiles or more (the others
-            // interpolated by the order kernel: bunny +0.25 %, lucy +0.2 %); at 4 tiles per wave the
-            // 2-way shard lost 2.5 % with it (spheres gained 0.6-0.8 %), and IterativeRRNEE, whose order
-            // has no tail chunks behind it, lost 2-4 % on elf's shard (profiles/r06/tail/ab_probe_step*.log)
-            pr.probe_step = (integ == SP_INTEGRATOR_DIRECT_LIGHTING && (tail_auto || p->tail_fraction > 0.0f) &&
-                             n_tiles >= 6 * (int64_t)waves) ? 2 : 1;
-            if (const char* v = std::getenv("SP_PROBE_STEP")) pr.probe_step = std::max(1, std::atoi(v));
-            SP_HIP(spd::launch_probe(sc_run, pr, integ, variant, blocks, lds_bytes, stream));
-            // cost estimates blended with their queue neighbours only where those sit at known
-            // image offsets: a whole frame, or a host list with a constant stride (the bench's list,
-            // a rank's interleaved shard; order_neighbours); any other list keeps each tile's own time
-            SP_HIP(spd::launch_tile_order(s->d_tile_time, n_tiles, hoist, order_neighbours(p, listed, n_tiles, a.tiles_x),
-                                          pr.probe_step, s->d_order, stream));
-            SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
-            a.order = s->d_order;
-            launches += 2;
-        }
-        // Tail chunks (sp_mega.hpp, sp_device.hpp TailArgs): the K = tail_frac x n_tiles most
-        // expensive tiles of the order are rendered as sample chunks at the end of the queue.
-        // DirectLighting at 3 or 4 waves per SIMD with the tile order; the preps take the draw counts
-        // from the camera hits, or with an image light replay Light::sample on the stream (TailArgs
-        // replay); SP_TAIL_FRAC (0: off) and SP_TAIL_CHUNKS override.
-        spd::ChunkArgs tail_sum{};
-        // counts replayed on the stream (an image light, or SP_CHUNK_REPLAY): the 4-wave kernel only
-        const bool tail_replay = !chunk_plan(s, 1, spp_u, 1).known_draws;
-        if (integ == SP_INTEGRATOR_DIRECT_LIGHTING && (variant == 4 || (variant == 3 && !tail_replay)) && a.order) {
-            // automatic: SP_TAIL_FRAC, or the environment's SP_TAIL_FRAC (A/B runs); the caller's
-            // tail_fraction when set (< 0: off)
-            // automatic: one tile per persistent wave's worth (waves / n_tiles: 0.126 for the 1-GPU
-            // 1080p frame, 0.25 for a 2-way shard, 0.38 for a 3-way one), within [SP_TAIL_FRAC, 0.4]
-            // -- measured best 0.12-0.16, 0.2-0.3 and 0.4 there (profiles/r06/tail/)
-            float tail_frac = std::min(0.4f, std::max(SP_TAIL_FRAC, (float)((double)waves / (double)n_tiles)));
-            tail_ch         = SP_TAIL_CHUNKS;
-            if (const char* v = std::getenv("SP_TAIL_FRAC")) tail_frac = (float)std::atof(v);
-            if (const char* v = std::getenv("SP_TAIL_CHUNKS")) tail_ch = std::atoi(v);
-            if (p->tail_fraction != 0.0f) tail_frac = p->tail_fraction;
-            const ChunkPlan tp = chunk_plan(s, 1, spp_u, std::max(1, tail_ch));
-            if (tail_frac > 0.0f) {
-                // ceil(frac x n), with frac the f32 caller value (0.05f x 5120 = 256.0000038: 256 tiles)
-                tail_k = std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)std::ceil((double)tail_frac * (double)n_tiles - 1e-3)));
-                const ChunkPlan cp    = chunk_plan(s, tail_k, spp_u, std::max(1, tail_ch));
-                const size_t    a_hdr = 256, a_rdy = ((size_t)tail_k * 4 + 255) / 256 * 256;
-                const size_t    need  = a_hdr + a_rdy + cp.b_hits + cp.b_L + cp.b_snap + cp.b_ctl;
-                // the sample chunks' budget (chunk_max_gb, never more than the device can still give):
-                // 20 GB for bunny's 4096 tail tiles (the store: 30 generations per pixel); a scene
-                // with many lights (a store bound of 34 draws per light and sample) renders without
-                // tail chunks rather than fail
-                const double tail_budget = std::min(ck_max_gb * 1e9, (double)free_b + (double)s->tail_cap);
-                if ((double)need > tail_budget) tail_k = 0;
-                if (tail_k > 0 && need > s->tail_cap) {
-                    if (s->tail_buf) (void)hipFree(s->tail_buf);
-                    s->tail_buf = nullptr;
-                    s->tail_cap = 0;
-                    if (hipMalloc(&s->tail_buf, need) != hipSuccess) {
-                        s->tail_buf = nullptr;
-                        (void)hipGetLastError();
-                        tail_k = 0;
-                    } else {
-                        s->tail_cap = need;
-                    }
-                }
-            }
-            if (tail_k > 0) {
-                const ChunkPlan cp    = chunk_plan(s, tail_k, spp_u, std::max(1, tail_ch));
-                const size_t    a_hdr = 256, a_rdy = ((size_t)tail_k * 4 + 255) / 256 * 256;
-                char*         base = static_cast<char*>(s->tail_buf);
-                spd::TailArgs ta{};
-                tail_ch        = (int)cp.chunks;
-                ta.n_prep      = tail_k;
-                ta.replay      = tail_replay ? 1 : 0; // an image light: the preps replay Light::sample
-                ta.n_items     = tail_k * cp.chunks;
-                ta.chunks      = (uint32_t)cp.chunks;
-                ta.chunk_len   = cp.len;
-                ta.gens_per_px = cp.gens;
-                ta.n_px        = (size_t)tail_k * 64;
-                ta.ready       = reinterpret_cast<uint32_t*>(base + a_hdr);
-                ta.hits        = reinterpret_cast<float4*>(base + a_hdr + a_rdy);
-                ta.L           = reinterpret_cast<float*>(base + a_hdr + a_rdy + cp.b_hits);
-                ta.gens        = reinterpret_cast<uint64_t*>(base + a_hdr + a_rdy + cp.b_hits + cp.b_L);
-                ta.snap_ctl    = reinterpret_cast<uint32_t*>(base + a_hdr + a_rdy + cp.b_hits + cp.b_L + cp.b_snap);
-                // the kernel reads TailArgs from device memory (stream-ordered behind the previous
-                // call's kernels, which may still read it)
-                SP_HIP(hipMemcpyAsync(base, &ta, sizeof(ta), hipMemcpyHostToDevice, stream));
-                SP_HIP(hipMemsetAsync(ta.ready, 0, (size_t)tail_k * 4, stream));
-                a.tail_prep  = ta.n_prep;
-                a.tail_items = ta.n_items;
-                a.tail       = reinterpret_cast<const spd::TailArgs*>(base);
-                tail_sum.tile_ids  = d_ids;
-                tail_sum.num_tiles = tail_k;
-                tail_sum.tiles_x   = a.tiles_x;
-                tail_sum.spp       = spp_u;
-                tail_sum.n_px      = ta.n_px;
-                tail_sum.L         = ta.L;
-                tail_sum.out       = d_out;
-                tail_sum.slot_map  = s->d_order; // chunk slot k is queue item k: tile slot order[k]
-            }
-        }
-        if (timing) {
-            if (!s->ev_render) SP_HIP(hipEventCreate(&s->ev_render));
-            SP_HIP(hipEventRecord(s->ev_render, stream));
-        }
-        if (tail_k > 0) {
-            const int     t_var    = tail_replay ? -variant : variant; // -4: the replaying tail kernel
-            const int     t_per_cu = spd::tail_blocks_per_cu(t_var, lds_bytes);
-            const int64_t t_need   = (n_tiles + a.tail_items + 3) / 4;
-            const int     t_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)s->n_cu * t_per_cu, t_need));
-            SP_HIP(spd::launch_tail(sc_run, a, t_var, t_blocks, lds_bytes, stream));
-            SP_HIP(spd::chunk_sum(sc_run, tail_sum, stream));
-            launches += 1;
-        } else {
-            SP_HIP(spd::launch_render(sc_run, a, integ, variant, blocks, lds_bytes, stream));
-        }
-        if (tdiag) { // diagnostic: waits for the render
-            SP_HIP(hipStreamSynchronize(stream));
-            std::vector<unsigned long long> rec((size_t)n_tiles * 8);
-            SP_HIP(hipMemcpy(rec.data(), tdiag, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            (void)hipFree(tdiag);
-            if (FILE* f = std::fopen(tdiag_path, "wb")) {
-                std::fwrite(rec.data(), sizeof(unsigned long long), rec.size(), f);
+        w.pb = 0;
+        w.pe = w.n;
+        SP_HIP(spd::wave_render(s->dev, w, c.d_out + (size_t)t0 * 64 * 3, per_cu, r.n_cu, c.stream,
+                                c.timing ? stage_ev.data() : nullptr, r.aux_stream.h, n_parts - 1, r.ev_fork, r.ev_join.h,
+                                r.ev_shade.h, &c.parts_used));
+        c.launches += 3 + 4 * (int)w.spp;
+        if (w.diag) {
+            std::vector<unsigned long long> h(diag_n);
+            SP_HIP(hipStreamSynchronize(c.stream));
+            SP_HIP(hipMemcpy(h.data(), diag.ptr, diag_n * 8, hipMemcpyDeviceToHost));
+            if (FILE* f = std::fopen(c.hooks.wave_diag, "wb")) {
+                std::fwrite(h.data(), 8, diag_n, f);
                 std::fclose(f);
             }
+            diag.reset();
+            w.diag = nullptr;
         }
-        launches += 1;
+        if (c.timing) {
+            SP_HIP(hipEventSynchronize(stage_ev[n_ev - 1]));
+            auto el = [&](size_t a, size_t b) {
+                float ms = 0.0f;
+                (void)hipEventElapsedTime(&ms, stage_ev[a], stage_ev[b]);
+                return ms;
+            };
+            c.stage[0] += el(0, 1) + el(n_ev - 2, n_ev - 1);
+            for (uint32_t i = 0; i < w.spp; ++i) {
+                const size_t b = 1 + 3 * (size_t)i;
+                c.stage[1] += el(b, b + 1);
+                c.stage[2] += el(b + 1, b + 2);
+                c.stage[3] += el(b + 2, b + 3);
+            }
+        }
     }
-    SP_HIP(hipEventRecord(s->ev1, stream));
-    SP_HIP(hipEventRecord(s->ev_done, stream));
-    s->done_rec = true;
+    return SP_OK;
+}
+
+// sp_chunk.hip: camera rays for all (pixel, sample) at once, a per-pixel replay of the stream
+// positions into the generator store, then every (tile, chunk) shaded in parallel, and the
+// in-order sum (buffers: splan::chunk_plan, reserved by plan_call)
+static int run_chunks(RenderCall& c)
+{
+    sp_scene*        s  = c.s;
+    RenderScratch&   r  = s->scratch;
+    const ChunkPlan& cp = c.plan.cp;
+    const int64_t    n_tiles = c.tiles.n;
+    const uint32_t   spp_u   = c.p->samples_per_pixel;
+    const size_t lds_bytes = shading_lds(s->dev);
+    if (lds_bytes > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    const size_t n_px   = (size_t)n_tiles * 64;
+    SP_HIP(r.ck_ctr.reserve(2 * sizeof(int32_t)));
+    const int per_cu = spd::chunk_blocks_per_cu(lds_bytes);
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)r.n_cu * per_cu, (n_tiles * cp.chunks + 3) / 4));
+    char*          base = r.ck_buf.as<char>();
+    spd::ChunkArgs a{};
+    a.tile_ids    = c.d_ids;
+    a.num_tiles   = n_tiles;
+    a.tiles_x     = (s->dev.width + 7) / 8;
+    a.spp         = spp_u;
+    a.chunks      = (uint32_t)cp.chunks;
+    a.chunk_len   = cp.len;
+    a.n_px        = n_px;
+    a.hits        = reinterpret_cast<float4*>(base);
+    a.L           = reinterpret_cast<float*>(base + cp.b_hits);
+    a.gens        = reinterpret_cast<uint64_t*>(base + cp.b_hits + cp.b_L);
+    a.gens_per_px = cp.gens;
+    a.snap_ctl    = reinterpret_cast<uint32_t*>(base + cp.b_hits + cp.b_L + cp.b_snap);
+    a.draws       = cp.known_draws ? reinterpret_cast<uint16_t*>(base + cp.b_hits + cp.b_L + cp.b_snap + cp.b_ctl) : nullptr;
+    a.n_lights    = s->dev.n_lights;
+    a.counter     = r.ck_ctr.as<int32_t>();
+    a.counters    = r.counters.as<unsigned long long>();
+    a.out         = c.d_out;
+    // Fused form (known draw counts): ck_camera, then the counts and the shading in ONE persistent
+    // queue of the megakernel's tail kernel (sp_mega.hpp, RenderArgs::tail_front): each tile's
+    // prep (stream positions, generations into the store) runs P tiles ahead of its chunks, so the
+    // HBM-bound twists overlap the shading instead of running as a phase of their own (ck_count).
+    // Same store contents and chunk starts, same image.  SP_CK_FUSED=0: the four-kernel form.
+    bool fused = cp.known_draws && c.hooks.ck_fused;
+    SP_HIP(hipMemsetAsync(r.ck_ctr.ptr, 0, 2 * sizeof(int32_t), c.stream));
+    // the tail kernel's LDS (the megakernel's: RSQRTSS table + per-wave stacks) and occupancy
+    if (fused && lds_bytes + spd::kernel_static_lds(spd::mega_kernel(spd::MegaFamily::Render, SP_INTEGRATOR_DIRECT_LIGHTING, 4)) > 160 * 1024)
+        fused = false;
+    if (!fused) {
+        SP_HIP(hipEventRecord(r.ev0, c.stream));
+        SP_HIP(spd::chunk_render(s->dev, a, blocks, r.n_cu, c.stream));
+        c.launches = 4;
+        return SP_OK;
+    }
+    const size_t a_hdr = 256, a_rdy = ((size_t)n_tiles * 4 + 255) / 256 * 256;
+    SP_HIP(r.tail_buf.reserve(a_hdr + 2 * a_rdy));
+    char*         tb = r.tail_buf.as<char>();
+    spd::TailArgs ta{};
+    ta.n_prep      = n_tiles;
+    ta.n_items     = n_tiles * cp.chunks;
+    ta.chunks      = (uint32_t)cp.chunks;
+    ta.chunk_len   = cp.len;
+    ta.gens_per_px = cp.gens;
+    ta.n_px        = n_px;
+    ta.hits        = a.hits;
+    ta.L           = a.L;
+    ta.gens        = a.gens;
+    ta.snap_ctl    = a.snap_ctl;
+    ta.draws       = a.draws;
+    ta.ready       = reinterpret_cast<uint32_t*>(tb + a_hdr);
+    // the camera pass as the queue's first items (SP_CK_CAMFOLD; blocks of SP_CK_CAM_BLOCK
+    // samples per item) instead of the ck_camera kernel before it
+    const bool cam_fold = c.hooks.ck_camfold;
+    if (cam_fold) {
+        ta.cam_block = c.hooks.ck_cam_block;
+        ta.n_cam     = n_tiles * (int64_t)((spp_u + ta.cam_block - 1) / ta.cam_block);
+        ta.cam_done  = reinterpret_cast<uint32_t*>(tb + a_hdr + a_rdy);
+        ta.draws_out = a.draws;
+    }
+    SP_HIP(hipMemcpyAsync(tb, &ta, sizeof(ta), hipMemcpyHostToDevice, c.stream));
+    SP_HIP(hipMemsetAsync(ta.ready, 0, 2 * a_rdy, c.stream));
+    spd::RenderArgs ra{};
+    ra.out          = c.d_out;
+    ra.tile_ids     = c.d_ids;
+    ra.num_tiles    = n_tiles;
+    ra.tiles_x      = a.tiles_x;
+    ra.spp          = spp_u;
+    ra.integrator   = c.integ;
+    ra.tile_counter = r.ck_ctr.as<int32_t>();
+    ra.counters     = r.counters.as<unsigned long long>();
+    ra.tail_prep    = ta.n_prep;
+    ra.tail_items   = ta.n_items;
+    const int     t_per_cu = spd::kernel_blocks_per_cu(spd::tail_kernel(0), lds_bytes); // 0: sp_fused_kernel
+    const int64_t t_waves  = (int64_t)r.n_cu * t_per_cu * 4;
+    // P: the preps ahead of the first chunks; the rest are dealt one per tile's chunks
+    ra.tail_front = std::max<int64_t>(1, t_waves / c.hooks.ck_front_div);
+    ra.tail_cam   = ta.n_cam;
+    ra.tail       = reinterpret_cast<const spd::TailArgs*>(tb);
+    const int t_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)r.n_cu * t_per_cu, (n_tiles * (cp.chunks + 1) + 3) / 4));
+    SP_HIP(hipEventRecord(r.ev0, c.stream));
+    if (!cam_fold) SP_HIP(spd::chunk_camera(s->dev, a, r.n_cu, c.stream));
+    SP_HIP(spd::launch_tail(s->dev, ra, 0, t_blocks, lds_bytes, c.stream));
+    SP_HIP(spd::chunk_sum(s->dev, a, c.stream));
+    c.launches = cam_fold ? 2 : 3;
+    return SP_OK;
+}
+
+// Tail chunks (sp_mega.hpp, sp_device.hpp TailArgs): the K = tail_frac x n_tiles most expensive
+// tiles of the order are rendered as sample chunks at the end of the queue.  DirectLighting at 3
+// or 4 waves per SIMD with the tile order; the preps take the draw counts from the camera hits, or
+// with an image light replay Light::sample on the stream (TailArgs replay); SP_TAIL_FRAC (0: off)
+// and SP_TAIL_CHUNKS override.  Sets c.tail_k / c.tail_ch, m.a's tail fields and tail_sum's
+// arguments; c.tail_k == 0: no tail chunks in this call.
+static int plan_tail_chunks(RenderCall& c, MegaSetup& m, bool tail_replay, spd::ChunkArgs& tail_sum)
+{
+    sp_scene*      s = c.s;
+    RenderScratch& r = s->scratch;
+    const int64_t  n_tiles = c.tiles.n;
+    const uint32_t spp_u   = c.p->samples_per_pixel;
+    // automatic: one tile per persistent wave's worth (waves / n_tiles: 0.126 for the 1-GPU
+    // 1080p frame, 0.25 for a 2-way shard, 0.38 for a 3-way one), within [SP_TAIL_FRAC, 0.4]
+    // -- measured best 0.12-0.16, 0.2-0.3 and 0.4 there (profiles/r06/tail/); the environment's
+    // SP_TAIL_FRAC instead (A/B runs); the caller's tail_fraction when set (< 0: off)
+    float tail_frac = std::min(0.4f, std::max(SP_TAIL_FRAC, (float)((double)m.waves / (double)n_tiles)));
+    if (c.hooks.tail_frac_set) tail_frac = c.hooks.tail_frac;
+    if (c.p->tail_fraction != 0.0f) tail_frac = c.p->tail_fraction;
+    c.tail_ch = c.hooks.tail_chunks;
+    if (!(tail_frac > 0.0f)) return SP_OK;
+    // ceil(frac x n), with frac the f32 caller value (0.05f x 5120 = 256.0000038: 256 tiles)
+    const int64_t   k     = std::min<int64_t>(n_tiles, std::max<int64_t>(1, (int64_t)std::ceil((double)tail_frac * (double)n_tiles - 1e-3)));
+    const ChunkPlan cp    = splan::chunk_plan(k, spp_u, std::max(1, c.tail_ch), s->dev.n_lights, c.image_light, c.hooks);
+    const size_t    a_hdr = 256, a_rdy = ((size_t)k * 4 + 255) / 256 * 256;
+    const size_t    need  = a_hdr + a_rdy + cp.b_hits + cp.b_L + cp.b_snap + cp.b_ctl;
+    // the sample chunks' budget (chunk_max_gb, never more than the device can still give):
+    // 20 GB for bunny's 4096 tail tiles (the store: 30 generations per pixel); a scene
+    // with many lights (a store bound of 34 draws per light and sample) renders without
+    // tail chunks rather than fail -- as it does when the allocation itself fails
+    const double tail_budget = std::min(c.ck_max_gb * 1e9, (double)c.free_b + (double)r.tail_buf.cap);
+    if ((double)need > tail_budget || r.tail_buf.reserve(need) != hipSuccess) return SP_OK;
+    char*         base = r.tail_buf.as<char>();
+    spd::TailArgs ta{};
+    c.tail_k       = k;
+    c.tail_ch      = (int)cp.chunks;
+    ta.n_prep      = k;
+    ta.replay      = tail_replay ? 1 : 0; // an image light: the preps replay Light::sample
+    ta.n_items     = k * cp.chunks;
+    ta.chunks      = (uint32_t)cp.chunks;
+    ta.chunk_len   = cp.len;
+    ta.gens_per_px = cp.gens;
+    ta.n_px        = (size_t)k * 64;
+    ta.ready       = reinterpret_cast<uint32_t*>(base + a_hdr);
+    ta.hits        = reinterpret_cast<float4*>(base + a_hdr + a_rdy);
+    ta.L           = reinterpret_cast<float*>(base + a_hdr + a_rdy + cp.b_hits);
+    ta.gens        = reinterpret_cast<uint64_t*>(base + a_hdr + a_rdy + cp.b_hits + cp.b_L);
+    ta.snap_ctl    = reinterpret_cast<uint32_t*>(base + a_hdr + a_rdy + cp.b_hits + cp.b_L + cp.b_snap);
+    // the kernel reads TailArgs from device memory (stream-ordered behind the previous
+    // call's kernels, which may still read it)
+    SP_HIP(hipMemcpyAsync(base, &ta, sizeof(ta), hipMemcpyHostToDevice, c.stream));
+    SP_HIP(hipMemsetAsync(ta.ready, 0, (size_t)k * 4, c.stream));
+    m.a.tail_prep  = ta.n_prep;
+    m.a.tail_items = ta.n_items;
+    m.a.tail       = reinterpret_cast<const spd::TailArgs*>(base);
+    tail_sum.tile_ids  = c.d_ids;
+    tail_sum.num_tiles = k;
+    tail_sum.tiles_x   = m.a.tiles_x;
+    tail_sum.spp       = spp_u;
+    tail_sum.n_px      = ta.n_px;
+    tail_sum.L         = ta.L;
+    tail_sum.out       = c.d_out;
+    tail_sum.slot_map  = m.a.order; // chunk slot k is queue item k: tile slot order[k]
+    return SP_OK;
+}
+
+static int run_megakernel(RenderCall& c)
+{
+    sp_scene*               s = c.s;
+    RenderScratch&          r = s->scratch;
+    const sp_render_params* p = c.p;
+    const int64_t           n_tiles = c.tiles.n;
+    MegaSetup m;
+    if (int rc = mega_setup(s, spd::MegaFamily::Render, c.integ, p->waves_per_simd, c.d_ids, n_tiles, m)) return rc;
+    SP_HIP(hipMemsetAsync(r.tile_counter.ptr, 0, sizeof(int32_t), c.stream));
+    m.sc_run.merge_queries = (p->flags & SP_RENDER_PER_LANE_QUERIES) ? 0 : 1;
+    m.a.out = c.d_out;
+    m.a.spp = p->samples_per_pixel;
+    SP_HIP(hipEventRecord(r.ev0, c.stream));
+    // SP_TILE_DIAG=<file>: per-tile timeline {t0, t1, wave, item} (u64, s_memrealtime 100 MHz) and,
+    // in a -DSP_MEGA_PROF build, shader clocks in trace / light sample / eval / occlusion
+    DeviceScratch tdiag;
+    if (c.hooks.tile_diag) {
+        // the -DSP_WAVE_PROF / -DSP_TRAFFIC_DIAG builds add their totals into words 0..47
+        const size_t words = std::max<size_t>((size_t)n_tiles * 8, 48);
+        SP_HIP(tdiag.reserve(words * sizeof(unsigned long long)));
+        SP_HIP(hipMemsetAsync(tdiag.ptr, 0, words * sizeof(unsigned long long), c.stream));
+    }
+    m.a.tile_diag = tdiag.as<unsigned long long>();
+    // Tile order (order_tiles): the queue ordered by cost class (slower than `hoist` x the mean
+    // first, the cheapest last), so the frame does not end with a few waves finishing expensive
+    // tiles alone.  Used where it measured faster
+    // (profiles/r03/ab_tile_order.txt, profiles/r04/tile_classes/): DirectLighting with many
+    // tiles per persistent wave and a probe that costs little of the frame (bunny 1080p @ 256
+    // spp, 7.9 tiles per wave; lucy; spheres 1024^2 @ 64 spp, 4 tiles per wave, loses 1 %);
+    // IterativeRRNEE, whose tile costs spread wider (paths end at any depth), from 4 tiles per
+    // wave and 16 spp (elf 1024^2 @ 16 spp +1.7 %; elf's 8-way shard +3 % with two classes, +5 % more with six).  DirectLighting and
+    // IterativeRRNEE have probe kernels (sp_probe_*.hip); the other integrators render in queue
+    // order.  sp_render_params.tile_order_factor > 0 forces it with that factor, < 0 turns it off.
+    const bool    rrnee     = c.integ == SP_INTEGRATOR_ITERATIVE_RRNEE;
+    const bool    tail_auto = c.plan.tail_auto;
+    const int64_t waves     = (int64_t)m.waves;
+    // (DirectLighting with tail chunks: from 3 tiles per wave, splan::tail_auto)
+    float hoist = (n_tiles >= (rrnee ? 4 : 6) * waves && p->samples_per_pixel >= (rrnee ? 16u : 128u)) ? 2.0f : 0.0f;
+    if (tail_auto && 2 * n_tiles >= 5 * waves) hoist = 2.0f; // the tail chunks need the order
+    if (p->tile_order_factor != 0.0f) hoist = std::max(0.0f, p->tile_order_factor);
+    if (hoist > 0.0f && n_tiles > waves && spd::has_probe(c.integ)) {
+        SP_HIP(r.d_tile_time.reserve((size_t)n_tiles * sizeof(float))); // the pair grows together: one size
+        SP_HIP(r.d_order.reserve((size_t)n_tiles * sizeof(int32_t)));
+        // every 2nd slot timed where tail chunks follow and a wave takes 6 tiles or more (the others
+        // interpolated by the order kernel: bunny +0.25 %, lucy +0.2 %); at 4 tiles per wave the
+        // 2-way shard lost 2.5 % with it (spheres gained 0.6-0.8 %), and IterativeRRNEE, whose order
+        // has no tail chunks behind it, lost 2-4 % on elf's shard (profiles/r06/tail/ab_probe_step*.log)
+        int probe_step = (c.integ == SP_INTEGRATOR_DIRECT_LIGHTING && (tail_auto || p->tail_fraction > 0.0f) && n_tiles >= 6 * waves) ? 2 : 1;
+        if (c.hooks.probe_step) probe_step = c.hooks.probe_step;
+        // cost estimates blended with their queue neighbours only where those sit at known
+        // image offsets: a whole frame, or a host list with a constant stride (the bench's list,
+        // a rank's interleaved shard; order_neighbours); any other list keeps each tile's own time
+        const int neighbours = splan::order_neighbours(p->tile_ids, c.tiles.listed, n_tiles, m.a.tiles_x);
+        if (int rc = order_tiles(s, m, c.d_out, r.d_tile_time.as<float>(), r.d_order.as<int32_t>(), hoist, probe_step, neighbours, c.stream))
+            return rc;
+        m.a.order = r.d_order.as<int32_t>();
+        c.launches += 2;
+    }
+    spd::ChunkArgs tail_sum{};
+    // counts replayed on the stream (an image light, or SP_CHUNK_REPLAY): the 4-wave kernel only
+    const bool tail_replay = !splan::chunk_plan(1, p->samples_per_pixel, 1, s->dev.n_lights, c.image_light, c.hooks).known_draws;
+    if (c.integ == SP_INTEGRATOR_DIRECT_LIGHTING && (m.variant == 4 || (m.variant == 3 && !tail_replay)) && m.a.order)
+        if (int rc = plan_tail_chunks(c, m, tail_replay, tail_sum)) return rc;
+    if (c.timing) {
+        if (!r.ev_render) SP_HIP(hipEventCreate(&r.ev_render[0]));
+        SP_HIP(hipEventRecord(r.ev_render, c.stream));
+    }
+    if (c.tail_k > 0) {
+        const int     t_var    = tail_replay ? -m.variant : m.variant; // -4: the replaying tail kernel
+        const int     t_per_cu = spd::kernel_blocks_per_cu(spd::tail_kernel(t_var), m.lds_bytes);
+        const int64_t t_need   = (n_tiles + m.a.tail_items + 3) / 4;
+        const int     t_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)r.n_cu * t_per_cu, t_need));
+        SP_HIP(spd::launch_tail(m.sc_run, m.a, t_var, t_blocks, m.lds_bytes, c.stream));
+        SP_HIP(spd::chunk_sum(m.sc_run, tail_sum, c.stream));
+        c.launches += 1;
+    } else {
+        SP_HIP(spd::launch_mega(m.family, m.sc_run, m.a, nullptr, nullptr, m.integ, m.variant, m.blocks, m.lds_bytes, c.stream));
+    }
+    if (tdiag.ptr) { // diagnostic: waits for the render
+        SP_HIP(hipStreamSynchronize(c.stream));
+        std::vector<unsigned long long> rec((size_t)n_tiles * 8);
+        SP_HIP(hipMemcpy(rec.data(), tdiag.ptr, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (FILE* f = std::fopen(c.hooks.tile_diag, "wb")) {
+            std::fwrite(rec.data(), sizeof(unsigned long long), rec.size(), f);
+            std::fclose(f);
+        }
+    }
+    c.launches += 1;
+    return SP_OK;
+}
+
+// The sample chunks count camera rays and samples on the host: one per inside pixel and sample
+static int chunk_stats(const RenderCall& c, const unsigned long long (&ctr)[8], sp_render_stats* stats)
+{
+    const sp_scene*      s = c.s;
+    std::vector<int32_t> ids;
+    if (c.tiles.listed) {
+        ids.resize((size_t)c.tiles.n);
+        if (c.p->tile_ids) std::memcpy(ids.data(), c.p->tile_ids, ids.size() * sizeof(int32_t));
+        else SP_HIP(hipMemcpy(ids.data(), c.p->d_tile_ids, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    int64_t       inside = 0;
+    const int32_t tw     = (s->dev.width + 7) / 8;
+    for (int64_t sl = 0; sl < c.tiles.n; ++sl) {
+        const int64_t t = c.tiles.listed ? ids[(size_t)sl] : sl;
+        if (t < 0 || t >= c.tiles.total) continue;
+        const int64_t x0 = (t % tw) * 8, y0 = (t / tw) * 8;
+        inside += std::min<int64_t>(8, s->dev.width - x0) * std::min<int64_t>(8, s->dev.height - y0);
+    }
+    stats->samples = (unsigned long long)inside * c.p->samples_per_pixel;
+    stats->rays    = (s->dev.max_depth > 0 ? stats->samples : 0ull) + ctr[1];
+    return SP_OK;
+}
+
+static int render_tiles_impl(sp_scene* s, const sp_render_params* p, float* d_out, sp_render_stats* stats)
+{
+    if (int rc = validate_render(s, p, d_out)) return rc;
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch& r = s->scratch;
+    RenderCall     c{ s, p, d_out, static_cast<hipStream_t>(p->stream), RenderHooks::from_env() };
+    if (int rc = resolve_integrator(s, p->integrator, p->waves_per_simd, c.integ)) return rc;
+    c.tiles = tile_list(s, p->tile_ids, p->d_tile_ids, p->num_tiles);
+    if (int rc = check_tile_list(c.tiles, p->tile_ids)) return rc;
+    c.d_ids  = p->d_tile_ids;
+    c.timing = (p->flags & SP_RENDER_STAGE_TIMING) != 0;
+    if (stats) *stats = sp_render_stats{};
+    if (c.tiles.n == 0) return SP_OK;
+    // the previous call on this scene may have used another stream: its work on the shared
+    // scratch comes first (sp_scene::mu)
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(c.stream, r.ev_done, 0));
+    if (p->tile_ids)
+        if (int rc = stage_tile_list(c)) return rc;
+    if (int rc = device_cus(s)) return rc;
+    if (int rc = plan_call(c)) return rc;
+    SP_HIP(hipMemsetAsync(r.counters.ptr, 0, 8 * sizeof(unsigned long long), c.stream));
+    const int pipeline = c.plan.pipeline;
+    if (int rc = pipeline == SP_PIPELINE_WAVEFRONT       ? run_wavefront(c)
+                 : pipeline == SP_PIPELINE_SAMPLE_CHUNKS ? run_chunks(c)
+                                                         : run_megakernel(c))
+        return rc;
+    if (int rc = end_call(s, c.stream)) return rc;
     // stream order: without stats nothing waits -- the render is only enqueued
-    if (stats) {
-        SP_HIP(hipEventSynchronize(s->ev1));
-        unsigned long long c[8];
-        SP_HIP(hipMemcpy(c, s->counters, sizeof(c), hipMemcpyDeviceToHost));
-        float ms = 0.0f;
-        SP_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        if (pipeline == SP_PIPELINE_SAMPLE_CHUNKS) {
-            // camera rays and samples: one per inside pixel and sample (counted here, not on device)
-            std::vector<int32_t> ids;
-            if (listed) {
-                ids.resize((size_t)n_tiles);
-                if (p->tile_ids) std::memcpy(ids.data(), p->tile_ids, ids.size() * sizeof(int32_t));
-                else SP_HIP(hipMemcpy(ids.data(), p->d_tile_ids, ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            }
-            int64_t       inside = 0;
-            const int32_t tw     = (s->dev.width + 7) / 8;
-            for (int64_t sl = 0; sl < n_tiles; ++sl) {
-                const int64_t t = listed ? ids[(size_t)sl] : sl;
-                if (t < 0 || t >= total) continue;
-                const int64_t x0 = (t % tw) * 8, y0 = (t / tw) * 8;
-                inside += std::min<int64_t>(8, s->dev.width - x0) * std::min<int64_t>(8, s->dev.height - y0);
-            }
-            c[0] = (s->dev.max_depth > 0 ? (unsigned long long)inside * spp_u : 0ull) + c[1];
-            c[2] = (unsigned long long)inside * spp_u;
-        }
-        stats->rays        = c[0];
-        stats->shadow_rays = c[1];
-        stats->samples     = c[2];
-        stats->rng_draws   = c[3];
-        stats->kernel_ms   = ms;
-        stats->pipeline    = pipeline;
-        stats->launches    = launches;
-        stats->primary_hits = c[4];
-        stats->parts        = parts_used;
-        stats->stack_depth  = s->dev.stack_depth;
-        stats->tail_tiles   = (int32_t)tail_k;
-        stats->tail_chunks  = tail_k > 0 ? tail_ch : 0;
-        if (pipeline == SP_PIPELINE_MEGAKERNEL && timing) { // [0] the render kernel, [1] probe + tile order
-            float r = ms;
-            if (s->ev_render) SP_HIP(hipEventElapsedTime(&r, s->ev_render, s->ev1));
-            stage[0] = r;
-            stage[1] = ms - r;
-        }
-        for (int k = 0; k < 4; ++k) stats->stage_ms[k] = stage[k];
+    if (!stats) return SP_OK;
+    unsigned long long ctr[8];
+    if (int rc = read_stats(s, pipeline, c.launches, stats, ctr)) return rc;
+    if (pipeline == SP_PIPELINE_SAMPLE_CHUNKS)
+        if (int rc = chunk_stats(c, ctr, stats)) return rc;
+    stats->primary_hits = ctr[4];
+    stats->parts        = c.parts_used;
+    stats->tail_tiles   = (int32_t)c.tail_k;
+    stats->tail_chunks  = c.tail_k > 0 ? c.tail_ch : 0;
+    if (pipeline == SP_PIPELINE_MEGAKERNEL && c.timing) { // [0] the render kernel, [1] probe + tile order
+        float render_ms = stats->kernel_ms;
+        if (r.ev_render) SP_HIP(hipEventElapsedTime(&render_ms, r.ev_render, r.ev1));
+        c.stage[0] = render_ms;
+        c.stage[1] = stats->kernel_ms - render_ms;
     }
+    for (int k = 0; k < 4; ++k) stats->stage_ms[k] = c.stage[k];
     return SP_OK;
 }
 
@@ -1744,19 +1761,8 @@ int sp_render_tiles_host(sp_scene* s, const sp_render_params* p, float* h_out, s
     if (!s || !p || !h_out) return fail(SP_ERR_ARG, "null argument");
     if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before rendering");
     SP_HIP(hipSetDevice(s->device));
-    int64_t total;
-    sp_tile_count(s->dev.width, s->dev.height, &total);
-    const int64_t n     = p->tile_ids ? p->num_tiles : total;
-    const size_t  bytes = (size_t)std::max<int64_t>(n, 1) * 64 * 3 * sizeof(float);
-    float*        d     = nullptr;
-    SP_HIP(hipMalloc(&d, bytes));
-    int rc = sp_render_tiles(s, p, d, stats);
-    if (rc == SP_OK) {
-        hipError_t e = hipMemcpy(h_out, d, (size_t)n * 64 * 3 * sizeof(float), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return rc;
+    const int64_t n = tile_list(s, p->tile_ids, p->d_tile_ids, p->num_tiles).n; // what the render writes
+    return render_to_host(n, h_out, [&](float* d) { return sp_render_tiles(s, p, d, stats); });
 }
 
 // ---- progressive renders (sp_progress) ---------------------------------------------------------
@@ -1791,26 +1797,13 @@ static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_pro
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_progress_params.reserved must be 0");
     if (p->tile_ids && p->d_tile_ids) return fail(SP_ERR_ARG, "give tile_ids (host) or d_tile_ids (device), not both");
     if (p->tile_order_factor != p->tile_order_factor) return fail(SP_ERR_ARG, "tile_order_factor is NaN");
-    const bool listed = p->tile_ids || p->d_tile_ids;
-    if (listed && p->num_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
     if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_progress_create");
-    int32_t integ = p->integrator;
-    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = s->host->integrator;
-    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = SP_INTEGRATOR_DIRECT_LIGHTING; // main.cpp:390
-    if (integ < SP_INTEGRATOR_MANDELBROT || integ > SP_INTEGRATOR_WHITTED) return fail(SP_ERR_ARG, "Unknown integrator type");
-    if (p->waves_per_simd != 0) {
-        const int  w  = p->waves_per_simd;
-        const bool ok = integ == SP_INTEGRATOR_DIRECT_LIGHTING ? (w >= 1 && w <= 4)
-                        : integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? (w >= 2 && w <= 4)
-                                                                  : false;
-        if (!ok) return fail(SP_ERR_ARG, "waves_per_simd: DirectLighting 1-4, IterativeRRNEE 2-4, else 0");
-    }
-    int64_t total;
-    sp_tile_count(s->dev.width, s->dev.height, &total);
-    const int64_t n_tiles = listed ? p->num_tiles : total;
-    if (p->tile_ids)
-        for (int64_t i = 0; i < n_tiles; ++i)
-            if (p->tile_ids[i] < 0 || p->tile_ids[i] >= total) return fail(SP_ERR_ARG, "tile id out of range");
+    int32_t integ = 0;
+    if (int rc = resolve_integrator(s, p->integrator, p->waves_per_simd, integ)) return rc;
+    const TileList tiles = tile_list(s, p->tile_ids, p->d_tile_ids, p->num_tiles);
+    if (int rc = check_tile_list(tiles, p->tile_ids)) return rc;
+    const bool    listed  = tiles.listed;
+    const int64_t n_tiles = tiles.n;
     SP_HIP(hipSetDevice(s->device));
     std::unique_ptr<sp_progress> g(new sp_progress());
     g->scene        = s;
@@ -1829,38 +1822,24 @@ static int progress_create_impl(sp_scene* s, const sp_progress_params* p, sp_pro
         if (p->tile_ids) std::memcpy(g->h_ids.data(), p->tile_ids, (size_t)n_tiles * sizeof(int32_t));
         else if (n_tiles > 0)
             SP_HIP(hipMemcpy(g->h_ids.data(), p->d_tile_ids, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost));
-        SP_HIP(hipMalloc(&g->d_ids, nt * sizeof(int32_t)));
+        SP_HIP(g->alloc(&g->d_ids, nt * sizeof(int32_t), false));
         SP_HIP(hipMemcpy(g->d_ids, g->h_ids.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice));
-        g->bytes += (int64_t)(nt * sizeof(int32_t));
     }
-    const size_t b_gen = nt * (size_t)spd::MT_GEN_WORDS * 8, b_pos = nt * 64 * 4, b_draws = nt * 64 * 8, b_sum = nt * 192 * 4;
-    SP_HIP(hipMalloc(&g->st.gen, b_gen));
-    SP_HIP(hipMalloc(&g->st.pos, b_pos));
-    SP_HIP(hipMalloc(&g->st.draws, b_draws));
-    SP_HIP(hipMalloc(&g->st.sum, b_sum));
-    SP_HIP(hipMemset(g->st.gen, 0, b_gen)); // pixels outside the image stay zero: they export as zero records
-    SP_HIP(hipMemset(g->st.pos, 0, b_pos));
-    SP_HIP(hipMemset(g->st.draws, 0, b_draws));
-    SP_HIP(hipMemset(g->st.sum, 0, b_sum));
-    g->bytes += (int64_t)(b_gen + b_pos + b_draws + b_sum);
+    // zeroed: pixels outside the image stay zero and export as zero records
+    SP_HIP(g->alloc(&g->st.gen, nt * (size_t)spd::MT_GEN_WORDS * 8));
+    SP_HIP(g->alloc(&g->st.pos, nt * 64 * 4));
+    SP_HIP(g->alloc(&g->st.draws, nt * 64 * 8));
+    SP_HIP(g->alloc(&g->st.sum, nt * 192 * 4));
     if (adaptive) {
         g->adaptive = true;
         const size_t b_px = nt * 64 * 4, b_tile = nt * 4;
-        SP_HIP(hipMalloc(&g->ad.mean, b_px));
-        SP_HIP(hipMalloc(&g->ad.m2, b_px));
-        SP_HIP(hipMalloc(&g->ad.done, b_tile));
-        SP_HIP(hipMalloc(&g->ad.err, b_tile));
-        SP_HIP(hipMalloc(&g->ad.flag, b_tile));
-        SP_HIP(hipMalloc(&g->ad.active, b_tile));
-        SP_HIP(hipMalloc(&g->ad.n_active, sizeof(int32_t)));
-        SP_HIP(hipMemset(g->ad.mean, 0, b_px)); // as the sums: zero outside the image
-        SP_HIP(hipMemset(g->ad.m2, 0, b_px));
-        SP_HIP(hipMemset(g->ad.done, 0, b_tile));
-        SP_HIP(hipMemset(g->ad.err, 0, b_tile));
-        SP_HIP(hipMemset(g->ad.flag, 0, b_tile));
-        SP_HIP(hipMemset(g->ad.active, 0, b_tile));
-        SP_HIP(hipMemset(g->ad.n_active, 0, sizeof(int32_t)));
-        g->bytes += (int64_t)(2 * b_px + 4 * b_tile + sizeof(int32_t));
+        SP_HIP(g->alloc(&g->ad.mean, b_px)); // as the sums: zero outside the image
+        SP_HIP(g->alloc(&g->ad.m2, b_px));
+        SP_HIP(g->alloc(&g->ad.done, b_tile));
+        SP_HIP(g->alloc(&g->ad.err, b_tile));
+        SP_HIP(g->alloc(&g->ad.flag, b_tile));
+        SP_HIP(g->alloc(&g->ad.active, b_tile));
+        SP_HIP(g->alloc(&g->ad.n_active, sizeof(int32_t)));
         g->h_inside.assign(nt, 0);
         int32_t x, y;
         for (int64_t sl = 0; sl < n_tiles; ++sl)
@@ -1901,7 +1880,7 @@ static int adaptive_fetch(sp_progress* g, std::vector<uint32_t>& done, std::vect
 {
     sp_scene* s = g->scene;
     SP_HIP(hipSetDevice(s->device));
-    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (int rc = wait_done(s)) return rc;
     done.assign((size_t)g->n_tiles, 0u);
     if (g->n_tiles == 0) return SP_OK;
     SP_HIP(hipMemcpy(done.data(), g->ad.done, done.size() * 4, hipMemcpyDeviceToHost));
@@ -1925,7 +1904,8 @@ struct AdaptRound {
 static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t stream, float* d_out, sp_render_stats* stats,
                                 const AdaptRound* rd = nullptr)
 {
-    sp_scene* s = g->scene;
+    sp_scene*      s = g->scene;
+    RenderScratch& r = s->scratch;
     if (int rc = progress_live(g)) return rc;
     if (more == 0) return fail(SP_ERR_ARG, "more_samples must be > 0");
     if ((!rd || rd->uniform) && (uint64_t)g->st.n0 + more > UINT32_MAX)
@@ -1942,157 +1922,83 @@ static int progress_render_impl(sp_progress* g, uint32_t more, hipStream_t strea
         return SP_OK;
     }
     // the scene's scratch (mt_state, counters) is shared with sp_render_tiles: same ordering
-    if (s->done_rec) SP_HIP(hipStreamWaitEvent(stream, s->ev_done, 0));
-    if (s->n_cu == 0) {
-        hipDeviceProp_t prop;
-        SP_HIP(hipGetDeviceProperties(&prop, s->device));
-        s->n_cu = prop.multiProcessorCount;
-    }
-    const int integ = g->integ;
-    // LDS, occupancy variant, persistent blocks: as the megakernel branch of render_tiles_impl
-    const int    rs_words  = spd::rsqrt_words(s->dev);
-    const size_t lds_bytes = (size_t)rs_words * 4 + (size_t)4 * s->dev.stack_words * 64 * 4;
-    size_t       lds_static = 0;
-    for (int v = 2; v <= 4; ++v)
-        lds_static = std::max(lds_static, rd ? spd::adapt_static_lds(integ, v) : spd::resume_static_lds(integ, v));
-    const size_t lds_all = lds_bytes + lds_static;
-    if (lds_all > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
-    const int lds_waves = (int)std::min<size_t>(8, (160 * 1024) / lds_all);
-    int       variant   = integ == SP_INTEGRATOR_ITERATIVE_RRNEE ? 3 : 4;
-    variant             = std::max(2, std::min(variant, lds_waves));
-    if (g->waves_req) variant = g->waves_req;
-    const int     per_cu = rd ? spd::adapt_blocks_per_cu(integ, variant, lds_bytes) : spd::resume_blocks_per_cu(integ, variant, lds_bytes);
-    const int     blocks = (int)std::max<int64_t>(1, std::min((int64_t)s->n_cu * per_cu, (n_tiles + 3) / 4));
-    const size_t  waves  = (size_t)blocks * 4;
-    if (waves > s->mt_waves) {
-        if (s->mt_state) (void)hipFree(s->mt_state);
-        s->mt_state = nullptr;
-        s->mt_waves = 0;
-        SP_HIP(hipMalloc(&s->mt_state, waves * 2 * (size_t)spd::MT_GEN_WORDS * sizeof(uint64_t)));
-        s->mt_waves = waves;
-    }
-    SP_HIP(hipMemsetAsync(s->counters, 0, 8 * sizeof(unsigned long long), stream));
-    SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
-    spd::Scene sc_run    = s->dev;
-    sc_run.merge_queries = 1;
-    spd::RenderArgs a{};
-    a.out          = d_out;
-    a.tile_ids     = g->d_ids;
-    a.num_tiles    = n_tiles;
-    a.tiles_x      = (s->dev.width + 7) / 8;
-    a.spp          = more; // (an adaptive call: at most; a tile's own count decides, AdaptArgs)
-    a.integrator   = integ;
-    a.tile_counter = s->tile_counter;
-    a.mt_state     = s->mt_state;
-    a.counters     = s->counters;
-    if ((integ == SP_INTEGRATOR_BRUTE_FORCE || integ == SP_INTEGRATOR_WHITTED) && s->dev.max_depth > MAX_RECURSION) {
-        const size_t lanes = waves * 64;
-        const size_t bytes = lanes * ((size_t)s->dev.max_depth + 1) * 5 * sizeof(float);
-        if (bytes > s->deep_cap) {
-            if (s->deep_buf) (void)hipFree(s->deep_buf);
-            s->deep_buf = nullptr;
-            s->deep_cap = 0;
-            SP_HIP(hipMalloc(&s->deep_buf, bytes));
-            s->deep_cap = bytes;
-        }
-        a.deep        = static_cast<float*>(s->deep_buf);
-        a.deep_stride = lanes;
-    }
-    SP_HIP(hipEventRecord(s->ev0, stream));
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    if (int rc = device_cus(s)) return rc;
+    MegaSetup m;
+    if (int rc = mega_setup(s, rd ? spd::MegaFamily::Adapt : spd::MegaFamily::Resume, g->integ, g->waves_req, g->d_ids, n_tiles, m))
+        return rc;
+    SP_HIP(hipMemsetAsync(r.counters.ptr, 0, 8 * sizeof(unsigned long long), stream));
+    SP_HIP(hipMemsetAsync(r.tile_counter.ptr, 0, sizeof(int32_t), stream));
+    m.sc_run.merge_queries = 1;
+    m.a.out = d_out;
+    m.a.spp = more; // (an adaptive call: at most; a tile's own count decides, AdaptArgs)
+    SP_HIP(hipEventRecord(r.ev0, stream));
     int launches = 1;
-    // Tile order (render_tiles_impl): the one-sample probe runs in the first call and its order is
+    // Tile order (run_megakernel): the one-sample probe runs in the first call and its order is
     // kept -- it only permutes the tiles.  Automatic from the same tiles per wave as a one-shot
     // render (whose samples threshold has no counterpart here: a call does not know the total).
     if (!g->order_tried) {
         g->order_tried = true;
-        const bool rrnee = integ == SP_INTEGRATOR_ITERATIVE_RRNEE;
-        float      hoist = n_tiles >= (rrnee ? 4 : 6) * (int64_t)waves ? 2.0f : 0.0f;
+        const bool rrnee = g->integ == SP_INTEGRATOR_ITERATIVE_RRNEE;
+        float      hoist = n_tiles >= (rrnee ? 4 : 6) * (int64_t)m.waves ? 2.0f : 0.0f;
         if (g->order_factor != 0.0f) hoist = std::max(0.0f, g->order_factor);
-        if (hoist > 0.0f && n_tiles > (int64_t)waves && spd::has_probe(integ)) {
-            SP_HIP(hipMalloc(&g->d_tile_time, (size_t)n_tiles * sizeof(float)));
-            SP_HIP(hipMalloc(&g->d_order, (size_t)n_tiles * sizeof(int32_t)));
-            g->bytes += (int64_t)n_tiles * 8;
-            if (!s->probe_counters) SP_HIP(hipMalloc(&s->probe_counters, 8 * sizeof(unsigned long long)));
-            spd::RenderArgs pr = a;
-            pr.out        = nullptr;
-            pr.spp        = 1;
-            pr.tile_time  = g->d_tile_time;
-            pr.counters   = s->probe_counters;
-            pr.probe_step = 1;
-            SP_HIP(spd::launch_probe(sc_run, pr, integ, variant, blocks, lds_bytes, stream));
-            sp_render_params np{};
-            np.tile_ids = g->listed ? g->h_ids.data() : nullptr;
-            SP_HIP(spd::launch_tile_order(g->d_tile_time, n_tiles, hoist, order_neighbours(&np, g->listed, n_tiles, a.tiles_x), 1,
-                                          g->d_order, stream));
-            SP_HIP(hipMemsetAsync(s->tile_counter, 0, sizeof(int32_t), stream));
+        if (hoist > 0.0f && n_tiles > (int64_t)m.waves && spd::has_probe(g->integ)) {
+            SP_HIP(g->alloc(&g->d_tile_time, (size_t)n_tiles * sizeof(float), false));
+            SP_HIP(g->alloc(&g->d_order, (size_t)n_tiles * sizeof(int32_t), false));
+            const int neighbours = splan::order_neighbours(g->listed ? g->h_ids.data() : nullptr, g->listed, n_tiles, m.a.tiles_x);
+            if (int rc = order_tiles(s, m, nullptr, g->d_tile_time, g->d_order, hoist, 1, neighbours, stream)) return rc;
             g->ordered = true;
             launches += 2;
         }
     }
-    a.order = g->ordered ? g->d_order : nullptr;
+    m.a.order = g->ordered ? g->d_order : nullptr;
+    spd::AdaptArgs ad = g->ad;
     if (rd) {
         // errors and the selection, the selected slots in the kept tile order, the render kernel on
         // that list (its length stays on the device), then the image of the tiles it left alone
         spd::SelectArgs sa{};
         sa.tile_ids    = g->d_ids;
         sa.num_tiles   = n_tiles;
-        sa.tiles_x     = a.tiles_x;
+        sa.tiles_x     = m.a.tiles_x;
         sa.width       = s->dev.width;
         sa.height      = s->dev.height;
         sa.threshold   = rd->threshold;
         sa.floor       = rd->floor;
         sa.min_samples = rd->min_samples;
         sa.max_samples = rd->max_samples;
-        spd::AdaptArgs ad = g->ad;
-        ad.step           = rd->step;
-        ad.cap            = rd->max_samples;
+        ad.step        = rd->step;
+        ad.cap         = rd->max_samples;
         SP_HIP(spd::launch_adapt_select(ad, sa, ad.err, ad.flag, stream));
-        SP_HIP(spd::launch_adapt_compact(ad, a.order, n_tiles, stream));
-        SP_HIP(spd::launch_adapt(sc_run, a, g->st, ad, integ, variant, blocks, lds_bytes, stream));
+        SP_HIP(spd::launch_adapt_compact(ad, m.a.order, n_tiles, stream));
         launches += 2;
-        if (d_out && !rd->uniform) {
-            SP_HIP(spd::launch_adapt_resolve(g->st, ad, true, n_tiles, d_out, stream));
-            launches += 1;
-        }
-    } else {
-        SP_HIP(spd::launch_resume(sc_run, a, g->st, integ, variant, blocks, lds_bytes, stream));
     }
-    SP_HIP(hipEventRecord(s->ev1, stream));
-    SP_HIP(hipEventRecord(s->ev_done, stream));
-    s->done_rec = true;
+    SP_HIP(spd::launch_mega(m.family, m.sc_run, m.a, &g->st, &ad, m.integ, m.variant, m.blocks, m.lds_bytes, stream));
+    if (rd && d_out && !rd->uniform) {
+        SP_HIP(spd::launch_adapt_resolve(g->st, ad, true, n_tiles, d_out, stream));
+        launches += 1;
+    }
+    if (int rc = end_call(s, stream)) return rc;
     g->st.n0 = n0_after;
     if (rd && rd->result) {
-        sp_adaptive_result&   r = *rd->result;
+        sp_adaptive_result&   res = *rd->result;
         std::vector<uint32_t> done;
         std::vector<float>    err;
         if (int rc = adaptive_fetch(g, done, &err)) return rc;
         int32_t n_act = 0;
         SP_HIP(hipMemcpy(&n_act, g->ad.n_active, sizeof(n_act), hipMemcpyDeviceToHost));
-        r.active_tiles = n_act;
-        r.min_done     = UINT32_MAX;
+        res.active_tiles = n_act;
+        res.min_done     = UINT32_MAX;
         for (int64_t i = 0; i < n_tiles; ++i) {
-            r.samples_total += (uint64_t)done[(size_t)i] * g->h_inside[(size_t)i];
-            r.min_done  = std::min(r.min_done, done[(size_t)i]);
-            r.max_done  = std::max(r.max_done, done[(size_t)i]);
-            r.max_error = std::max(r.max_error, err[(size_t)i]);
+            res.samples_total += (uint64_t)done[(size_t)i] * g->h_inside[(size_t)i];
+            res.min_done  = std::min(res.min_done, done[(size_t)i]);
+            res.max_done  = std::max(res.max_done, done[(size_t)i]);
+            res.max_error = std::max(res.max_error, err[(size_t)i]);
         }
-        g->st.n0 = r.max_done;
+        g->st.n0 = res.max_done;
     }
     if (stats) {
-        SP_HIP(hipEventSynchronize(s->ev1));
-        unsigned long long c[8];
-        SP_HIP(hipMemcpy(c, s->counters, sizeof(c), hipMemcpyDeviceToHost));
-        float ms = 0.0f;
-        SP_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        stats->rays        = c[0];
-        stats->shadow_rays = c[1];
-        stats->samples     = c[2];
-        stats->rng_draws   = c[3];
-        stats->kernel_ms   = ms;
-        stats->pipeline    = SP_PIPELINE_MEGAKERNEL;
-        stats->launches    = launches;
-        stats->parts       = 1;
-        stats->stack_depth = s->dev.stack_depth;
+        unsigned long long ctr[8];
+        if (int rc = read_stats(s, SP_PIPELINE_MEGAKERNEL, launches, stats, ctr)) return rc;
     }
     return SP_OK;
 }
@@ -2117,16 +2023,7 @@ int sp_progress_render_host(sp_progress* g, uint32_t more_samples, float* h_out,
     if (!g || !h_out) return fail(SP_ERR_ARG, "null argument");
     if (g->scene->device < 0) return fail(SP_ERR_STATE, "the scene is no longer uploaded");
     SP_HIP(hipSetDevice(g->scene->device));
-    const size_t bytes = (size_t)g->n_tiles * 64 * 3 * sizeof(float);
-    float*       d     = nullptr;
-    SP_HIP(hipMalloc(&d, std::max<size_t>(bytes, 4)));
-    int rc = sp_progress_render(g, more_samples, nullptr, d, stats);
-    if (rc == SP_OK && bytes) {
-        hipError_t e = hipMemcpy(h_out, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return rc;
+    return render_to_host(g->n_tiles, h_out, [&](float* d) { return sp_progress_render(g, more_samples, nullptr, d, stats); });
 }
 
 int sp_progress_samples(const sp_progress* g, uint32_t* out)
@@ -2165,7 +2062,7 @@ static int progress_export_impl(sp_progress* g, sp_pixel_state* h, int64_t capac
     *samples = g->st.n0;
     if (n_px == 0) return SP_OK;
     SP_HIP(hipSetDevice(s->device));
-    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (int rc = wait_done(s)) return rc;
     std::vector<uint32_t> tile_done; // an adaptive object: each tile has its own count
     if (g->adaptive) {
         if (int rc = adaptive_fetch(g, tile_done, nullptr)) return rc;
@@ -2235,7 +2132,7 @@ static int progress_import_impl(sp_progress* g, const sp_pixel_state* h, int64_t
         return SP_OK;
     }
     SP_HIP(hipSetDevice(s->device));
-    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (int rc = wait_done(s)) return rc;
     if (g->adaptive) { // every tile at `samples`, no statistics: sp_adaptive_import brings both
         const std::vector<uint32_t> all((size_t)g->n_tiles, samples);
         SP_HIP(hipMemcpy(g->ad.done, all.data(), all.size() * 4, hipMemcpyHostToDevice));
@@ -2321,16 +2218,7 @@ int sp_adaptive_round_host(sp_progress* g, const sp_adaptive_params* p, float* h
     if (!g || !p || !h_out) return fail(SP_ERR_ARG, "null argument");
     if (g->scene->device < 0) return fail(SP_ERR_STATE, "the scene is no longer uploaded");
     SP_HIP(hipSetDevice(g->scene->device));
-    const size_t bytes = (size_t)g->n_tiles * 64 * 3 * sizeof(float);
-    float*       d     = nullptr;
-    SP_HIP(hipMalloc(&d, std::max<size_t>(bytes, 4)));
-    int rc = sp_adaptive_round(g, p, nullptr, d, stats, result);
-    if (rc == SP_OK && bytes) {
-        hipError_t e = hipMemcpy(h_out, d, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(SP_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return rc;
+    return render_to_host(g->n_tiles, h_out, [&](float* d) { return sp_adaptive_round(g, p, nullptr, d, stats, result); });
 }
 
 int sp_adaptive_tile_samples(sp_progress* g, uint32_t* h_out, int64_t capacity)
@@ -2357,7 +2245,7 @@ static int adaptive_tile_errors_impl(sp_progress* g, float floor, float* h_out, 
     if (capacity < g->n_tiles) return fail(SP_ERR_ARG, "capacity below num_tiles");
     if (g->n_tiles == 0) return SP_OK;
     SP_HIP(hipSetDevice(s->device));
-    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (int rc = wait_done(s)) return rc;
     spd::SelectArgs sa{};
     sa.tile_ids  = g->d_ids;
     sa.num_tiles = g->n_tiles;
@@ -2418,7 +2306,7 @@ static int adaptive_import_impl(sp_progress* g, const sp_pixel_noise* h, int64_t
     if (tiles != g->n_tiles) return fail(SP_ERR_ARG, "tiles is not num_tiles");
     if (n_px == 0) return SP_OK;
     SP_HIP(hipSetDevice(s->device));
-    if (s->done_rec) SP_HIP(hipEventSynchronize(s->ev_done));
+    if (int rc = wait_done(s)) return rc;
     std::vector<float> mean((size_t)n_px, 0.0f), m2((size_t)n_px, 0.0f);
     int32_t            x, y;
     for (int64_t i = 0; i < n_px; ++i) {

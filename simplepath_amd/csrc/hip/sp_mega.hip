@@ -17,10 +17,25 @@ KernelFn select_kernel(int integ, int variant)
     }
 }
 
-hipError_t launch_render(const Scene& sc, const RenderArgs& args, int integ, int variant, int blocks, size_t lds_bytes,
-                         hipStream_t stream)
+const void* mega_kernel(MegaFamily family, int integ, int variant)
 {
-    hipLaunchKernelGGL(select_kernel(integ, variant), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds_bytes, stream, sc, args);
+    switch (family) {
+    case MegaFamily::Resume: return reinterpret_cast<const void*>(select_resume(integ, variant));
+    case MegaFamily::Adapt: return reinterpret_cast<const void*>(select_adapt(integ, variant));
+    default: return reinterpret_cast<const void*>(select_kernel(integ, variant));
+    }
+}
+
+hipError_t launch_mega(MegaFamily family, const Scene& sc, const RenderArgs& args, const ResumeArgs* res, const AdaptArgs* ad,
+                       int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream)
+{
+    const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
+    if ((family != MegaFamily::Render && !res) || (family == MegaFamily::Adapt && !ad)) return hipErrorInvalidValue;
+    switch (family) {
+    case MegaFamily::Resume: hipLaunchKernelGGL(select_resume(integ, variant), grid, block, lds_bytes, stream, sc, args, *res); break;
+    case MegaFamily::Adapt: hipLaunchKernelGGL(select_adapt(integ, variant), grid, block, lds_bytes, stream, sc, args, *res, *ad); break;
+    default: hipLaunchKernelGGL(select_kernel(integ, variant), grid, block, lds_bytes, stream, sc, args); break;
+    }
     return hipGetLastError();
 }
 
@@ -82,7 +97,7 @@ __device__ __forceinline__ int tile_class(float t, float thr)
 // tile below (> 0), -1 when only the +-1 queue entries are used, < -1 the column blend alone with
 // offset -tx - 1, 0 none (a caller's list in arbitrary order: the probe time alone); the +-1 entries
 // are the left / right tiles of a whole frame and k tiles apart in a stride-k list
-// (sp_capi.hip order_neighbours).
+// (sp_plan.hpp order_neighbours).
 // Measured against the row blend alone (round 4's form) and the probe time alone: lucy +0.9-1.5 %,
 // elf's 8-way shard +1.3 %, bunny level (profiles/r05/tile_order/).  SP_TILE_SMOOTH 0: probe time alone.
 __device__ __forceinline__ float tile_est(const float* t, int64_t i, int64_t n, int tx)
@@ -170,40 +185,29 @@ hipError_t launch_tile_order(float* tile_time, int64_t n_tiles, float factor, in
     return hipGetLastError();
 }
 
-// Static LDS of a render kernel (libm tables, the rho sink, IterativeRRNEE's served-estimate
-// rows): the 160 KB guard and the LDS occupancy cap count it beside the dynamic part.
-size_t render_static_lds(int integ, int variant)
+size_t kernel_static_lds(const void* kernel)
 {
     hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(select_kernel(integ, variant))) != hipSuccess) return 0;
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return 0;
     return fa.sharedSizeBytes;
 }
 
-// variant 0: the sample chunks' fused form (sp_fused_kernel), 3 / 4: the tail kernel at 3 / 4 waves,
-// -4: the tail kernel with an image light's replay (4 waves)
-static KernelFn tail_kernel(int variant)
-{
-    return variant == 0 ? fused_chunks() : tail_direct(variant < 0 ? -variant : variant, variant < 0);
-}
-hipError_t launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream)
-{
-    hipLaunchKernelGGL(tail_kernel(variant), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds_bytes, stream, sc, args);
-    return hipGetLastError();
-}
-int tail_blocks_per_cu(int variant, size_t lds_bytes)
+int kernel_blocks_per_cu(const void* kernel, size_t lds_bytes)
 {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tail_kernel(variant), 64 * WAVES_PER_BLOCK, lds_bytes) != hipSuccess) return 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * WAVES_PER_BLOCK, lds_bytes) != hipSuccess) return 1;
     return n > 0 ? n : 1;
 }
 
-int render_blocks_per_cu(int integ, int variant, size_t lds_bytes)
+static KernelFn select_tail(int variant)
 {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, select_kernel(integ, variant), 64 * WAVES_PER_BLOCK, lds_bytes) !=
-        hipSuccess)
-        return 1;
-    return n > 0 ? n : 1;
+    return variant == 0 ? fused_chunks() : tail_direct(variant < 0 ? -variant : variant, variant < 0);
+}
+const void* tail_kernel(int variant) { return reinterpret_cast<const void*>(select_tail(variant)); }
+hipError_t  launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(select_tail(variant), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds_bytes, stream, sc, args);
+    return hipGetLastError();
 }
 
 } // namespace spd

@@ -4,6 +4,7 @@
 // heavy translation units compile in parallel.
 #pragma once
 #include "sp_path.hpp"
+#include "sp_launch.hpp"
 
 namespace spd {
 inline namespace SPD_LAYOUT_NS {
@@ -633,21 +634,13 @@ ResumeFn   resume_direct(int variant);
 ResumeFn   resume_mandelbrot();
 ResumeFn   resume_rrnee(int waves);
 ResumeFn   resume_path(int integ); // BruteForce, its iterative forms, Whitted
-hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, int integ, int variant, int blocks,
-                         size_t lds_bytes, hipStream_t stream);
-int        resume_blocks_per_cu(int integ, int variant, size_t lds_bytes);
-size_t     resume_static_lds(int integ, int variant);
+ResumeFn   select_resume(int integ, int variant); // variant as select_kernel's (sp_mega.hip)
 // adaptive progress objects (sp_mega_adapt*.hip, the same split; sp_adaptive.hip: selection, list, resolve)
 using AdaptFn = void (*)(Scene, RenderArgs, ResumeArgs, AdaptArgs);
 AdaptFn    adapt_direct(int variant);
 AdaptFn    adapt_mandelbrot();
 AdaptFn    adapt_rrnee(int waves);
 AdaptFn    adapt_path(int integ);
-hipError_t launch_adapt(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, const AdaptArgs& ad, int integ,
-                        int variant, int blocks, size_t lds_bytes, hipStream_t stream);
-int        adapt_blocks_per_cu(int integ, int variant, size_t lds_bytes);
-size_t     adapt_static_lds(int integ, int variant);
-hipError_t launch_tile_order(float* tile_time, int64_t n_tiles, float factor, int tiles_x, int step, int32_t* order,
-                             hipStream_t stream);
+AdaptFn    select_adapt(int integ, int variant);
 
 } // namespace spd

@@ -1,5 +1,5 @@
 // sp_mega_adapt.hip -- rounds and uniform passes on adaptive progress objects (sp_adaptive_round,
-// sp_progress_render): the sp_adapt_kernel family's launch helpers, and its DirectLighting and
+// sp_progress_render): the sp_adapt_kernel family's kernel selection, and its DirectLighting and
 // Mandelbrot instantiations with the sampler options of their one-shot kernels (sp_mega_direct.hip),
 // as sp_mega_resume.hip does for sp_resume_kernel.  The other integrators' instantiations carry
 // their own options in sp_mega_adapt_rrnee.hip and sp_mega_adapt_path.hip.
@@ -25,7 +25,7 @@ AdaptFn adapt_direct(int variant)
 AdaptFn adapt_mandelbrot() { return sp_adapt_kernel<SP_INTEGRATOR_MANDELBROT, 2>; }
 
 // variant as select_kernel's (sp_mega.hip)
-static AdaptFn select_adapt(int integ, int variant)
+AdaptFn select_adapt(int integ, int variant)
 {
     switch (integ) {
     case SP_INTEGRATOR_BRUTE_FORCE:
@@ -36,29 +36,5 @@ static AdaptFn select_adapt(int integ, int variant)
     case SP_INTEGRATOR_MANDELBROT: return adapt_mandelbrot();
     default: return adapt_direct(variant);
     }
-}
-
-hipError_t launch_adapt(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, const AdaptArgs& ad, int integ,
-                        int variant, int blocks, size_t lds_bytes, hipStream_t stream)
-{
-    hipLaunchKernelGGL(select_adapt(integ, variant), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds_bytes, stream, sc, args, res,
-                       ad);
-    return hipGetLastError();
-}
-
-int adapt_blocks_per_cu(int integ, int variant, size_t lds_bytes)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, select_adapt(integ, variant), 64 * WAVES_PER_BLOCK, lds_bytes) !=
-        hipSuccess)
-        return 1;
-    return n > 0 ? n : 1;
-}
-
-size_t adapt_static_lds(int integ, int variant)
-{
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(select_adapt(integ, variant))) != hipSuccess) return 0;
-    return fa.sharedSizeBytes;
 }
 } // namespace spd

@@ -1,5 +1,5 @@
 // sp_mega_resume.hip -- progressive renders (sp_progress_render): the sp_resume_kernel family's
-// launch helpers, and its DirectLighting and Mandelbrot instantiations with the sampler options of
+// kernel selection, and its DirectLighting and Mandelbrot instantiations with the sampler options of
 // their one-shot kernels (sp_mega_direct.hip).  The other integrators' instantiations carry their
 // own options in sp_mega_resume_rrnee.hip and sp_mega_resume_path.hip.
 #define SP_RNG_PF 0
@@ -24,7 +24,7 @@ ResumeFn resume_direct(int variant)
 ResumeFn resume_mandelbrot() { return sp_resume_kernel<SP_INTEGRATOR_MANDELBROT, 2>; }
 
 // variant as select_kernel's (sp_mega.hip)
-static ResumeFn select_resume(int integ, int variant)
+ResumeFn select_resume(int integ, int variant)
 {
     switch (integ) {
     case SP_INTEGRATOR_BRUTE_FORCE:
@@ -35,28 +35,5 @@ static ResumeFn select_resume(int integ, int variant)
     case SP_INTEGRATOR_MANDELBROT: return resume_mandelbrot();
     default: return resume_direct(variant);
     }
-}
-
-hipError_t launch_resume(const Scene& sc, const RenderArgs& args, const ResumeArgs& res, int integ, int variant, int blocks,
-                         size_t lds_bytes, hipStream_t stream)
-{
-    hipLaunchKernelGGL(select_resume(integ, variant), dim3(blocks), dim3(64 * WAVES_PER_BLOCK), lds_bytes, stream, sc, args, res);
-    return hipGetLastError();
-}
-
-int resume_blocks_per_cu(int integ, int variant, size_t lds_bytes)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, select_resume(integ, variant), 64 * WAVES_PER_BLOCK, lds_bytes) !=
-        hipSuccess)
-        return 1;
-    return n > 0 ? n : 1;
-}
-
-size_t resume_static_lds(int integ, int variant)
-{
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(select_resume(integ, variant))) != hipSuccess) return 0;
-    return fa.sharedSizeBytes;
 }
 } // namespace spd

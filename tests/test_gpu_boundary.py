@@ -7,6 +7,7 @@
     image is computed, never the image;
   * argument validation (reserved fields, unknown flags, both tile lists, occupancy ranges).
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -67,6 +68,28 @@ def test_device_tile_list(scene_dir, pipeline):
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
     assert (st.rays, st.shadow_rays, st.samples, st.rng_draws) == (rst.rays, rst.shadow_rays, rst.samples, rst.rng_draws)
+
+
+def test_host_render_of_a_device_tile_list(scene_dir):
+    # sp_render_tiles_host with d_tile_ids renders and copies back num_tiles tiles (num_tiles * 64 * 3
+    # floats, as the header promises) -- not the frame's six
+    s = load(scene_dir, "bunny.sp", 24, 16, bvh=1)
+    assert sp.TileScheduler(24, 16).get_num_tiles() == 6
+    ids = np.array([4, 0, 3], dtype=np.int32)
+    d = torch.from_numpy(ids).cuda()
+    ref = torch.zeros((ids.size, 64, 3), dtype=torch.float32, device="cuda:0")
+    sp.render_tiles_device(s, "direct_lighting", 2, None, ref.data_ptr(), torch.cuda.current_stream().cuda_stream,
+                           d_tile_ids=d.data_ptr(), num_tiles=ids.size)
+    torch.cuda.synchronize()
+    p, _ = sp._params("direct_lighting", 2, None)
+    p.d_tile_ids = C.c_void_p(d.data_ptr())
+    p.num_tiles = ids.size
+    sentinel = np.float32(-12345.5)
+    h_out = np.full((6 + 1, 64, 3), sentinel, dtype=np.float32)
+    st = _abi.sp_render_stats()
+    _abi.check(sp.lib().sp_render_tiles_host(s.handle, C.byref(p), h_out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+    assert np.array_equal(h_out[:ids.size].view(np.uint32), ref.cpu().numpy().view(np.uint32))
+    assert np.all(h_out[ids.size:].view(np.uint32) == sentinel.view(np.uint32))
 
 
 @pytest.mark.parametrize("integrator,waves", [("direct_lighting", (1, 2, 3, 4)), ("iterative_rrnee", (2, 3, 4))])
@@ -167,7 +190,7 @@ def test_tile_order_probe_is_invisible(scene_dir, integrator):
 @pytest.mark.parametrize("integrator", ["direct_lighting", "iterative_rrnee"])
 def test_tile_order_on_strided_lists(scene_dir, integrator):
     # a host list in image order with a constant stride (a rank's interleaved shard) gets the
-    # neighbour-blended estimate (sp_capi.hip order_neighbours: the tile below when the stride
+    # neighbour-blended estimate (sp_plan.hpp order_neighbours: the tile below when the stride
     # divides tiles_x, else left / right only); the list as a whole frame (stride 1), a stride that
     # divides the 160 tiles per row (2, 4) and one that does not (3) all render the frame's rows
     s = load(scene_dir, "bunny.sp", 1280, 1024)  # 20480 tiles, 160 per row
