@@ -21,6 +21,8 @@
  *                                         Scene ctor's accelerator build, base/Scene.h:59)
  *   sp_scene_bvh_build_info               base/Scene.h:59 Scene ctor's BVHAccelerator build
  *                                         (shapes/BVHAccelerator.h:173), host only: statistics
+ *   sp_scene_upload_with                  the same upload with the binary BVH built on the device
+ *   sp_scene_bvh_check / _bvh_build_check (no counterpart: structural check of a built BVH)
  *   sp_render_tiles                       main.cpp:77-107 `render_thread`: for each scheduled
  *                                         tile, for each pixel, num_pixel_samples x
  *                                         `integrator.integrate(camera.generate_ray(...))`,
@@ -473,6 +475,52 @@ int  sp_adaptive_export(sp_progress* progress, sp_pixel_noise* h_noise, int64_t 
                         uint32_t* h_tile_samples, int64_t tiles);
 int  sp_adaptive_import(sp_progress* progress, const sp_pixel_noise* h_noise, int64_t count,
                         const uint32_t* h_tile_samples, int64_t tiles);
+
+/* ---- device BVH build ----------------------------------------------------------------------
+ * An upload builds the geometry BVH on one host core (binned SAH, or the reference's median split).
+ * sp_scene_upload_with can build it on the device instead: a linear BVH (Morton order, Karras 2012
+ * ranges) that is ready in a fraction of the time and traces somewhat slower.  Everything after the
+ * binary tree -- the 8-wide collapse, the primitive records, the stack or parent-link decision -- is
+ * the same code for either builder.  Images of a device-built scene differ from the SAH build's only
+ * where two primitives are hit at exactly equal distance.  sp_scene_upload_ex(s, d, p) is
+ * sp_scene_upload_with(s, d, p, NULL); NULL or SP_BUILDER_AUTO selects the host builders.  The
+ * environment variable SP_DEVICE_BUILD=1 (a test hook like SP_WIDE) turns AUTO into DEVICE for
+ * bvh_mode 0.  An explicit SP_BUILDER_DEVICE with bvh_mode 1 is SP_ERR_ARG: the reference order is a
+ * host contract.  A device build that cannot allocate or sort returns SP_ERR_HIP; it never falls back
+ * to the host.  The same scene uploaded with another builder is uploaded again. */
+#define SP_HAS_DEVICE_BUILD 1
+
+enum { SP_BUILDER_AUTO = 0, SP_BUILDER_HOST = 1, SP_BUILDER_DEVICE = 2 };
+typedef struct sp_build_params {      /* zero-initialise; struct_size = sizeof */
+    uint32_t struct_size;             /* a size the library does not know => SP_ERR_ARG */
+    int32_t  builder;                 /* SP_BUILDER_* */
+    int32_t  reserved[2];             /* must be 0 */
+} sp_build_params;
+int  sp_scene_upload_with(sp_scene* scene, int32_t device, const sp_upload_params* params, const sp_build_params* build);
+
+/* Structural check of a binary geometry BVH.  errors counts the violations of: child indices in
+ * range; every node reached from the root exactly once; leaf counts >= 1 and, for bvh_mode 0, at
+ * most 7 and at most the leaf size of the options (the reference build makes a leaf of any size
+ * where its split fails); the leaves' slot ranges partition [0, slots); prim_order is a
+ * permutation; no child box or primitive bound lies outside its node's box on any axis (compared
+ * with < and >, so an all-NaN bound does not count); depth agrees with a walk.  first_error_kind:
+ * 1 child range, 2 reached twice, 3 unreachable, 4 leaf count, 5 slots, 6 prim_order, 7 box, 8 depth. */
+typedef struct sp_bvh_check {         /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  builder;                 /* builder that made the tree: SP_BUILDER_HOST or _DEVICE */
+    int64_t  nodes, leaves, slots;
+    int32_t  depth, max_leaf;         /* levels as sp_bvh_info.depth; largest leaf */
+    int64_t  errors;                  /* 0 = every invariant holds */
+    int32_t  first_error_kind, reserved;
+    int64_t  first_error_node;
+    uint64_t hash;                    /* FNV-1a 64 over the node array, then prim_order */
+} sp_bvh_check;
+/* Uploaded scene: copies the binary geometry BVH and the slot codes back from the device and checks them. */
+int  sp_scene_bvh_check(sp_scene* scene, sp_bvh_check* out);
+/* Host only, no device: builds what an upload with these options would build and checks it; builder
+ * DEVICE runs the host restatement of the device algorithm, which makes the same tree bit for bit. */
+int  sp_scene_bvh_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
+                              sp_bvh_check* out);
 
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the

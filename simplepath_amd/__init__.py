@@ -115,14 +115,9 @@ class Scene:
     def set_resolution(self, width: int, height: int) -> None:
         check(lib().sp_scene_set_resolution(self._h, width, height))
 
-    def upload(self, device: int = 0, bvh_mode: int = 0, stackless: bool = False, stack_max_levels: int = 0,
-               wide_bvh: bool = True, env_replay: bool = False, sah_leaf: int = 0,
-               binary_closest: bool = False) -> None:
-        """bvh_mode 0 = SAH (throughput), 1 = the reference's median-split BVH (tie-exact order).
-        The other options (sp_upload_params) change how the same image is computed, never the
-        image: the parent-link walk, the LDS-stack depth budget, the image-light guide tables, the
-        SAH leaf size.  On the SAH BVH, wide_bvh / binary_closest choose the 8-wide or binary walks,
-        which can only differ in which of two primitives at exactly equal distance wins."""
+    @staticmethod
+    def _upload_params(bvh_mode=0, stackless=False, stack_max_levels=0, wide_bvh=True, env_replay=False, sah_leaf=0,
+                       binary_closest=False) -> _abi.sp_upload_params:
         p = _abi.sp_upload_params()
         p.bvh_mode = bvh_mode
         p.walk = _abi.SP_WALK_STACKLESS if stackless else _abi.SP_WALK_AUTO
@@ -131,8 +126,54 @@ class Scene:
         p.binary_closest = 1 if binary_closest else 0
         p.env_replay = 1 if env_replay else 0
         p.sah_leaf = sah_leaf
-        check(lib().sp_scene_upload_ex(self._h, device, C.byref(p)))
+        return p
+
+    @staticmethod
+    def _build_params(builder) -> _abi.sp_build_params:
+        b = _abi.sp_build_params()
+        b.struct_size = C.sizeof(_abi.sp_build_params)
+        b.builder = _abi.BUILDERS[builder] if isinstance(builder, str) else int(builder)
+        return b
+
+    def upload(self, device: int = 0, bvh_mode: int = 0, stackless: bool = False, stack_max_levels: int = 0,
+               wide_bvh: bool = True, env_replay: bool = False, sah_leaf: int = 0,
+               binary_closest: bool = False, builder="auto") -> None:
+        """bvh_mode 0 = SAH (throughput), 1 = the reference's median-split BVH (tie-exact order).
+        The other options (sp_upload_params) change how the same image is computed, never the
+        image: the parent-link walk, the LDS-stack depth budget, the image-light guide tables, the
+        SAH leaf size.  On the SAH BVH, wide_bvh / binary_closest choose the 8-wide or binary walks,
+        which can only differ in which of two primitives at exactly equal distance wins.
+        builder "auto" | "host" | "device" (sp_build_params): "device" builds a linear BVH on the
+        GPU instead of the SAH one on the host -- a much shorter upload, a somewhat slower trace,
+        and again the same image up to such ties."""
+        p = self._upload_params(bvh_mode, stackless, stack_max_levels, wide_bvh, env_replay, sah_leaf, binary_closest)
+        b = self._build_params(builder)
+        check(lib().sp_scene_upload_with(self._h, device, C.byref(p), C.byref(b)))
         self._device = device
+
+    @staticmethod
+    def _check_dict(c: _abi.sp_bvh_check) -> dict:
+        d = {k: getattr(c, k) for k, _ in _abi.sp_bvh_check._fields_ if k not in ("struct_size", "reserved")}
+        d["builder"] = {v: k for k, v in _abi.BUILDERS.items()}.get(c.builder, c.builder)
+        return d
+
+    def bvh_check(self) -> dict:
+        """Structural check of the uploaded scene's binary geometry BVH, read back from the device
+        (sp_scene_bvh_check): errors == 0 when every invariant holds; hash names the tree."""
+        c = _abi.sp_bvh_check()
+        c.struct_size = C.sizeof(_abi.sp_bvh_check)
+        check(lib().sp_scene_bvh_check(self._h, C.byref(c)))
+        return self._check_dict(c)
+
+    def bvh_build_check(self, builder="auto", **upload_options) -> dict:
+        """The same check on what upload(builder=..., **upload_options) would build, on the host
+        alone (sp_scene_bvh_build_check); "device" runs the host restatement of the device builder."""
+        p = self._upload_params(**upload_options)
+        b = self._build_params(builder)
+        c = _abi.sp_bvh_check()
+        c.struct_size = C.sizeof(_abi.sp_bvh_check)
+        check(lib().sp_scene_bvh_build_check(self._h, C.byref(p), C.byref(b), C.byref(c)))
+        return self._check_dict(c)
 
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()

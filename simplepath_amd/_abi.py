@@ -123,6 +123,22 @@ class sp_bvh_info(C.Structure):
                 ("stack_depth", C.c_int32), ("nodes", C.c_int64), ("slots", C.c_int64)]
 
 
+SP_BUILDER_AUTO, SP_BUILDER_HOST, SP_BUILDER_DEVICE = 0, 1, 2
+BUILDERS = {"auto": SP_BUILDER_AUTO, "host": SP_BUILDER_HOST, "device": SP_BUILDER_DEVICE}
+
+
+class sp_build_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class sp_bvh_check(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32),
+                ("nodes", C.c_int64), ("leaves", C.c_int64), ("slots", C.c_int64),
+                ("depth", C.c_int32), ("max_leaf", C.c_int32), ("errors", C.c_int64),
+                ("first_error_kind", C.c_int32), ("reserved", C.c_int32), ("first_error_node", C.c_int64),
+                ("hash", C.c_uint64)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -183,6 +199,10 @@ SIGNATURES = {
     "sp_device_count": (C.c_int, [C.POINTER(C.c_int32)]),
     "sp_scene_upload": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "sp_scene_upload_ex": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(sp_upload_params)]),
+    "sp_scene_upload_with": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(sp_upload_params), C.POINTER(sp_build_params)]),
+    "sp_scene_bvh_check": (C.c_int, [C.c_void_p, C.POINTER(sp_bvh_check)]),
+    "sp_scene_bvh_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.POINTER(sp_build_params),
+                                           C.POINTER(sp_bvh_check)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

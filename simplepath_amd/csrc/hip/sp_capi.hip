@@ -4,11 +4,13 @@
 #include "sp_chunk.hpp"
 #include "sp_launch.hpp"
 #include "sp_plan.hpp"
+#include "sp_build.hpp"
 #include "../host/sp_host.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -100,10 +102,11 @@ struct UploadOpts {
     bool env_guide  = true;  // image-light guide tables
     bool wide_closest = true;  // closest-hit queries on the 8-wide BVH as well
     int  sah_leaf   = 4;
+    int  builder    = SP_BUILDER_HOST; // SP_BUILDER_HOST or SP_BUILDER_DEVICE (sp_build_params, resolved)
     bool operator==(const UploadOpts& o) const
     {
         return bvh_mode == o.bvh_mode && stackless == o.stackless && stack_max == o.stack_max && wide == o.wide &&
-               env_guide == o.env_guide && sah_leaf == o.sah_leaf && wide_closest == o.wide_closest;
+               env_guide == o.env_guide && sah_leaf == o.sah_leaf && wide_closest == o.wide_closest && builder == o.builder;
     }
 };
 
@@ -135,10 +138,29 @@ int resolve_upload(const sp_upload_params* p, UploadOpts& o)
     return SP_OK;
 }
 
+// The builder of an upload (sp_build_params): NULL or AUTO is the host builders, unless the test
+// hook SP_DEVICE_BUILD=1 asks for the device builder on a SAH-mode upload.
+int resolve_build(const sp_build_params* b, UploadOpts& o)
+{
+    int builder = SP_BUILDER_AUTO;
+    if (b) {
+        if (b->struct_size != sizeof(sp_build_params)) return fail(SP_ERR_ARG, "sp_build_params.struct_size is not a known size");
+        if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_build_params.reserved must be 0");
+        if (b->builder != SP_BUILDER_AUTO && b->builder != SP_BUILDER_HOST && b->builder != SP_BUILDER_DEVICE)
+            return fail(SP_ERR_ARG, "builder must be SP_BUILDER_AUTO, SP_BUILDER_HOST or SP_BUILDER_DEVICE");
+        builder = b->builder;
+    }
+    if (builder == SP_BUILDER_DEVICE && o.bvh_mode == 1)
+        return fail(SP_ERR_ARG, "the device builder cannot make the reference order (bvh_mode 1)");
+    if (builder == SP_BUILDER_AUTO)
+        builder = (o.bvh_mode == 0 && env_int("SP_DEVICE_BUILD", 0) == 1) ? SP_BUILDER_DEVICE : SP_BUILDER_HOST;
+    o.builder = builder;
+    return SP_OK;
+}
+
 // Scene ctor partition (base/Scene.h:29: bounded primitives first, planes after, libstdc++
-// std::partition order) and the BVH over the bounded part: the reference's median split
-// (bvh_mode 1, shapes/BVHAccelerator.h:173) or SAH.
-sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int32_t>& prims, size_t& part)
+// std::partition order) and the bounds of the bounded part
+std::vector<sph::PrimBounds> bounded_prims(const sph::Scene& h, std::vector<int32_t>& prims, size_t& part)
 {
     prims.resize(h.prim_kind.size());
     for (size_t i = 0; i < prims.size(); ++i) prims[i] = (int32_t)i;
@@ -150,7 +172,44 @@ sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int3
         if (h.prim_kind[p] == SP_PRIM_TRIANGLE) bounds.push_back(tri_bounds(h, h.prim_index[p]));
         else bounds.push_back(sphere_bounds(from_desc(h.shapes[h.prim_index[p]].object_to_world)));
     }
-    return (o.bvh_mode == 1) ? sph::build_bvh_reference(bounds) : sph::build_bvh_sah(bounds, o.sah_leaf);
+    return bounds;
+}
+
+// One upload's stage times (tools/upload_timing.py): printed as a JSON line when SP_UPLOAD_TIMING is set
+struct UploadTiming {
+    double          ms_bounds = 0, ms_bvh = 0, ms_wide = 0, ms_pack = 0, ms_copies = 0;
+    spb::BuildStats dev{};
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(double& ms)
+    {
+        const auto t1 = std::chrono::steady_clock::now();
+        ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+    }
+};
+
+// The BVH over the bounded part: the reference's median split (bvh_mode 1,
+// shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder -- built on the
+// current device when `on_device`, else by its host restatement (the same tree).
+sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int32_t>& prims, size_t& part, bool on_device = false,
+                      UploadTiming* tm = nullptr, std::vector<sph::PrimBounds>* bounds_out = nullptr)
+{
+    std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
+    if (tm) tm->lap(tm->ms_bounds);
+    sph::Bvh bvh;
+    if (o.bvh_mode == 1) bvh = sph::build_bvh_reference(bounds);
+    else if (o.builder != SP_BUILDER_DEVICE) bvh = sph::build_bvh_sah(bounds, o.sah_leaf);
+    else if (!on_device) bvh = sph::build_bvh_lbvh(bounds, o.sah_leaf);
+    else {
+        spb::BuildStats st;
+        std::string     err;
+        const int       rc = spb::build_lbvh_device(bounds, o.sah_leaf, bvh, st, err, tm != nullptr);
+        if (rc != SP_OK) throw sph::SpError(rc, err);
+        if (tm) tm->dev = st;
+    }
+    if (tm) tm->lap(tm->ms_bvh);
+    if (bounds_out) bounds_out->swap(bounds);
+    return bvh;
 }
 
 // SAH scenes get the 8-wide quantised BVH for any-hit queries (no_wide_bvh keeps the binary walk)
@@ -749,11 +808,12 @@ static int stack_entries(int depth, int wide_depth, int light_depth, bool wide_c
     return std::max(depth, std::max(wide_depth, light_depth)) + 1;
 }
 
-static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params* up_params)
+static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params* up_params, const sp_build_params* build)
 {
     if (!s) return fail(SP_ERR_ARG, "null scene");
     UploadOpts opts;
     if (int rc0 = resolve_upload(up_params, opts)) return rc0;
+    if (int rc0 = resolve_build(build, opts)) return rc0;
     const int bvh_mode = opts.bvh_mode;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SP_ERR_HIP, "no HIP device");
@@ -795,7 +855,9 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     // ---- geometry: Scene ctor partition (base/Scene.h:29) then BVH over the bounded part
     std::vector<int32_t> prims;
     size_t               part = 0;
-    const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part);
+    UploadTiming         timing;
+    UploadTiming*        tm   = std::getenv("SP_UPLOAD_TIMING") ? &timing : nullptr;
+    const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part, true, tm);
     std::vector<spd::Shape> shapes;
     for (auto& sh : h.shapes) {
         spd::Shape x{};
@@ -828,6 +890,7 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     std::vector<spd::Node> nodes(bvh.nodes.size());
     static_assert(sizeof(spd::Node) == sizeof(sph::BvhNode), "node layout");
     std::memcpy(nodes.data(), bvh.nodes.data(), nodes.size() * sizeof(spd::Node));
+    if (tm) tm->lap(tm->ms_pack);
     // ---- lights: Scene::m_lights order + accelerator (partition by boundedness)
     std::vector<spd::Light> lights;
     for (auto& l : h.lights) {
@@ -854,11 +917,14 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     const bool          stackless = stackless_for(opts, std::max(bvh.max_depth, lbvh.max_depth));
     sph::WideBvh        wide;
     std::vector<float4> wslot_tri;
+    if (tm) tm->lap(tm->ms_copies); // (lights: counted with the copies)
     if (wide_enabled(opts) && !nodes.empty() && !stackless) {
         wide = sph::build_wide(bvh);
+        if (tm) tm->lap(tm->ms_wide);
         wslot_tri.resize(wide.slot_of.size() * 3);
         for (size_t i = 0; i < wide.slot_of.size(); ++i)
             for (int k = 0; k < 3; ++k) wslot_tri[3 * i + k] = slot_tri[3 * (size_t)wide.slot_of[i] + k];
+        if (tm) tm->lap(tm->ms_pack);
     }
 
     // ---- upload
@@ -997,22 +1063,41 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     SP_HIP(hipEventCreate(&r.ev1[0]));
     SP_HIP(hipEventCreateWithFlags(&r.ev_done[0], hipEventDisableTiming));
     for (hipEvent_t& e : r.ev_tiles.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (tm) {
+        tm->lap(tm->ms_copies);
+        const spb::BuildStats& b = tm->dev;
+        std::fprintf(stderr,
+                     "sp_upload_timing {\"builder\": \"%s\", \"bvh_mode\": %d, \"prims\": %zu, \"nodes\": %zu, \"depth\": %d, "
+                     "\"stackless\": %d, \"bounds_ms\": %.3f, \"bvh_ms\": %.3f, \"wide_ms\": %.3f, \"pack_ms\": %.3f, \"copies_ms\": %.3f, "
+                     "\"device\": {\"bounds_up_ms\": %.3f, \"codes_ms\": %.3f, \"sort_ms\": %.3f, \"hierarchy_ms\": %.3f, \"fit_ms\": %.3f, "
+                     "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}}\n",
+                     opts.builder == SP_BUILDER_DEVICE ? "device" : "host", opts.bvh_mode, bvh.prim_order.size(), bvh.nodes.size(),
+                     bvh.max_depth, d.stackless, tm->ms_bounds, tm->ms_bvh, tm->ms_wide, tm->ms_pack, tm->ms_copies, b.ms_bounds_up,
+                     b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes);
+    }
     return SP_OK;
 }
 
 // No C++ exception crosses the C ABI: host-side failures (allocation, BVH encoding limits)
 // come back as error codes with sp_last_error() set.
-int sp_scene_upload_ex(sp_scene* s, int32_t device, const sp_upload_params* params)
+int sp_scene_upload_with(sp_scene* s, int32_t device, const sp_upload_params* params, const sp_build_params* build)
 {
     if (!s) return fail(SP_ERR_ARG, "null scene");
     std::lock_guard<std::mutex> lock(s->mu);
     try {
-        return scene_upload_impl(s, device, params);
+        return scene_upload_impl(s, device, params, build);
     } catch (const sph::SpError& e) {
+        s->release(); // a build that failed half way leaves no resident scene
         return fail(e.code, e.what());
     } catch (const std::exception& e) {
+        s->release();
         return fail(SP_ERR_UNSUPPORTED, std::string("scene upload failed: ") + e.what());
     }
+}
+
+int sp_scene_upload_ex(sp_scene* s, int32_t device, const sp_upload_params* params)
+{
+    return sp_scene_upload_with(s, device, params, nullptr);
 }
 
 int sp_scene_upload(sp_scene* s, int32_t device, int32_t bvh_mode)
@@ -2382,6 +2467,7 @@ int sp_scene_bvh_build_info(const sp_scene* s, int32_t bvh_mode, sp_bvh_info* ou
         up.bvh_mode = bvh_mode;
         UploadOpts opts;
         if (int rc0 = resolve_upload(&up, opts)) return rc0;
+        if (int rc0 = resolve_build(nullptr, opts)) return rc0;
         const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part);
         *out                      = sp_bvh_info{};
         out->depth                = bvh.max_depth;
@@ -2397,6 +2483,85 @@ int sp_scene_bvh_build_info(const sp_scene* s, int32_t bvh_mode, sp_bvh_info* ou
         return SP_OK;
     } catch (const std::exception& e) {
         return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
+    }
+}
+
+namespace {
+// sp_bvh_check from the host checker's findings; bvh_mode 1 leaves are not limited (a failed split)
+int fill_check(const sph::Bvh& bvh, const std::vector<sph::PrimBounds>& bounds, const UploadOpts& opts, sp_bvh_check* out)
+{
+    const sph::BvhCheck c = sph::check_bvh(bvh, bounds, opts.bvh_mode == 1 ? 0 : opts.sah_leaf);
+    const uint32_t      sz = out->struct_size;
+    *out                  = sp_bvh_check{};
+    out->struct_size      = sz;
+    out->builder          = opts.builder;
+    out->nodes            = c.nodes;
+    out->leaves           = c.leaves;
+    out->slots            = c.slots;
+    out->depth            = c.depth;
+    out->max_leaf         = c.max_leaf;
+    out->errors           = c.errors;
+    out->first_error_kind = c.first_error_kind;
+    out->first_error_node = c.first_error_node;
+    out->hash             = c.hash;
+    return SP_OK;
+}
+} // namespace
+
+int sp_scene_bvh_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build, sp_bvh_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
+    UploadOpts opts;
+    if (int rc0 = resolve_upload(params, opts)) return rc0;
+    if (int rc0 = resolve_build(build, opts)) return rc0;
+    try {
+        std::vector<int32_t>         prims;
+        size_t                       part = 0;
+        std::vector<sph::PrimBounds> bounds;
+        const sph::Bvh               bvh = geometry_bvh(*s->host, opts, prims, part, false, nullptr, &bounds);
+        return fill_check(bvh, bounds, opts, out);
+    } catch (const sph::SpError& e) {
+        return fail(e.code, e.what());
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
+    }
+}
+
+int sp_scene_bvh_check(sp_scene* s, sp_bvh_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
+    try {
+        SP_HIP(hipSetDevice(s->device));
+        sph::Bvh bvh;
+        bvh.nodes.resize(s->geom_nodes);
+        bvh.max_depth = s->geom_depth;
+        std::vector<uint32_t> codes(s->geom_slots);
+        SP_HIP(hipDeviceSynchronize()); // queued renders read these arrays; nothing writes them
+        if (!bvh.nodes.empty()) SP_HIP(hipMemcpy(bvh.nodes.data(), s->dev.nodes, bvh.nodes.size() * sizeof(sph::BvhNode), hipMemcpyDeviceToHost));
+        if (!codes.empty()) SP_HIP(hipMemcpy(codes.data(), s->dev.slot_code, codes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        // slot -> bounded primitive: each primitive's code (kind, index) names it
+        const sph::Scene&            h = *s->host;
+        std::vector<int32_t>         prims;
+        size_t                       part = 0;
+        std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
+        std::vector<std::pair<uint32_t, int32_t>> by_code(part);
+        for (size_t i = 0; i < part; ++i) by_code[i] = { code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]), (int32_t)i };
+        std::sort(by_code.begin(), by_code.end());
+        std::vector<uint8_t> taken(part, 0);
+        bvh.prim_order.resize(codes.size());
+        for (size_t sl = 0; sl < codes.size(); ++sl) {
+            auto it = std::lower_bound(by_code.begin(), by_code.end(), std::make_pair(codes[sl], (int32_t)0));
+            while (it != by_code.end() && it->first == codes[sl] && taken[(size_t)(it - by_code.begin())]) ++it; // a scene may list a primitive twice
+            if (it == by_code.end() || it->first != codes[sl]) bvh.prim_order[sl] = -1; // the checker reports it
+            else { taken[(size_t)(it - by_code.begin())] = 1; bvh.prim_order[sl] = it->second; }
+        }
+        return fill_check(bvh, bounds, s->opts, out);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("BVH check failed: ") + e.what());
     }
 }
 

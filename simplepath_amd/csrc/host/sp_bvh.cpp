@@ -6,8 +6,10 @@
 // and resolves equal-distance ties identically.  build_bvh_sah is the throughput build: binned
 // SAH (Wald 2007) with the same node format; it changes only the visiting order.
 #include "sp_host.hpp"
+#include "../common/sp_lbvh.h"
 
 #include <cstdio>
+#include <cstdlib>
 
 #include <stdexcept>
 #include <cstring>
@@ -238,6 +240,199 @@ Bvh build_bvh_sah(const std::vector<PrimBounds>& bounds, int max_leaf)
     out.prim_order = std::move(b.ids);
     out.max_depth  = b.max_depth;
     return out;
+}
+
+// ------------------------------------------------------------------------------ linear BVH
+// The device builder's algorithm (sp_build.hip) step by step on the host: the
+// arithmetic is sp_lbvh.h on both sides, the sort is stable on both sides, and the box merges
+// keep one operand order, so the two trees are equal bit for bit.
+int bvh_walk_depth(const std::vector<BvhNode>& nodes)
+{
+    if (nodes.empty()) return 0;
+    int                                     depth = 0;
+    size_t                                  seen  = 0;
+    std::vector<std::pair<uint32_t, int>>   stack{ { 0u, 1 } };
+    while (!stack.empty()) {
+        const auto [i, d] = stack.back();
+        stack.pop_back();
+        if (i >= nodes.size() || ++seen > nodes.size()) throw std::runtime_error("BVH links do not form a tree");
+        depth = std::max(depth, d);
+        if (nodes[i].b & BVH_LEAF) continue;
+        stack.push_back({ nodes[i].b, d + 1 });
+        stack.push_back({ nodes[i].a & BVH_CHILD_MASK, d + 1 });
+    }
+    return depth;
+}
+
+void lbvh_fit_boxes(Bvh& bvh, const std::vector<PrimBounds>& bounds)
+{
+    std::vector<BvhNode>& nodes = bvh.nodes;
+    if (nodes.empty()) return;
+    // parents before children, then backwards
+    std::vector<uint32_t> order;
+    order.reserve(nodes.size());
+    std::vector<uint32_t> stack{ 0u };
+    while (!stack.empty()) {
+        const uint32_t i = stack.back();
+        stack.pop_back();
+        if (i >= nodes.size() || order.size() >= nodes.size()) throw std::runtime_error("BVH links do not form a tree");
+        order.push_back(i);
+        if (nodes[i].b & BVH_LEAF) continue;
+        stack.push_back(nodes[i].b);
+        stack.push_back(nodes[i].a & BVH_CHILD_MASK);
+    }
+    for (size_t k = order.size(); k-- > 0;) {
+        BvhNode& nd = nodes[order[k]];
+        if (nd.b & BVH_LEAF) {
+            Box bb = empty_box();
+            for (uint32_t s = 0; s < (nd.b & ~BVH_LEAF); ++s) bb = merge(bb, bounds[(size_t)bvh.prim_order[nd.a + s]]);
+            for (int i = 0; i < 3; ++i) { nd.lo[i] = bb.lo[i]; nd.hi[i] = bb.hi[i]; }
+        } else {
+            const BvhNode& l = nodes[nd.a & BVH_CHILD_MASK];
+            const BvhNode& r = nodes[nd.b];
+            for (int i = 0; i < 3; ++i) {
+                nd.lo[i] = spm::sse_min(l.lo[i], r.lo[i]);
+                nd.hi[i] = spm::sse_max(l.hi[i], r.hi[i]);
+            }
+        }
+    }
+}
+
+Bvh build_bvh_lbvh(const std::vector<PrimBounds>& bounds, int max_leaf)
+{
+    Bvh          out;
+    const size_t n = bounds.size();
+    if (n >= (size_t(1) << BVH_AXIS_SHIFT)) throw std::runtime_error("too many primitives for the linear BVH");
+    if (max_leaf < 1 || max_leaf > 4) throw std::runtime_error("linear BVH: leaf size must be 1..4");
+    if (n == 0) return out;
+    // centroid bounds, cells, codes
+    float cb_lo[3] = { INFINITY, INFINITY, INFINITY }, cb_hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (const PrimBounds& b : bounds)
+        for (int d = 0; d < 3; ++d) {
+            const float c = lbvh::centre(b.lo[d], b.hi[d]);
+            cb_lo[d]      = lbvh::lower(cb_lo[d], c);
+            cb_hi[d]      = lbvh::upper(cb_hi[d], c);
+        }
+    std::vector<uint64_t> key(n);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t q[3];
+        for (int d = 0; d < 3; ++d) q[d] = lbvh::cell(lbvh::centre(bounds[i].lo[d], bounds[i].hi[d]), cb_lo[d], cb_hi[d]);
+        key[i] = lbvh::code(q[0], q[1], q[2]);
+    }
+    // stable sort of (code, id) by code
+    out.prim_order.resize(n);
+    for (size_t i = 0; i < n; ++i) out.prim_order[i] = (int32_t)i;
+    std::stable_sort(out.prim_order.begin(), out.prim_order.end(), [&](int32_t a, int32_t b) { return key[(size_t)a] < key[(size_t)b]; });
+    std::vector<uint64_t> codes(n);
+    for (size_t i = 0; i < n; ++i) codes[i] = key[(size_t)out.prim_order[i]];
+    // candidates: internal nodes 0..n-2, then single primitives; a child is kept when its parent
+    // covers more than max_leaf positions, and a kept node covering at most max_leaf is a leaf
+    const uint32_t           un = (uint32_t)n, total = 2 * un - 1;
+    std::vector<lbvh::Range> rng(n - 1);
+    std::vector<uint32_t>    keep(total, 0u), index(total);
+    // (ranges only shrink downwards, so "the parent covers more" holds for every ancestor too)
+    keep[0] = 1; // the root: internal node 0, or the only primitive
+    for (uint32_t i = 0; i + 1 < un; ++i) {
+        rng[i] = lbvh::node_range(codes.data(), (int64_t)n, i);
+        const uint32_t kept = (rng[i].last - rng[i].first + 1 > (uint32_t)max_leaf) ? 1u : 0u;
+        keep[lbvh::left_cand(rng[i], un)]  = kept;
+        keep[lbvh::right_cand(rng[i], un)] = kept;
+    }
+    uint32_t m = 0;
+    for (uint32_t c = 0; c < total; ++c) { index[c] = m; m += keep[c]; }
+    out.nodes.assign(m, BvhNode{});
+    for (uint32_t c = 0; c < total; ++c) {
+        if (!keep[c]) continue;
+        BvhNode& nd = out.nodes[index[c]];
+        if (c < un - 1 && rng[c].last - rng[c].first + 1 > (uint32_t)max_leaf) {
+            nd.a = index[lbvh::left_cand(rng[c], un)] | rng[c].axis << BVH_AXIS_SHIFT;
+            nd.b = index[lbvh::right_cand(rng[c], un)];
+        } else {
+            const uint32_t first = c < un - 1 ? rng[c].first : c - (un - 1);
+            const uint32_t count = c < un - 1 ? rng[c].last - rng[c].first + 1 : 1u;
+            nd.a = first;
+            nd.b = count | BVH_LEAF;
+        }
+    }
+    lbvh_fit_boxes(out, bounds);
+    out.max_depth = bvh_walk_depth(out.nodes);
+    return out;
+}
+
+// ------------------------------------------------------------------------------ checker
+BvhCheck check_bvh(const Bvh& bvh, const std::vector<PrimBounds>& bounds, int max_leaf)
+{
+    BvhCheck   r;
+    const auto& nodes = bvh.nodes;
+    r.nodes = (int64_t)nodes.size();
+    r.slots = (int64_t)bvh.prim_order.size();
+    auto bad = [&](int kind, int64_t node) {
+        if (r.errors++ == 0) { r.first_error_kind = kind; r.first_error_node = node; }
+    };
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto fnv = [&](const void* p, size_t bytes) {
+        const unsigned char* c = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 0x100000001b3ull; }
+    };
+    fnv(nodes.data(), nodes.size() * sizeof(BvhNode));
+    fnv(bvh.prim_order.data(), bvh.prim_order.size() * sizeof(int32_t));
+    r.hash = h;
+    // prim_order: a permutation of the bounded primitives
+    const size_t np = bounds.size();
+    bool         order_ok = bvh.prim_order.size() == np;
+    {
+        std::vector<uint8_t> seen(np, 0);
+        for (size_t s = 0; s < bvh.prim_order.size(); ++s) {
+            const int32_t p = bvh.prim_order[s];
+            if (p < 0 || (size_t)p >= np || seen[(size_t)p]++) { bad(BVH_ERR_PRIM_ORDER, (int64_t)s); order_ok = false; }
+        }
+        if (bvh.prim_order.size() != np) bad(BVH_ERR_PRIM_ORDER, -1);
+    }
+    if (nodes.empty()) {
+        if (np != 0) bad(BVH_ERR_SLOT_PARTITION, -1);
+        if (bvh.max_depth != 0) bad(BVH_ERR_DEPTH, -1);
+        return r;
+    }
+    auto outside = [](const float* lo, const float* hi, const BvhNode& n) {
+        for (int d = 0; d < 3; ++d)
+            if (lo[d] < n.lo[d] || hi[d] > n.hi[d]) return true;
+        return false;
+    };
+    std::vector<uint8_t>                  visited(nodes.size(), 0), covered(bvh.prim_order.size(), 0);
+    std::vector<std::pair<uint32_t, int>> stack{ { 0u, 1 } };
+    while (!stack.empty()) {
+        const auto [i, depth] = stack.back();
+        stack.pop_back();
+        if (visited[i]) { bad(BVH_ERR_VISITED_TWICE, i); continue; }
+        visited[i] = 1;
+        r.depth    = std::max(r.depth, depth);
+        const BvhNode& nd = nodes[i];
+        if (nd.b & BVH_LEAF) {
+            const uint32_t cnt = nd.b & ~BVH_LEAF;
+            ++r.leaves;
+            r.max_leaf = std::max<int>(r.max_leaf, (int)std::min<uint32_t>(cnt, 0x7fffffffu));
+            if (cnt < 1 || (max_leaf > 0 && (cnt > 7 || cnt > (uint32_t)max_leaf))) bad(BVH_ERR_LEAF_COUNT, i);
+            if ((uint64_t)nd.a + cnt > covered.size()) { bad(BVH_ERR_SLOT_PARTITION, i); continue; }
+            for (uint32_t s = 0; s < cnt; ++s) {
+                if (covered[nd.a + s]++) bad(BVH_ERR_SLOT_PARTITION, i);
+                const int32_t p = bvh.prim_order[nd.a + s];
+                if (order_ok && outside(bounds[(size_t)p].lo, bounds[(size_t)p].hi, nd)) bad(BVH_ERR_BOX, i);
+            }
+            continue;
+        }
+        const uint32_t kids[2] = { nd.a & BVH_CHILD_MASK, nd.b };
+        for (int k = 1; k >= 0; --k) {
+            if (kids[k] >= nodes.size()) { bad(BVH_ERR_CHILD_RANGE, i); continue; }
+            if (outside(nodes[kids[k]].lo, nodes[kids[k]].hi, nd)) bad(BVH_ERR_BOX, i);
+            stack.push_back({ kids[k], depth + 1 });
+        }
+    }
+    for (size_t i = 0; i < nodes.size(); ++i)
+        if (!visited[i]) bad(BVH_ERR_UNREACHABLE, (int64_t)i);
+    for (size_t s = 0; s < covered.size(); ++s)
+        if (!covered[s]) bad(BVH_ERR_SLOT_PARTITION, -1); // (a slot covered twice is counted above)
+    if (r.depth != bvh.max_depth) bad(BVH_ERR_DEPTH, -1);
+    return r;
 }
 
 // ---------------------------------------------------------------- 8-wide collapse

@@ -166,6 +166,33 @@ Bvh build_bvh_reference(const std::vector<PrimBounds>& bounds);
 // Binned SAH construction (product default).
 Bvh build_bvh_sah(const std::vector<PrimBounds>& bounds, int max_leaf = 4);
 
+// Linear BVH (Morton order + Karras 2012 ranges): the host restatement of the device builder
+// (sp_build.hip), the same tree bit for bit.  max_leaf 1..4.
+Bvh build_bvh_lbvh(const std::vector<PrimBounds>& bounds, int max_leaf = 4);
+// The two steps of it that the device build also runs on the host.  lbvh_fit_boxes fits every
+// box of a tree whose children and leaf ranges are set (leaves fold their primitives in slot
+// order, internal nodes merge left then right); bvh_walk_depth counts the levels (root = 1, empty
+// = 0) with an explicit stack and throws when the links do not form a tree.
+void lbvh_fit_boxes(Bvh& bvh, const std::vector<PrimBounds>& bounds);
+int  bvh_walk_depth(const std::vector<BvhNode>& nodes);
+
+// Structural check of a binary BVH over `bounds` (sp_bvh_check): what is wrong is counted in
+// `errors`, the first finding kept.  max_leaf 0: leaves of any size (the reference build makes a
+// leaf wherever its split fails).
+enum BvhError {
+    BVH_ERR_NONE = 0, BVH_ERR_CHILD_RANGE = 1, BVH_ERR_VISITED_TWICE = 2, BVH_ERR_UNREACHABLE = 3, BVH_ERR_LEAF_COUNT = 4,
+    BVH_ERR_SLOT_PARTITION = 5, BVH_ERR_PRIM_ORDER = 6, BVH_ERR_BOX = 7, BVH_ERR_DEPTH = 8
+};
+struct BvhCheck {
+    int64_t  nodes = 0, leaves = 0, slots = 0;
+    int      depth = 0, max_leaf = 0;
+    int64_t  errors = 0;
+    int      first_error_kind = BVH_ERR_NONE;
+    int64_t  first_error_node = -1;
+    uint64_t hash = 0; // FNV-1a 64 over the node array, then prim_order
+};
+BvhCheck check_bvh(const Bvh& bvh, const std::vector<PrimBounds>& bounds, int max_leaf);
+
 // 8-wide BVH collapsed from a binary SAH BVH (sp_bvh.cpp build_wide): 80-byte nodes with
 // child boxes quantised outward on a per-node power-of-two grid, internal children first.
 // Layout per node (5 x 16 bytes, u32 words):
