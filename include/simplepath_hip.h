@@ -480,8 +480,9 @@ int  sp_adaptive_import(sp_progress* progress, const sp_pixel_noise* h_noise, in
  * An upload builds the geometry BVH on one host core (binned SAH, or the reference's median split).
  * sp_scene_upload_with can build it on the device instead: a linear BVH (Morton order, Karras 2012
  * ranges) that is ready in a fraction of the time and traces somewhat slower.  Everything after the
- * binary tree -- the 8-wide collapse, the primitive records, the stack or parent-link decision -- is
- * the same code for either builder.  Images of a device-built scene differ from the SAH build's only
+ * binary tree -- the 8-wide collapse, the primitive records, the stack or parent-link decision --
+ * makes the same arrays for either builder, on the host or on the device (the device finish, below).
+ * Images of a device-built scene differ from the SAH build's only
  * where two primitives are hit at exactly equal distance.  sp_scene_upload_ex(s, d, p) is
  * sp_scene_upload_with(s, d, p, NULL); NULL or SP_BUILDER_AUTO selects the host builders.  The
  * environment variable SP_DEVICE_BUILD=1 (a test hook like SP_WIDE) turns AUTO into DEVICE for
@@ -521,6 +522,62 @@ int  sp_scene_bvh_check(sp_scene* scene, sp_bvh_check* out);
  * DEVICE runs the host restatement of the device algorithm, which makes the same tree bit for bit. */
 int  sp_scene_bvh_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
                               sp_bvh_check* out);
+
+/* ---- device finish -------------------------------------------------------------------------
+ * After the binary tree an upload collapses it into the 8-wide BVH (wnodes, wslot_tri), packs the
+ * primitive records (slot_tri, slot_code) and, for a stackless scene, links the parents.  The host
+ * does this on one core; the device finish does it in kernels on the binary tree resident in device
+ * memory, level by level, and writes the same bytes: every array equals the host's bit for bit, so
+ * renders are identical.  SP_FINISH_AUTO is the device finish when the builder resolves to
+ * SP_BUILDER_DEVICE and the host finish otherwise, so a default upload is untouched.
+ * SP_FINISH_DEVICE goes with either builder for bvh_mode 0; with bvh_mode 1 it is SP_ERR_ARG.  A
+ * device finish that fails (allocation, more than 2^24 records or 64 levels, a leaf that does not
+ * fit a meta byte, a failed quantisation) is SP_ERR_HIP and leaves no resident scene.  The
+ * environment variable SP_DEVICE_FINISH=0|1 (a test hook like SP_DEVICE_BUILD) decides AUTO.  The
+ * same scene uploaded with another finish is uploaded again.
+ *
+ * sp_build_params keeps its 16 bytes and its meaning.  sp_build_params_ex begins with the same
+ * fields and adds the finish; pass it to sp_scene_upload_with and the check calls through a cast
+ * -- struct_size tells the two apart. */
+#define SP_HAS_DEVICE_FINISH 1
+
+enum { SP_FINISH_AUTO = 0, SP_FINISH_HOST = 1, SP_FINISH_DEVICE = 2 };
+typedef struct sp_build_params_ex {   /* zero-initialise; struct_size = sizeof */
+    uint32_t struct_size;
+    int32_t  builder;                 /* SP_BUILDER_* */
+    int32_t  reserved[2];             /* must be 0 */
+    int32_t  finish;                  /* SP_FINISH_* */
+    int32_t  reserved2[3];            /* must be 0 */
+} sp_build_params_ex;
+
+/* Structural check of the 8-wide BVH and the records beside it.  errors counts the violations of:
+ * an inner slot's child_base + s in range; every record reached from the root exactly once, the
+ * others being holes (child slots no inner child took) that are all zero and named by no imask; an
+ * occupied leaf slot's meta byte has a count of 1..7; the leaf ranges [leaf_base + offset, + count)
+ * partition [0, slots); the wslot_tri codes are a permutation of slot_code; every child's decoded
+ * box -- fma(q, step, origin) as the walk decodes it -- contains the exact union of all primitive
+ * bounds beneath that child (compared with < and >, so a NaN bound does not count); depth agrees
+ * with a walk.  first_error_kind: 1 child range, 2 reached twice, 3 unreachable, 4 hole, 5 meta
+ * byte, 6 leaf ranges, 7 record codes, 8 box, 9 depth.  A scene without a wide tree (stackless,
+ * no_wide_bvh, bvh_mode 1, no bounded primitive) reports records 0 and hash_nodes 0. */
+typedef struct sp_wide_check {        /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  finish;                  /* SP_FINISH_HOST or _DEVICE that made the arrays */
+    int64_t  records, holes, slots;
+    int32_t  depth, reserved;
+    int64_t  errors;
+    int32_t  first_error_kind, reserved2;
+    int64_t  first_error_node;
+    uint64_t hash_nodes;              /* FNV-1a 64 over the wnodes words (0 when no wide tree) */
+    uint64_t hash_records;            /* over slot_tri bytes, slot_code, then wslot_tri bytes */
+    uint64_t hash_parents;            /* over parents (0 when not stackless) */
+} sp_wide_check;
+/* Uploaded scene: the arrays read back from the device. */
+int  sp_scene_wide_check(sp_scene* scene, sp_wide_check* out);
+/* Host only, no device: what an upload with these options would make; finish DEVICE runs the host
+ * restatement of the device finish (the level-wise collapse), which makes the same arrays. */
+int  sp_scene_wide_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
+                               sp_wide_check* out);
 
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the

@@ -129,15 +129,17 @@ class Scene:
         return p
 
     @staticmethod
-    def _build_params(builder) -> _abi.sp_build_params:
-        b = _abi.sp_build_params()
-        b.struct_size = C.sizeof(_abi.sp_build_params)
+    def _build_params(builder, finish="auto"):
+        """sp_build_params_ex as the pointer the entry points take (struct_size tells it apart)"""
+        b = _abi.sp_build_params_ex()
+        b.struct_size = C.sizeof(_abi.sp_build_params_ex)
         b.builder = _abi.BUILDERS[builder] if isinstance(builder, str) else int(builder)
-        return b
+        b.finish = _abi.FINISHES[finish] if isinstance(finish, str) else int(finish)
+        return C.cast(C.pointer(b), C.POINTER(_abi.sp_build_params))
 
     def upload(self, device: int = 0, bvh_mode: int = 0, stackless: bool = False, stack_max_levels: int = 0,
                wide_bvh: bool = True, env_replay: bool = False, sah_leaf: int = 0,
-               binary_closest: bool = False, builder="auto") -> None:
+               binary_closest: bool = False, builder="auto", finish="auto") -> None:
         """bvh_mode 0 = SAH (throughput), 1 = the reference's median-split BVH (tie-exact order).
         The other options (sp_upload_params) change how the same image is computed, never the
         image: the parent-link walk, the LDS-stack depth budget, the image-light guide tables, the
@@ -145,10 +147,13 @@ class Scene:
         which can only differ in which of two primitives at exactly equal distance wins.
         builder "auto" | "host" | "device" (sp_build_params): "device" builds a linear BVH on the
         GPU instead of the SAH one on the host -- a much shorter upload, a somewhat slower trace,
-        and again the same image up to such ties."""
+        and again the same image up to such ties.
+        finish "auto" | "host" | "device" (sp_build_params_ex): where the 8-wide collapse, the
+        primitive records and the parent links are made from the binary tree.  Both make the same
+        bytes; "auto" is "device" with the device builder and "host" otherwise."""
         p = self._upload_params(bvh_mode, stackless, stack_max_levels, wide_bvh, env_replay, sah_leaf, binary_closest)
-        b = self._build_params(builder)
-        check(lib().sp_scene_upload_with(self._h, device, C.byref(p), C.byref(b)))
+        b = self._build_params(builder, finish)
+        check(lib().sp_scene_upload_with(self._h, device, C.byref(p), b))
         self._device = device
 
     @staticmethod
@@ -172,8 +177,32 @@ class Scene:
         b = self._build_params(builder)
         c = _abi.sp_bvh_check()
         c.struct_size = C.sizeof(_abi.sp_bvh_check)
-        check(lib().sp_scene_bvh_build_check(self._h, C.byref(p), C.byref(b), C.byref(c)))
+        check(lib().sp_scene_bvh_build_check(self._h, C.byref(p), b, C.byref(c)))
         return self._check_dict(c)
+
+    @staticmethod
+    def _wide_dict(c: _abi.sp_wide_check) -> dict:
+        d = {k: getattr(c, k) for k, _ in _abi.sp_wide_check._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+        d["finish"] = {v: k for k, v in _abi.FINISHES.items()}.get(c.finish, c.finish)
+        return d
+
+    def wide_check(self) -> dict:
+        """Structural check of the uploaded scene's 8-wide BVH and the hashes of every array the
+        finish step made, read back from the device (sp_scene_wide_check)."""
+        c = _abi.sp_wide_check()
+        c.struct_size = C.sizeof(_abi.sp_wide_check)
+        check(lib().sp_scene_wide_check(self._h, C.byref(c)))
+        return self._wide_dict(c)
+
+    def wide_build_check(self, builder="auto", finish="auto", **upload_options) -> dict:
+        """The same on what upload(builder=..., finish=..., **upload_options) would make, on the
+        host alone (sp_scene_wide_build_check); "device" runs the level-wise host restatement."""
+        p = self._upload_params(**upload_options)
+        b = self._build_params(builder, finish)
+        c = _abi.sp_wide_check()
+        c.struct_size = C.sizeof(_abi.sp_wide_check)
+        check(lib().sp_scene_wide_build_check(self._h, C.byref(p), b, C.byref(c)))
+        return self._wide_dict(c)
 
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()

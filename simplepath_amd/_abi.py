@@ -131,6 +131,24 @@ class sp_build_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+SP_FINISH_AUTO, SP_FINISH_HOST, SP_FINISH_DEVICE = 0, 1, 2
+FINISHES = {"auto": SP_FINISH_AUTO, "host": SP_FINISH_HOST, "device": SP_FINISH_DEVICE}
+
+
+class sp_build_params_ex(C.Structure):
+    """sp_build_params with the finish behind it; the library tells the two apart by struct_size"""
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("finish", C.c_int32), ("reserved2", C.c_int32 * 3)]
+
+
+class sp_wide_check(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("finish", C.c_int32),
+                ("records", C.c_int64), ("holes", C.c_int64), ("slots", C.c_int64),
+                ("depth", C.c_int32), ("reserved", C.c_int32), ("errors", C.c_int64),
+                ("first_error_kind", C.c_int32), ("reserved2", C.c_int32), ("first_error_node", C.c_int64),
+                ("hash_nodes", C.c_uint64), ("hash_records", C.c_uint64), ("hash_parents", C.c_uint64)]
+
+
 class sp_bvh_check(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32),
                 ("nodes", C.c_int64), ("leaves", C.c_int64), ("slots", C.c_int64),
@@ -203,6 +221,8 @@ SIGNATURES = {
     "sp_scene_bvh_check": (C.c_int, [C.c_void_p, C.POINTER(sp_bvh_check)]),
     "sp_scene_bvh_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.POINTER(sp_build_params),
                                            C.POINTER(sp_bvh_check)]),
+    "sp_scene_wide_check": (C.c_int, [C.c_void_p, C.POINTER(sp_wide_check)]),
+    "sp_scene_wide_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.c_void_p, C.POINTER(sp_wide_check)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

@@ -174,36 +174,14 @@ __global__ __launch_bounds__(BLOCK) void lb_fit_pass(Node* __restrict__ nodes, u
     if (threadIdx.x == 0 && total) atomicAdd(&fitted[pass], (uint32_t)total);
 }
 
-// the build's device memory: freed when the build returns, whichever way
-struct Arena {
-    std::vector<void*> ptrs;
-    size_t             bytes = 0, peak = 0;
-    ~Arena()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** out, size_t count)
-    {
-        void*            p = nullptr;
-        const size_t     b = std::max<size_t>(count * sizeof(T), 16);
-        const hipError_t e = hipMalloc(&p, b);
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        bytes += b;
-        peak = std::max(peak, bytes);
-        *out = static_cast<T*>(p);
-        return hipSuccess;
-    }
-};
-
 uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) / BLOCK); }
 
 } // namespace
 
 int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, sph::Bvh& out, BuildStats& st, std::string& err,
-                      bool timed)
+                      bool timed, DeviceTree* keep)
 {
+    if (keep) *keep = DeviceTree{};
     out = sph::Bvh{};
     st  = BuildStats{};
     const size_t n = bounds.size();
@@ -321,6 +299,17 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
         done += now;
     }
     lap(st.ms_fit);
+    if (keep) {
+        mem.release(d_nodes);
+        mem.release(d_order);
+        keep->nodes   = d_nodes;
+        keep->order   = d_order;
+        keep->n_nodes = m;
+        keep->n_slots = un;
+        st.peak_bytes = mem.peak;
+        out.max_depth = st.passes + 1;
+        return SP_OK;
+    }
 
     out.nodes.resize(m);
     out.prim_order.resize(n);

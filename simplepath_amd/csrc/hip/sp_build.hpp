@@ -4,6 +4,9 @@
 
 #include "../host/sp_host.hpp"
 
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -15,10 +18,44 @@ struct BuildStats {
     size_t peak_bytes = 0; // device scratch alive at once, the sort's and the scan's temporaries included
 };
 
+// a build's device scratch (sp_build.hip, sp_finish.hip): freed when the build returns, whichever way
+struct Arena {
+    std::vector<void*> ptrs;
+    size_t             bytes = 0, peak = 0;
+    ~Arena()
+    {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t get(T** out, size_t count)
+    {
+        void*            p = nullptr;
+        const size_t     b = std::max<size_t>(count * sizeof(T), 16);
+        const hipError_t e = hipMalloc(&p, b);
+        if (e != hipSuccess) return e;
+        ptrs.push_back(p);
+        bytes += b;
+        peak = std::max(peak, bytes);
+        *out = static_cast<T*>(p);
+        return hipSuccess;
+    }
+    // hands a block over to the caller, who frees it
+    void release(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
+};
+
+// A tree that stays on the device (the device finish works on it there): the caller frees both
+// blocks with hipFree.
+struct DeviceTree {
+    void *   nodes = nullptr, *order = nullptr; // sph::BvhNode[n_nodes]; uint32_t[n_slots], slot -> primitive
+    uint32_t n_nodes = 0, n_slots = 0;
+};
+
 // Builds on the current device.  SP_OK, or SP_ERR_HIP with `err` set (nothing stays allocated and
 // HIP's error state is cleared; there is no host fall-back).  `timed` waits for the device after
-// each stage so the stats hold stage times.
+// each stage so the stats hold stage times.  With `keep` and more than one primitive the tree is
+// not copied back: `keep` takes the device blocks, and `out` holds only max_depth, which is the
+// fit's pass count plus one -- a node is fitted in the pass that equals its height.
 int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, sph::Bvh& out, BuildStats& st,
-                      std::string& err, bool timed);
+                      std::string& err, bool timed, DeviceTree* keep = nullptr);
 
 } // namespace spb

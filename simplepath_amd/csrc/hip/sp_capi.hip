@@ -5,6 +5,7 @@
 #include "sp_launch.hpp"
 #include "sp_plan.hpp"
 #include "sp_build.hpp"
+#include "sp_finish.hpp"
 #include "../host/sp_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -103,10 +104,12 @@ struct UploadOpts {
     bool wide_closest = true;  // closest-hit queries on the 8-wide BVH as well
     int  sah_leaf   = 4;
     int  builder    = SP_BUILDER_HOST; // SP_BUILDER_HOST or SP_BUILDER_DEVICE (sp_build_params, resolved)
+    int  finish     = SP_FINISH_HOST;  // SP_FINISH_HOST or SP_FINISH_DEVICE (sp_build_params_ex, resolved)
     bool operator==(const UploadOpts& o) const
     {
         return bvh_mode == o.bvh_mode && stackless == o.stackless && stack_max == o.stack_max && wide == o.wide &&
-               env_guide == o.env_guide && sah_leaf == o.sah_leaf && wide_closest == o.wide_closest && builder == o.builder;
+               env_guide == o.env_guide && sah_leaf == o.sah_leaf && wide_closest == o.wide_closest && builder == o.builder &&
+               finish == o.finish;
     }
 };
 
@@ -139,13 +142,24 @@ int resolve_upload(const sp_upload_params* p, UploadOpts& o)
 }
 
 // The builder of an upload (sp_build_params): NULL or AUTO is the host builders, unless the test
-// hook SP_DEVICE_BUILD=1 asks for the device builder on a SAH-mode upload.
+// hook SP_DEVICE_BUILD=1 asks for the device builder on a SAH-mode upload.  The finish
+// (sp_build_params_ex, told apart by struct_size): AUTO follows the builder unless the test hook
+// SP_DEVICE_FINISH=0|1 decides.
 int resolve_build(const sp_build_params* b, UploadOpts& o)
 {
-    int builder = SP_BUILDER_AUTO;
+    int builder = SP_BUILDER_AUTO, finish = SP_FINISH_AUTO;
     if (b) {
-        if (b->struct_size != sizeof(sp_build_params)) return fail(SP_ERR_ARG, "sp_build_params.struct_size is not a known size");
+        if (b->struct_size != sizeof(sp_build_params) && b->struct_size != sizeof(sp_build_params_ex))
+            return fail(SP_ERR_ARG, "sp_build_params.struct_size is not a known size");
         if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(SP_ERR_ARG, "sp_build_params.reserved must be 0");
+        if (b->struct_size == sizeof(sp_build_params_ex)) {
+            const sp_build_params_ex* x = reinterpret_cast<const sp_build_params_ex*>(b);
+            if (x->reserved2[0] != 0 || x->reserved2[1] != 0 || x->reserved2[2] != 0)
+                return fail(SP_ERR_ARG, "sp_build_params_ex.reserved2 must be 0");
+            if (x->finish != SP_FINISH_AUTO && x->finish != SP_FINISH_HOST && x->finish != SP_FINISH_DEVICE)
+                return fail(SP_ERR_ARG, "finish must be SP_FINISH_AUTO, SP_FINISH_HOST or SP_FINISH_DEVICE");
+            finish = x->finish;
+        }
         if (b->builder != SP_BUILDER_AUTO && b->builder != SP_BUILDER_HOST && b->builder != SP_BUILDER_DEVICE)
             return fail(SP_ERR_ARG, "builder must be SP_BUILDER_AUTO, SP_BUILDER_HOST or SP_BUILDER_DEVICE");
         builder = b->builder;
@@ -155,6 +169,14 @@ int resolve_build(const sp_build_params* b, UploadOpts& o)
     if (builder == SP_BUILDER_AUTO)
         builder = (o.bvh_mode == 0 && env_int("SP_DEVICE_BUILD", 0) == 1) ? SP_BUILDER_DEVICE : SP_BUILDER_HOST;
     o.builder = builder;
+    if (finish == SP_FINISH_DEVICE && o.bvh_mode == 1)
+        return fail(SP_ERR_ARG, "the device finish cannot serve the reference order (bvh_mode 1)");
+    if (finish == SP_FINISH_AUTO) {
+        const int hook = env_int("SP_DEVICE_FINISH", -1);
+        const bool dev = hook == 0 ? false : (hook == 1 ? true : builder == SP_BUILDER_DEVICE);
+        finish         = (dev && o.bvh_mode == 0) ? SP_FINISH_DEVICE : SP_FINISH_HOST;
+    }
+    o.finish = finish;
     return SP_OK;
 }
 
@@ -179,6 +201,7 @@ std::vector<sph::PrimBounds> bounded_prims(const sph::Scene& h, std::vector<int3
 struct UploadTiming {
     double          ms_bounds = 0, ms_bvh = 0, ms_wide = 0, ms_pack = 0, ms_copies = 0;
     spb::BuildStats dev{};
+    spf::FinishStats fin{};
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void lap(double& ms)
     {
@@ -191,8 +214,10 @@ struct UploadTiming {
 // The BVH over the bounded part: the reference's median split (bvh_mode 1,
 // shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder -- built on the
 // current device when `on_device`, else by its host restatement (the same tree).
+// With `keep` (device builder and device finish) the tree stays on the device: the Bvh returned has
+// only its depth, and `keep` the blocks.
 sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int32_t>& prims, size_t& part, bool on_device = false,
-                      UploadTiming* tm = nullptr, std::vector<sph::PrimBounds>* bounds_out = nullptr)
+                      UploadTiming* tm = nullptr, std::vector<sph::PrimBounds>* bounds_out = nullptr, spb::DeviceTree* keep = nullptr)
 {
     std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
     if (tm) tm->lap(tm->ms_bounds);
@@ -203,7 +228,7 @@ sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int3
     else {
         spb::BuildStats st;
         std::string     err;
-        const int       rc = spb::build_lbvh_device(bounds, o.sah_leaf, bvh, st, err, tm != nullptr);
+        const int       rc = spb::build_lbvh_device(bounds, o.sah_leaf, bvh, st, err, tm != nullptr, keep);
         if (rc != SP_OK) throw sph::SpError(rc, err);
         if (tm) tm->dev = st;
     }
@@ -230,6 +255,30 @@ sph::Bvh light_bvh(const sph::Scene& h, std::vector<int32_t>& lids, size_t& lpar
     std::vector<sph::PrimBounds> lb;
     for (size_t i = 0; i < lpart; ++i) lb.push_back(sphere_bounds(from_desc(h.lights[lids[i]].object_to_world)));
     return sph::build_bvh_reference(lb);
+}
+
+// Per-slot primitive records in the binary tree's order: slot_code, and slot_tri = 3 x float4 with
+// the triangle's vertices (zero for other primitives) and the code in p0.w, so a triangle test is
+// three 16-byte fetches
+void pack_records(const sph::Scene& h, const std::vector<int32_t>& prims, const std::vector<int32_t>& prim_order,
+                  std::vector<float4>& slot_tri, std::vector<uint32_t>& slot_code)
+{
+    slot_tri.assign(prim_order.size() * 3, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    slot_code.resize(prim_order.size());
+    for (size_t sl = 0; sl < prim_order.size(); ++sl) {
+        const int32_t p    = prims[prim_order[sl]];
+        const int     kind = h.prim_kind[p];
+        const int     idx  = h.prim_index[p];
+        slot_code[sl]      = code_of(kind, idx);
+        if (kind == SP_PRIM_TRIANGLE) {
+            for (int k = 0; k < 3; ++k) {
+                const spm::f3 v  = h.vertices[h.indices[3 * idx + k]];
+                slot_tri[3 * sl + k] = make_float4(v.x, v.y, v.z, 0.0f);
+            }
+        }
+        uint32_t code = slot_code[sl];
+        std::memcpy(&slot_tri[3 * sl].w, &code, 4);
+    }
 }
 
 // parent[i] of every node of a binary BVH (the root is its own parent)
@@ -402,6 +451,8 @@ struct sp_scene {
     spd::Scene           dev{};
     int                  geom_depth = 0, light_depth = 0;
     size_t               geom_nodes = 0, geom_slots = 0;
+    size_t               wide_records = 0, wide_slots = 0; // 8-wide BVH (0: none)
+    int                  wide_depth = 0;
     // One scene, many host threads (the reference's render() shares one Scene across N threads,
     // main.cpp:122-130): the render scratch is per scene, so calls are serialised -- on the
     // host by `mu`, and on the device by making each call's stream wait for the previous call's
@@ -857,7 +908,16 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     size_t               part = 0;
     UploadTiming         timing;
     UploadTiming*        tm   = std::getenv("SP_UPLOAD_TIMING") ? &timing : nullptr;
-    const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part, true, tm);
+    const bool           dev_finish = opts.finish == SP_FINISH_DEVICE;
+    spb::DeviceTree      dtree; // device builder + device finish: the binary tree never comes back
+    struct OrderGuard {         // its order is build scratch: freed after the finish, whichever way
+        spb::DeviceTree& t;
+        ~OrderGuard() { if (t.order) (void)hipFree(t.order); }
+    } order_guard{ dtree };
+    const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part, true, tm, nullptr, dev_finish ? &dtree : nullptr);
+    if (dtree.nodes) s->bufs.push_back(DevBuf{ dtree.nodes, (size_t)dtree.n_nodes * sizeof(sph::BvhNode) });
+    const size_t n_nodes = dtree.nodes ? dtree.n_nodes : bvh.nodes.size();
+    const size_t n_slots = dtree.nodes ? dtree.n_slots : bvh.prim_order.size();
     std::vector<spd::Shape> shapes;
     for (auto& sh : h.shapes) {
         spd::Shape x{};
@@ -870,23 +930,9 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     }
     std::vector<int32_t> unbounded;
     for (size_t i = part; i < prims.size(); ++i) unbounded.push_back(h.prim_index[prims[i]]);
-    std::vector<float4>   slot_tri(bvh.prim_order.size() * 3);
-    std::vector<uint32_t> slot_code(bvh.prim_order.size());
-    for (size_t sl = 0; sl < bvh.prim_order.size(); ++sl) {
-        const int32_t p    = prims[bvh.prim_order[sl]];
-        const int     kind = h.prim_kind[p];
-        const int     idx  = h.prim_index[p];
-        slot_code[sl]      = code_of(kind, idx);
-        if (kind == SP_PRIM_TRIANGLE) {
-            for (int k = 0; k < 3; ++k) {
-                const spm::f3 v  = h.vertices[h.indices[3 * idx + k]];
-                slot_tri[3 * sl + k] = make_float4(v.x, v.y, v.z, 0.0f);
-            }
-        }
-        // the primitive code rides in p0.w so a triangle test is three 16-byte fetches
-        uint32_t code = slot_code[sl];
-        std::memcpy(&slot_tri[3 * sl].w, &code, 4);
-    }
+    std::vector<float4>   slot_tri;
+    std::vector<uint32_t> slot_code;
+    if (!dev_finish) pack_records(h, prims, bvh.prim_order, slot_tri, slot_code);
     std::vector<spd::Node> nodes(bvh.nodes.size());
     static_assert(sizeof(spd::Node) == sizeof(sph::BvhNode), "node layout");
     std::memcpy(nodes.data(), bvh.nodes.data(), nodes.size() * sizeof(spd::Node));
@@ -918,7 +964,8 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     sph::WideBvh        wide;
     std::vector<float4> wslot_tri;
     if (tm) tm->lap(tm->ms_copies); // (lights: counted with the copies)
-    if (wide_enabled(opts) && !nodes.empty() && !stackless) {
+    const bool want_wide = wide_enabled(opts) && n_nodes != 0 && !stackless;
+    if (want_wide && !dev_finish) {
         wide = sph::build_wide(bvh);
         if (tm) tm->lap(tm->ms_wide);
         wslot_tri.resize(wide.slot_of.size() * 3);
@@ -941,8 +988,9 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     d.alpha2_1 = a2[1];
     d.n_unbounded = (int)unbounded.size();
     up(unbounded, &d.unbounded);
-    d.n_nodes = (int)nodes.size();
-    up(nodes, &d.nodes);
+    d.n_nodes = (int)n_nodes;
+    if (dtree.nodes) d.nodes = static_cast<const spd::Node*>(dtree.nodes);
+    else up(nodes, &d.nodes);
     d.wnodes    = nullptr;
     d.wslot_tri = nullptr;
     if (!wide.words.empty()) {
@@ -951,12 +999,59 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
         up(wn, &d.wnodes);
         up(wslot_tri, &d.wslot_tri);
     }
-    up(slot_tri, &d.slot_tri);
-    up(slot_code, &d.slot_code);
+    if (!dev_finish) {
+        up(slot_tri, &d.slot_tri);
+        up(slot_code, &d.slot_code);
+    }
     std::vector<float> nrm(h.normals.size() * 3);
     for (size_t i = 0; i < h.normals.size(); ++i) { nrm[3 * i] = h.normals[i].x; nrm[3 * i + 1] = h.normals[i].y; nrm[3 * i + 2] = h.normals[i].z; }
     up(nrm, &d.normals);
     up(h.indices, &d.indices);
+    size_t wide_records = wide.words.size() / 20, wide_slots = wide.slot_of.size();
+    int    wide_depth   = wide.depth;
+    d.parents           = nullptr;
+    if (dev_finish && rc2 == SP_OK) {
+        // the finish on the device (sp_finish.hip): the same arrays from the resident binary tree
+        if (tm) tm->lap(tm->ms_copies);
+        std::vector<uint32_t> codes(part);
+        for (size_t i = 0; i < part; ++i) codes[i] = code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]);
+        spf::FinishIn in;
+        in.d_nodes      = reinterpret_cast<const sph::BvhNode*>(d.nodes);
+        in.n_nodes      = (uint32_t)n_nodes;
+        in.d_order      = static_cast<const uint32_t*>(dtree.order);
+        in.h_order      = bvh.prim_order.data();
+        in.n_slots      = (uint32_t)n_slots;
+        in.h_codes      = codes.data();
+        in.n_prims      = (uint32_t)part;
+        in.h_verts      = h.vertices.data();
+        in.n_verts      = h.vertices.size();
+        in.d_indices    = d.indices;
+        in.n_indices    = h.indices.size();
+        in.want_wide    = want_wide;
+        in.want_parents = stackless;
+        spf::FinishOut   fo;
+        spf::FinishStats fs;
+        std::string      ferr;
+        const int        frc = spf::finish_device(in, fo, fs, ferr, tm != nullptr);
+        if (frc != SP_OK) throw sph::SpError(frc, ferr);
+        if (dtree.order) (void)hipFree(dtree.order);
+        dtree.order = nullptr;
+        if (tm) tm->fin = fs;
+        const std::pair<void*, size_t> got[] = { { fo.wnodes, fo.wnodes_bytes }, { fo.wslot_tri, fo.wslot_tri_bytes },
+                                                 { fo.slot_tri, fo.slot_tri_bytes }, { fo.slot_code, fo.slot_code_bytes },
+                                                 { fo.parents, fo.parents_bytes } };
+        for (const auto& g : got)
+            if (g.first) s->bufs.push_back(DevBuf{ g.first, g.second });
+        d.wnodes     = static_cast<const uint4*>(fo.wnodes);
+        d.wslot_tri  = static_cast<const float4*>(fo.wslot_tri);
+        d.slot_tri   = static_cast<const float4*>(fo.slot_tri);
+        d.slot_code  = static_cast<const uint32_t*>(fo.slot_code);
+        d.parents    = static_cast<const uint32_t*>(fo.parents);
+        wide_records = fo.records;
+        wide_slots   = fo.wide_slots;
+        wide_depth   = fo.depth;
+        if (tm) tm->lap(tm->ms_wide);
+    }
     up(h.tri_material, &d.tri_material);
     up(shapes, &d.shapes);
     d.n_lights = (int)lights.size();
@@ -1033,29 +1128,33 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     d.rsqrt_denorm = rc.denorm_result;
     s->geom_depth  = bvh.max_depth;
     s->light_depth = lbvh.max_depth;
-    s->geom_nodes  = nodes.size();
-    s->geom_slots  = slot_code.size();
+    s->geom_nodes  = n_nodes;
+    s->geom_slots  = n_slots;
+    s->wide_records = wide_records;
+    s->wide_slots   = wide_slots;
+    s->wide_depth   = wide_depth;
     // SAH scenes walk the 8-wide BVH for every query: any-hit since round 1 (shadow stage 0.82 ->
     // 0.53 ms), closest hit since round 3 with octant-ordered slots, near-first entry and group
     // distances (bunny 3110 -> 3200, lucy 2175 -> 2280 Mrays/s).  Its stack keeps a
     // distance per entry in the upper half.
     d.ordered     = bvh_mode == 1 ? 0 : 1; // reference order is part of the bit-exact contract
-    d.wide_closest = (opts.wide_closest && !wide.words.empty()) ? 1 : 0;
-    d.stack_depth  = stack_entries(bvh.max_depth, wide.depth, lbvh.max_depth, d.wide_closest != 0);
+    d.wide_closest = (opts.wide_closest && wide_records != 0) ? 1 : 0;
+    d.stack_depth  = stack_entries(bvh.max_depth, wide_depth, lbvh.max_depth, d.wide_closest != 0);
     d.stackless   = stackless ? 1 : 0;
     d.merge_queries = 1; // per render: SP_RENDER_PER_LANE_QUERIES clears it
-    d.parents       = nullptr;
     d.light_parents = nullptr;
     if (d.stackless) { // deeper than the LDS budget: parent links instead of a stack
-        std::vector<uint32_t> par  = parent_links(bvh.nodes);
         std::vector<uint32_t> lpar = parent_links(lbvh.nodes);
-        up(par, &d.parents);
+        if (!dev_finish) { // (the device finish has linked the geometry's)
+            std::vector<uint32_t> par = parent_links(bvh.nodes);
+            up(par, &d.parents);
+        }
         up(lpar, &d.light_parents);
         if (rc2 != SP_OK) return rc2;
         d.stack_depth = 0;
     }
     d.stack_words     = d.stack_depth;
-    d.any_stack_words = d.stackless ? 0 : std::max(wide.words.empty() ? bvh.max_depth : wide.depth, lbvh.max_depth) + 1;
+    d.any_stack_words = d.stackless ? 0 : std::max(wide_records == 0 ? bvh.max_depth : wide_depth, lbvh.max_depth) + 1;
     RenderScratch& r = s->scratch;
     SP_HIP(r.tile_counter.reserve(sizeof(int32_t)));
     SP_HIP(r.counters.reserve(8 * sizeof(unsigned long long)));
@@ -1070,10 +1169,15 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
                      "sp_upload_timing {\"builder\": \"%s\", \"bvh_mode\": %d, \"prims\": %zu, \"nodes\": %zu, \"depth\": %d, "
                      "\"stackless\": %d, \"bounds_ms\": %.3f, \"bvh_ms\": %.3f, \"wide_ms\": %.3f, \"pack_ms\": %.3f, \"copies_ms\": %.3f, "
                      "\"device\": {\"bounds_up_ms\": %.3f, \"codes_ms\": %.3f, \"sort_ms\": %.3f, \"hierarchy_ms\": %.3f, \"fit_ms\": %.3f, "
-                     "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}}\n",
-                     opts.builder == SP_BUILDER_DEVICE ? "device" : "host", opts.bvh_mode, bvh.prim_order.size(), bvh.nodes.size(),
+                     "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}, "
+                     "\"finish\": \"%s\", \"device_finish\": {\"inputs_up_ms\": %.3f, \"collapse_ms\": %.3f, \"sums_ms\": %.3f, "
+                     "\"bases_ms\": %.3f, \"emit_ms\": %.3f, \"pack_ms\": %.3f, \"parents_ms\": %.3f, \"levels\": %d, "
+                     "\"peak_scratch_bytes\": %zu}}\n",
+                     opts.builder == SP_BUILDER_DEVICE ? "device" : "host", opts.bvh_mode, n_slots, n_nodes,
                      bvh.max_depth, d.stackless, tm->ms_bounds, tm->ms_bvh, tm->ms_wide, tm->ms_pack, tm->ms_copies, b.ms_bounds_up,
-                     b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes);
+                     b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes,
+                     dev_finish ? "device" : "host", tm->fin.ms_inputs_up, tm->fin.ms_collapse, tm->fin.ms_sums, tm->fin.ms_bases,
+                     tm->fin.ms_emit, tm->fin.ms_pack, tm->fin.ms_parents, tm->fin.levels, tm->fin.peak_bytes);
     }
     return SP_OK;
 }
@@ -2562,6 +2666,128 @@ int sp_scene_bvh_check(sp_scene* s, sp_bvh_check* out)
         return fill_check(bvh, bounds, s->opts, out);
     } catch (const std::exception& e) {
         return fail(SP_ERR_UNSUPPORTED, std::string("BVH check failed: ") + e.what());
+    }
+}
+
+namespace {
+// slot -> index into `by` of the entry with that code; entries sharing a code (a scene may list a
+// primitive twice) are handed out in order, -1 when none is left
+void match_codes(const std::vector<uint32_t>& codes, const std::vector<uint32_t>& by, std::vector<int32_t>& out)
+{
+    std::vector<std::pair<uint32_t, int32_t>> by_code(by.size());
+    for (size_t i = 0; i < by.size(); ++i) by_code[i] = { by[i], (int32_t)i };
+    std::sort(by_code.begin(), by_code.end());
+    std::vector<uint8_t> taken(by.size(), 0);
+    out.assign(codes.size(), -1);
+    for (size_t sl = 0; sl < codes.size(); ++sl) {
+        auto it = std::lower_bound(by_code.begin(), by_code.end(), std::make_pair(codes[sl], (int32_t)0));
+        while (it != by_code.end() && it->first == codes[sl] && taken[(size_t)(it - by_code.begin())]) ++it;
+        if (it == by_code.end() || it->first != codes[sl]) continue;
+        taken[(size_t)(it - by_code.begin())] = 1;
+        out[sl] = it->second;
+    }
+}
+
+// sp_wide_check from the arrays a render reads
+int fill_wide_check(const sph::WideBvh& wide, const std::vector<int32_t>& prim_order, const std::vector<sph::PrimBounds>& bounds,
+                    const std::vector<float4>& slot_tri, const std::vector<uint32_t>& slot_code, const std::vector<float4>& wslot_tri,
+                    const std::vector<uint32_t>& parents, bool stackless, int finish, sp_wide_check* out)
+{
+    const uint32_t sz = out->struct_size;
+    *out              = sp_wide_check{};
+    out->struct_size  = sz;
+    out->finish       = finish;
+    if (!wide.words.empty()) {
+        const sph::WideCheck c = sph::check_wide(wide, prim_order, bounds);
+        out->records          = c.records;
+        out->holes            = c.holes;
+        out->slots            = c.slots;
+        out->depth            = c.depth;
+        out->errors           = c.errors;
+        out->first_error_kind = c.first_error_kind;
+        out->first_error_node = c.first_error_node;
+        out->hash_nodes       = c.hash_nodes;
+    }
+    uint64_t h = sph::fnv1a64(slot_tri.data(), slot_tri.size() * sizeof(float4));
+    h          = sph::fnv1a64(slot_code.data(), slot_code.size() * sizeof(uint32_t), h);
+    out->hash_records = sph::fnv1a64(wslot_tri.data(), wslot_tri.size() * sizeof(float4), h);
+    out->hash_parents = stackless ? sph::fnv1a64(parents.data(), parents.size() * sizeof(uint32_t)) : 0;
+    return SP_OK;
+}
+} // namespace
+
+int sp_scene_wide_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build, sp_wide_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_wide_check)) return fail(SP_ERR_ARG, "sp_wide_check.struct_size is not a known size");
+    UploadOpts opts;
+    if (int rc0 = resolve_upload(params, opts)) return rc0;
+    if (int rc0 = resolve_build(build, opts)) return rc0;
+    try {
+        const sph::Scene&            h = *s->host;
+        std::vector<int32_t>         prims, lids;
+        size_t                       part = 0, lpart = 0;
+        std::vector<sph::PrimBounds> bounds;
+        const sph::Bvh               bvh = geometry_bvh(h, opts, prims, part, false, nullptr, &bounds);
+        const bool stackless = stackless_for(opts, std::max(bvh.max_depth, light_bvh(h, lids, lpart).max_depth));
+        std::vector<float4>   slot_tri, wslot_tri;
+        std::vector<uint32_t> slot_code, parents;
+        pack_records(h, prims, bvh.prim_order, slot_tri, slot_code);
+        sph::WideBvh wide;
+        if (wide_enabled(opts) && !bvh.nodes.empty() && !stackless) {
+            wide = opts.finish == SP_FINISH_DEVICE ? sph::build_wide_levels(bvh) : sph::build_wide(bvh);
+            wslot_tri.resize(wide.slot_of.size() * 3);
+            for (size_t i = 0; i < wide.slot_of.size(); ++i)
+                for (int k = 0; k < 3; ++k) wslot_tri[3 * i + k] = slot_tri[3 * (size_t)wide.slot_of[i] + k];
+        }
+        if (stackless) parents = parent_links(bvh.nodes);
+        return fill_wide_check(wide, bvh.prim_order, bounds, slot_tri, slot_code, wslot_tri, parents, stackless, opts.finish, out);
+    } catch (const sph::SpError& e) {
+        return fail(e.code, e.what());
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
+    }
+}
+
+int sp_scene_wide_check(sp_scene* s, sp_wide_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_wide_check)) return fail(SP_ERR_ARG, "sp_wide_check.struct_size is not a known size");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
+    try {
+        SP_HIP(hipSetDevice(s->device));
+        SP_HIP(hipDeviceSynchronize()); // queued renders read these arrays; nothing writes them
+        auto down = [&](auto& vec, const void* src) -> hipError_t {
+            if (vec.empty()) return hipSuccess;
+            if (!src) return hipErrorInvalidValue;
+            return hipMemcpy(vec.data(), src, vec.size() * sizeof(vec[0]), hipMemcpyDeviceToHost);
+        };
+        const spd::Scene&     d = s->dev;
+        sph::WideBvh          wide;
+        std::vector<float4>   slot_tri(s->geom_slots * 3), wslot_tri(d.wnodes ? s->wide_slots * 3 : 0);
+        std::vector<uint32_t> slot_code(s->geom_slots), parents(d.stackless ? s->geom_nodes : 0);
+        wide.words.resize(d.wnodes ? s->wide_records * 20 : 0);
+        wide.depth = d.wnodes ? s->wide_depth : 0;
+        SP_HIP(down(wide.words, d.wnodes));
+        SP_HIP(down(slot_tri, d.slot_tri));
+        SP_HIP(down(wslot_tri, d.wslot_tri));
+        SP_HIP(down(slot_code, d.slot_code));
+        SP_HIP(down(parents, d.parents));
+        // slot -> bounded primitive and wide slot -> slot: each primitive's code (kind, index) names it
+        const sph::Scene&            h = *s->host;
+        std::vector<int32_t>         prims;
+        size_t                       part = 0;
+        std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
+        std::vector<uint32_t>        prim_codes(part), wcodes(wslot_tri.size() / 3);
+        for (size_t i = 0; i < part; ++i) prim_codes[i] = code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]);
+        for (size_t i = 0; i < wcodes.size(); ++i) std::memcpy(&wcodes[i], &wslot_tri[3 * i].w, 4);
+        std::vector<int32_t> prim_order;
+        match_codes(slot_code, prim_codes, prim_order);
+        match_codes(wcodes, slot_code, wide.slot_of);
+        return fill_wide_check(wide, prim_order, bounds, slot_tri, slot_code, wslot_tri, parents, d.stackless != 0, s->opts.finish, out);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("wide BVH check failed: ") + e.what());
     }
 }
 

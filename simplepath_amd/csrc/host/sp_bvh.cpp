@@ -7,6 +7,7 @@
 // SAH (Wald 2007) with the same node format; it changes only the visiting order.
 #include "sp_host.hpp"
 #include "../common/sp_lbvh.h"
+#include "../common/sp_wide.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -436,147 +437,32 @@ BvhCheck check_bvh(const Bvh& bvh, const std::vector<PrimBounds>& bounds, int ma
 }
 
 // ---------------------------------------------------------------- 8-wide collapse
+// The per-node work -- which children a wide node takes, their octant slots, the quantisation --
+// is spw::collapse (sp_wide.h), shared with the level-wise form below and the device finish.
 namespace {
-
-float node_area(const BvhNode& n)
-{
-    const float dx = n.hi[0] - n.lo[0], dy = n.hi[1] - n.lo[1], dz = n.hi[2] - n.lo[2];
-    if (!(dx >= 0.0f)) return 0.0f;
-    return 2.0f * (dx * dy + dy * dz + dz * dx);
-}
 
 struct WideBuilder {
     const Bvh& b;
     WideBvh&   out;
 
-    bool is_leaf(uint32_t i) const { return (b.nodes[i].b & BVH_LEAF) != 0; }
-    uint32_t left(uint32_t i) const { return b.nodes[i].a & BVH_CHILD_MASK; }
-    uint32_t right(uint32_t i) const { return b.nodes[i].b; }
-
-    // Quantise one axis of the children onto origin p with the smallest power-of-two step that
-    // keeps every decoded box (fma(q, step, p), as the device decodes it) outside the exact one.
-    void quantise(const float* lo, const float* hi, int n, float p, float extent, uint8_t* qlo, uint8_t* qhi,
-                  uint8_t& ebyte)
-    {
-        int k = -126;
-        if (extent > 0.0f) {
-            int e2;
-            std::frexp(extent / 254.0f, &e2); // extent/254 < 2^e2
-            k = std::max(e2, -126);
-        }
-        for (;; ++k) {
-            const float step = std::ldexp(1.0f, k);
-            bool        ok   = true;
-            for (int c = 0; c < n && ok; ++c) {
-                float ql = std::floor((lo[c] - p) / step);
-                ql       = std::min(std::max(ql, 0.0f), 255.0f);
-                while (ql > 0.0f && std::fma(ql, step, p) > lo[c]) ql -= 1.0f;
-                float qh = std::ceil((hi[c] - p) / step);
-                qh       = std::min(std::max(qh, 0.0f), 255.0f);
-                while (qh < 255.0f && std::fma(qh, step, p) < hi[c]) qh += 1.0f;
-                if (std::fma(ql, step, p) > lo[c] || std::fma(qh, step, p) < hi[c]) ok = false;
-                qlo[c] = (uint8_t)ql;
-                qhi[c] = (uint8_t)qh;
-            }
-            if (ok) {
-                ebyte = (uint8_t)(k + 127);
-                return;
-            }
-            if (k >= 127) throw std::runtime_error("wide BVH: cannot quantise child boxes");
-        }
-    }
-
     void emit(uint32_t wi, uint32_t bi, int depth)
     {
         out.depth = std::max(out.depth, depth);
-        // collapse: open the internal child of largest area until 8 children
-        std::vector<uint32_t> kids;
-        if (is_leaf(bi)) kids.push_back(bi);
-        else { kids.push_back(left(bi)); kids.push_back(right(bi)); }
-        while (kids.size() < 8) {
-            int   best = -1;
-            float ba   = -1.0f;
-            for (size_t i = 0; i < kids.size(); ++i)
-                if (!is_leaf(kids[i]) && node_area(b.nodes[kids[i]]) > ba) { ba = node_area(b.nodes[kids[i]]); best = (int)i; }
-            if (best < 0) break;
-            const uint32_t n = kids[(size_t)best];
-            kids[(size_t)best] = left(n);
-            kids.insert(kids.begin() + best + 1, right(n));
-        }
-        // Slots by octant: slot s takes the child lying towards (+ on axis a iff bit a of s) from
-        // the node's centre, so a ray whose direction has sign bits o (bit a: d_a < 0) meets the
-        // children roughly near to far in the order slot ^ o = 0, 1, ... (sp_path.hpp key_mask).
-        // Greedy assignment of the largest projection first; inner child in slot s is node
-        // child_base + s (slots taken by leaves or empty leave holes).
-        const int n = (int)kids.size();
-        float     ulo[3], uhi[3], cen[8][3];
-        for (int a = 0; a < 3; ++a) { ulo[a] = INFINITY; uhi[a] = -INFINITY; }
-        for (int c = 0; c < n; ++c)
-            for (int a = 0; a < 3; ++a) {
-                ulo[a]    = std::min(ulo[a], b.nodes[kids[(size_t)c]].lo[a]);
-                uhi[a]    = std::max(uhi[a], b.nodes[kids[(size_t)c]].hi[a]);
-                cen[c][a] = 0.5f * (b.nodes[kids[(size_t)c]].lo[a] + b.nodes[kids[(size_t)c]].hi[a]);
-            }
-        int  slot_kid[8];
-        bool kid_done[8] = {};
-        for (int s = 0; s < 8; ++s) slot_kid[s] = -1;
-        for (int round = 0; round < n; ++round) {
-            int   bc = -1, bs = -1;
-            float best = -INFINITY;
-            for (int c = 0; c < n; ++c) {
-                if (kid_done[c]) continue;
-                for (int s = 0; s < 8; ++s) {
-                    if (slot_kid[s] >= 0) continue;
-                    float score = 0.0f;
-                    for (int a = 0; a < 3; ++a) score += ((s >> a) & 1 ? 1.0f : -1.0f) * (cen[c][a] - 0.5f * (ulo[a] + uhi[a]));
-                    if (bc < 0 || score > best) { best = score; bc = c; bs = s; } // NaN (empty box): any slot
-                }
-            }
-            slot_kid[bs] = bc;
-            kid_done[bc] = true;
-        }
-        float lo[3][8], hi[3][8];
-        for (int s = 0; s < 8; ++s)
-            for (int a = 0; a < 3; ++a) {
-                const int c = slot_kid[s] >= 0 ? slot_kid[s] : 0; // empty slots: any box (never tested)
-                lo[a][s]    = b.nodes[kids[(size_t)c]].lo[a];
-                hi[a][s]    = b.nodes[kids[(size_t)c]].hi[a];
-            }
-        uint8_t q[6][8] = {};
-        uint8_t eb[3];
-        for (int a = 0; a < 3; ++a) quantise(lo[a], hi[a], 8, ulo[a], uhi[a] - ulo[a], q[a], q[3 + a], eb[a]);
-        uint32_t imask = 0;
-        int      span  = 0; // child slots allocated: last inner slot + 1
-        for (int s = 0; s < 8; ++s)
-            if (slot_kid[s] >= 0 && !is_leaf(kids[(size_t)slot_kid[s]])) { imask |= 1u << s; span = s + 1; }
+        spw::Collapsed c;
+        const int      e = spw::collapse(b.nodes.data(), (uint32_t)b.nodes.size(), bi, c);
+        if (e != spw::OK) throw std::runtime_error(spw::error_text(e));
+        // inner child in slot s is node child_base + s (slots taken by leaves or empty leave holes)
         const uint32_t child_base = (uint32_t)(out.words.size() / 20);
-        out.words.resize(out.words.size() + 20 * (size_t)span);
+        out.words.resize(out.words.size() + 20 * (size_t)c.span);
         const uint32_t leaf_base = (uint32_t)out.slot_of.size();
-        uint8_t        meta[8]   = {};
-        for (int s = 0; s < 8; ++s) {
-            if (slot_kid[s] < 0 || ((imask >> s) & 1u)) continue;
-            const BvhNode& lf  = b.nodes[kids[(size_t)slot_kid[s]]];
-            const uint32_t cnt = lf.b & ~BVH_LEAF;
-            const uint32_t off = (uint32_t)out.slot_of.size() - leaf_base;
-            if (cnt == 0 || cnt > 7 || off > 31) throw std::runtime_error("wide BVH: leaf does not fit a meta byte");
-            meta[s] = (uint8_t)(cnt << 5 | off);
-            for (uint32_t j = 0; j < cnt; ++j) out.slot_of.push_back((int32_t)(lf.a + j));
-        }
+        out.slot_of.resize(out.slot_of.size() + c.own);
+        spw::write_slots(b.nodes.data(), c, leaf_base, out.slot_of.data());
         uint32_t* w = &out.words[(size_t)wi * 20];
-        std::memcpy(&w[0], &ulo[0], 4);
-        std::memcpy(&w[1], &ulo[1], 4);
-        std::memcpy(&w[2], &ulo[2], 4);
-        w[3] = (uint32_t)eb[0] | (uint32_t)eb[1] << 8 | (uint32_t)eb[2] << 16 | imask << 24;
+        std::memcpy(w, c.w, sizeof c.w);
         w[4] = child_base;
         w[5] = leaf_base;
-        w[6] = (uint32_t)meta[0] | (uint32_t)meta[1] << 8 | (uint32_t)meta[2] << 16 | (uint32_t)meta[3] << 24;
-        w[7] = (uint32_t)meta[4] | (uint32_t)meta[5] << 8 | (uint32_t)meta[6] << 16 | (uint32_t)meta[7] << 24;
-        for (int r = 0; r < 6; ++r)
-            for (int h = 0; h < 2; ++h)
-                w[8 + 2 * r + h] = (uint32_t)q[r][4 * h] | (uint32_t)q[r][4 * h + 1] << 8 | (uint32_t)q[r][4 * h + 2] << 16 |
-                                   (uint32_t)q[r][4 * h + 3] << 24;
         for (int s = 0; s < 8; ++s)
-            if ((imask >> s) & 1u) emit(child_base + (uint32_t)s, kids[(size_t)slot_kid[s]], depth + 1);
+            if ((c.imask >> s) & 1u) emit(child_base + (uint32_t)s, c.kid[s], depth + 1);
     }
 };
 
@@ -593,6 +479,234 @@ WideBvh build_wide(const Bvh& bvh)
     if (std::getenv("SP_WIDE_STATS"))
         std::fprintf(stderr, "wide BVH: %zu node records, %zu leaf slots, depth %d\n", out.words.size() / 20, out.slot_of.size(), out.depth);
     return out;
+}
+
+// ------------------------------------------------------------------ level-wise collapse
+// build_wide numbers records (child_base) and slots (leaf_base) with running counters in
+// pre-order.  Both have a closed form in the subtree sums N(v) = span(v) + sum N(c) and
+// L(v) = own(v) + sum L(c) over the inner children c in slot order: the k-th of them has
+// child_base(v) + span(v) + sum_{j<k} N(c_j) and leaf_base(v) + own(v) + sum_{j<k} L(c_j), and
+// its record at child_base(v) + slot.  So the levels can be worked one after another.
+WideBvh build_wide_levels(const Bvh& bvh)
+{
+    WideBvh out;
+    if (bvh.nodes.empty()) return out;
+    struct Item {
+        uint32_t root, record;      // binary root; final record index (set top-down)
+        uint32_t first_child;       // index of its first inner child in the next level's list
+        uint32_t n_sub, l_sub;      // N, L
+        uint32_t child_base, leaf_base;
+        spw::Collapsed c;
+    };
+    const BvhNode*                 nodes = bvh.nodes.data();
+    std::vector<std::vector<Item>> levels;
+    // 1. top-down: collapse; count, exclusive scan, scatter
+    {
+        Item root{};
+        root.root = 0;
+        levels.push_back({ root });
+    }
+    size_t collapsed = 0;
+    for (size_t l = 0;; ++l) {
+        std::vector<Item>& cur = levels[l];
+        std::vector<uint32_t> count(cur.size());
+        for (size_t i = 0; i < cur.size(); ++i) {
+            const int e = spw::collapse(nodes, (uint32_t)bvh.nodes.size(), cur[i].root, cur[i].c);
+            if (e != spw::OK) throw std::runtime_error(spw::error_text(e));
+            count[i] = (uint32_t)__builtin_popcount(cur[i].c.imask);
+        }
+        collapsed += cur.size();
+        if (collapsed > bvh.nodes.size()) throw std::runtime_error(spw::error_text(spw::ERR_LINKS));
+        uint32_t total = 0;
+        for (size_t i = 0; i < cur.size(); ++i) { cur[i].first_child = total; total += count[i]; }
+        if (total == 0) break;
+        if (levels.size() >= (size_t)spw::MAX_LEVELS) throw std::runtime_error(spw::error_text(spw::ERR_LEVELS));
+        std::vector<Item> next(total, Item{});
+        for (size_t i = 0; i < cur.size(); ++i) {
+            uint32_t k = cur[i].first_child;
+            for (int s = 0; s < 8; ++s)
+                if ((cur[i].c.imask >> s) & 1u) next[k++].root = cur[i].c.kid[s];
+        }
+        levels.push_back(std::move(next)); // (cur is dangling from here)
+    }
+    out.depth = (int)levels.size();
+    // 2. bottom-up: subtree sums
+    for (size_t l = levels.size(); l-- > 0;)
+        for (Item& v : levels[l]) {
+            uint64_t n = (uint64_t)v.c.span, ls = v.c.own;
+            uint32_t k = v.first_child;
+            for (int s = 0; s < 8; ++s)
+                if ((v.c.imask >> s) & 1u) { n += levels[l + 1][k].n_sub; ls += levels[l + 1][k].l_sub; ++k; }
+            if (n + 1 >= spw::MAX_RECORDS) throw std::runtime_error(spw::error_text(spw::ERR_RECORDS));
+            v.n_sub = (uint32_t)n;
+            v.l_sub = (uint32_t)ls;
+        }
+    // 3. top-down: bases
+    levels[0][0].record     = 0;
+    levels[0][0].child_base = 1;
+    levels[0][0].leaf_base  = 0;
+    for (size_t l = 0; l + 1 < levels.size(); ++l)
+        for (const Item& v : levels[l]) {
+            uint32_t cb = v.child_base + (uint32_t)v.c.span, lb = v.leaf_base + v.c.own, k = v.first_child;
+            for (int s = 0; s < 8; ++s) {
+                if (!((v.c.imask >> s) & 1u)) continue;
+                Item& c      = levels[l + 1][k++];
+                c.record     = v.child_base + (uint32_t)s;
+                c.child_base = cb;
+                c.leaf_base  = lb;
+                cb += c.n_sub;
+                lb += c.l_sub;
+            }
+        }
+    // 4. records and slots at their final places; holes stay zero
+    out.words.assign(20 * (size_t)(1u + levels[0][0].n_sub), 0u);
+    out.slot_of.assign(levels[0][0].l_sub, 0);
+    for (const auto& level : levels)
+        for (const Item& v : level) {
+            uint32_t* w = &out.words[20 * (size_t)v.record];
+            std::memcpy(w, v.c.w, sizeof v.c.w);
+            w[4] = v.child_base;
+            w[5] = v.leaf_base;
+            spw::write_slots(nodes, v.c, v.leaf_base, out.slot_of.data());
+        }
+    return out;
+}
+
+// ------------------------------------------------------------------------- wide checker
+uint64_t fnv1a64(const void* p, size_t bytes, uint64_t h)
+{
+    const unsigned char* c = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 0x100000001b3ull; }
+    return h;
+}
+
+WideCheck check_wide(const WideBvh& wide, const std::vector<int32_t>& prim_order, const std::vector<PrimBounds>& bounds)
+{
+    WideCheck r;
+    const std::vector<uint32_t>& W = wide.words;
+    const size_t nrec = W.size() / 20, nslots = wide.slot_of.size();
+    r.records = (int64_t)nrec;
+    r.slots   = (int64_t)nslots;
+    auto bad = [&](int kind, int64_t node) {
+        if (r.errors++ == 0) { r.first_error_kind = kind; r.first_error_node = node; }
+    };
+    if (W.empty()) {
+        if (nslots != 0) bad(WIDE_ERR_SLOT_PARTITION, -1);
+        if (wide.depth != 0) bad(WIDE_ERR_DEPTH, -1);
+        return r;
+    }
+    r.hash_nodes = fnv1a64(W.data(), W.size() * 4);
+    // the wide slots name every binary slot once
+    bool slots_ok = nslots == prim_order.size();
+    if (!slots_ok) bad(WIDE_ERR_RECORDS, -1);
+    {
+        std::vector<uint8_t> seen(prim_order.size(), 0);
+        for (size_t i = 0; i < nslots; ++i) {
+            const int32_t b = wide.slot_of[i];
+            if (b < 0 || (size_t)b >= seen.size() || seen[(size_t)b]++) { bad(WIDE_ERR_RECORDS, (int64_t)i); slots_ok = false; }
+        }
+    }
+    // 0 unseen, 1 reached, 2 inside a reached node's span
+    std::vector<uint8_t> state(nrec, 0), covered(nslots, 0);
+    state[0] = 2;
+    struct Frame {
+        uint32_t rec;
+        int      depth, slot;   // next slot to look at
+        int      from;          // the parent frame's slot this one hangs in
+        Box      acc;           // union of what lies beneath the slot being worked
+    };
+    auto decoded_outside = [&](const uint32_t* w, int s, const Box& u) {
+        for (int a = 0; a < 3; ++a) {
+            float origin, step;
+            std::memcpy(&origin, &w[a], 4);
+            const uint32_t sb = ((w[3] >> (8 * a)) & 0xffu) << 23;
+            std::memcpy(&step, &sb, 4);
+            const uint32_t ql = (w[8 + 2 * a + s / 4] >> (8 * (s % 4))) & 0xffu;
+            const uint32_t qh = (w[8 + 2 * (3 + a) + s / 4] >> (8 * (s % 4))) & 0xffu;
+            const float    dlo = std::fma((float)ql, step, origin), dhi = std::fma((float)qh, step, origin);
+            if (u.lo[a] < dlo || u.hi[a] > dhi) return true;
+        }
+        return false;
+    };
+    auto merge_box = [](Box& into, const Box& b) {
+        for (int a = 0; a < 3; ++a) {
+            into.lo[a] = spm::sse_min(into.lo[a], b.lo[a]);
+            into.hi[a] = spm::sse_max(into.hi[a], b.hi[a]);
+        }
+    };
+    std::vector<Frame> stack;
+    std::vector<Box>   total; // per frame: union of the whole node
+    auto enter = [&](uint32_t rec, int depth, int from) {
+        stack.push_back(Frame{ rec, depth, 0, from, empty_box() });
+        total.push_back(empty_box());
+        r.depth = std::max(r.depth, depth);
+        const uint32_t* w = &W[20 * (size_t)rec];
+        bool            zero = true;
+        for (int i = 0; i < 20; ++i) zero = zero && w[i] == 0u;
+        if (zero) bad(WIDE_ERR_HOLE, rec); // an imask names a hole
+        const uint32_t imask = w[3] >> 24;
+        int            span  = 0;
+        for (int s = 0; s < 8; ++s)
+            if ((imask >> s) & 1u) span = s + 1;
+        for (int s = 0; s < span; ++s)
+            if ((uint64_t)w[4] + (uint32_t)s < nrec && state[w[4] + (uint32_t)s] == 0) state[w[4] + (uint32_t)s] = 2;
+    };
+    state[0] = 1;
+    enter(0, 1, -1);
+    while (!stack.empty()) {
+        Frame&          f = stack.back();
+        const uint32_t* w = &W[20 * (size_t)f.rec];
+        if (f.slot == 8) { // done: hand the union up
+            const Box  mine = total.back();
+            const int  from = f.from;
+            stack.pop_back();
+            total.pop_back();
+            if (!stack.empty()) {
+                const uint32_t* pw = &W[20 * (size_t)stack.back().rec];
+                if (decoded_outside(pw, from, mine)) bad(WIDE_ERR_BOX, stack.back().rec);
+                merge_box(total.back(), mine);
+            }
+            continue;
+        }
+        const int      s     = f.slot++;
+        const uint32_t imask = w[3] >> 24;
+        const uint32_t meta  = (w[6 + s / 4] >> (8 * (s % 4))) & 0xffu;
+        if ((imask >> s) & 1u) {
+            const uint64_t c = (uint64_t)w[4] + (uint32_t)s;
+            if (c >= nrec) { bad(WIDE_ERR_CHILD_RANGE, f.rec); continue; }
+            if (state[c] == 1) { bad(WIDE_ERR_VISITED_TWICE, (int64_t)c); continue; }
+            state[c] = 1;
+            if (meta != 0) bad(WIDE_ERR_META, f.rec);
+            enter((uint32_t)c, f.depth + 1, s); // (f is dangling from here)
+            continue;
+        }
+        if (meta == 0) continue; // empty slot
+        const uint32_t cnt = meta >> 5, off = meta & 31u; // (cnt <= 7 and off <= 31 by construction of the byte)
+        if (cnt == 0) { bad(WIDE_ERR_META, f.rec); continue; }
+        if ((uint64_t)w[5] + off + cnt > nslots) { bad(WIDE_ERR_SLOT_PARTITION, f.rec); continue; }
+        Box u = empty_box();
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const size_t ws = (size_t)w[5] + off + j;
+            if (covered[ws]++) bad(WIDE_ERR_SLOT_PARTITION, f.rec);
+            if (!slots_ok) continue;
+            const int32_t p = prim_order[(size_t)wide.slot_of[ws]];
+            if (p < 0 || (size_t)p >= bounds.size()) continue; // (the binary checker reports the order)
+            u = merge(u, bounds[(size_t)p]);
+        }
+        if (slots_ok && decoded_outside(w, s, u)) bad(WIDE_ERR_BOX, f.rec);
+        merge_box(total.back(), u);
+    }
+    for (size_t i = 0; i < nrec; ++i) {
+        if (state[i] == 1) continue;
+        if (state[i] == 0) { bad(WIDE_ERR_UNREACHABLE, (int64_t)i); continue; }
+        ++r.holes;
+        for (int k = 0; k < 20; ++k)
+            if (W[20 * i + (size_t)k] != 0u) { bad(WIDE_ERR_HOLE, (int64_t)i); break; }
+    }
+    for (size_t s = 0; s < nslots; ++s)
+        if (!covered[s]) bad(WIDE_ERR_SLOT_PARTITION, -1);
+    if (r.depth != wide.depth) bad(WIDE_ERR_DEPTH, -1);
+    return r;
 }
 
 } // namespace sph

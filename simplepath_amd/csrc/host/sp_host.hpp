@@ -206,6 +206,28 @@ struct WideBvh {
     int                   depth = 0;
 };
 WideBvh build_wide(const Bvh& bvh);
+// The same collapse level by level, the host restatement of the device finish
+// (sp_finish.hip): collapse top-down one level at a time, subtree sums bottom-up, bases top-down,
+// then every record at its final index.  Equal to build_wide word for word.
+WideBvh build_wide_levels(const Bvh& bvh);
+
+// Structural check of an 8-wide BVH against the binary tree's primitive order and the primitive
+// bounds (sp_wide_check): what is wrong is counted in `errors`, the first finding kept.
+enum WideError {
+    WIDE_ERR_NONE = 0, WIDE_ERR_CHILD_RANGE = 1, WIDE_ERR_VISITED_TWICE = 2, WIDE_ERR_UNREACHABLE = 3, WIDE_ERR_HOLE = 4,
+    WIDE_ERR_META = 5, WIDE_ERR_SLOT_PARTITION = 6, WIDE_ERR_RECORDS = 7, WIDE_ERR_BOX = 8, WIDE_ERR_DEPTH = 9
+};
+struct WideCheck {
+    int64_t  records = 0, holes = 0, slots = 0;
+    int      depth = 0;
+    int64_t  errors = 0;
+    int      first_error_kind = WIDE_ERR_NONE;
+    int64_t  first_error_node = -1;
+    uint64_t hash_nodes = 0; // FNV-1a 64 over the words (0 when there are none)
+};
+// prim_order: binary slot -> bounded primitive (-1: unknown); wide.slot_of: wide slot -> binary slot
+WideCheck check_wide(const WideBvh& wide, const std::vector<int32_t>& prim_order, const std::vector<PrimBounds>& bounds);
+uint64_t  fnv1a64(const void* p, size_t bytes, uint64_t h = 0xcbf29ce484222325ull);
 
 // libstdc++ std::partition on a bidirectional range, returning the split point.
 template <typename T, typename Pred>

@@ -2,12 +2,15 @@
 """Wall time of one scene upload, stage by stage, for the host and the device BVH builder.
 
     python tools/upload_timing.py --scene bunny --scene lucy --builders host,device --repeat 2
+    python tools/upload_timing.py --scene lucy --builders host --finish device
 
 Each upload runs in a child process of its own (a fresh process: the library is loaded, the
 scene parsed, and one upload timed), with SP_UPLOAD_TIMING=1, under which the library prints its
 stage times: bounds, BVH build, 8-wide collapse, primitive-record packing, copies; and for the
 device build its own stages (bounds copy, codes, sort, hierarchy, fit passes, copy-back), the
-number of fit passes and the peak device scratch.  Builders alternate within a repeat.  One JSON
+number of fit passes and the peak device scratch; and for the device finish (--finish device, or
+"auto" with the device builder) its stages (inputs copy, collapse levels, sums, bases, emit,
+packing, parents), the level count and its peak scratch.  Builders alternate within a repeat.  One JSON
 line per scene, builder and repeat goes to stdout."""
 import argparse
 import json
@@ -22,13 +25,16 @@ WRITERS = {"bunny": "write_bunny_scene", "bunny_scan": "write_bunny_scan_scene",
            "elf": "write_elf_scene", "spheres": "write_spheres_scene"}
 
 
-def child(path: str, builder: str, device: int) -> None:
+def child(path: str, builder: str, device: int, finish: str) -> None:
     sys.path.insert(0, ROOT)
     import simplepath_amd as sp
     t0 = time.perf_counter()
     scene = sp.Scene.from_file(path)
     t1 = time.perf_counter()
-    scene.upload(device=device, builder=builder)
+    if finish == "auto":  # (also what a library from before the device finish understands)
+        scene.upload(device=device, builder=builder)
+    else:
+        scene.upload(device=device, builder=builder, finish=finish)
     t2 = time.perf_counter()
     info = scene.bvh_info()
     print("upload_timing_child " + json.dumps({"parse_s": t1 - t0, "upload_s": t2 - t1, "bvh_info": info,
@@ -39,13 +45,14 @@ def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scene", action="append", default=None, help="a built-in scene name or a .sp file (repeatable)")
     ap.add_argument("--builders", default="host,device")
+    ap.add_argument("--finish", default="auto", choices=["auto", "host", "device"])
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--timeout", type=float, default=900.0, help="seconds per upload")
     ap.add_argument("--child", nargs=2, metavar=("PATH", "BUILDER"), help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        child(args.child[0], args.child[1], args.device)
+        child(args.child[0], args.child[1], args.device, args.finish)
         return 0
     sys.path.insert(0, ROOT)
     from simplepath_amd import scenes
@@ -55,9 +62,10 @@ def main() -> int:
         for rep in range(args.repeat):
             for builder in args.builders.split(","):
                 env = dict(os.environ, SP_UPLOAD_TIMING="1")
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--device", str(args.device), "--child", path, builder],
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--device", str(args.device), "--finish", args.finish,
+                                    "--child", path, builder],
                                    capture_output=True, text=True, env=env, timeout=args.timeout)
-                line = {"scene": os.path.basename(path), "builder": builder, "repeat": rep}
+                line = {"scene": os.path.basename(path), "builder": builder, "finish": args.finish, "repeat": rep}
                 if r.returncode != 0:
                     line["error"] = (r.stderr or r.stdout)[-400:]
                     print(json.dumps(line), flush=True)
