@@ -181,7 +181,7 @@ uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) 
 int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, sph::Bvh& out, BuildStats& st, std::string& err,
                       bool timed, DeviceTree* keep)
 {
-    if (keep) *keep = DeviceTree{};
+    if (keep) keep->reset();
     out = sph::Bvh{};
     st  = BuildStats{};
     const size_t n = bounds.size();

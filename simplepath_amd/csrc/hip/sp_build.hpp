@@ -43,11 +43,28 @@ struct Arena {
     void release(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
 };
 
-// A tree that stays on the device (the device finish works on it there): the caller frees both
-// blocks with hipFree.
+// A tree that stays on the device (the device finish works on it there).  It owns both blocks:
+// what the caller has not taken over (sp_scene::adopt nulls the pointer it takes) is freed with it.
 struct DeviceTree {
     void *   nodes = nullptr, *order = nullptr; // sph::BvhNode[n_nodes]; uint32_t[n_slots], slot -> primitive
     uint32_t n_nodes = 0, n_slots = 0;
+
+    DeviceTree() = default;
+    DeviceTree(const DeviceTree&) = delete;
+    DeviceTree& operator=(const DeviceTree&) = delete;
+    ~DeviceTree() { reset(); }
+    void free_order() // build scratch once the finish has read it
+    {
+        if (order) (void)hipFree(order);
+        order = nullptr;
+    }
+    void reset()
+    {
+        free_order();
+        if (nodes) (void)hipFree(nodes);
+        nodes   = nullptr;
+        n_nodes = n_slots = 0;
+    }
 };
 
 // Builds on the current device.  SP_OK, or SP_ERR_HIP with `err` set (nothing stays allocated and

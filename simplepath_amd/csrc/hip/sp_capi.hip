@@ -113,13 +113,33 @@ struct UploadOpts {
     }
 };
 
-static int env_int(const char* name, int fallback)
-{
-    const char* v = std::getenv(name);
-    return v ? std::atoi(v) : fallback;
-}
+// The SP_* test hooks of the upload path, read once per call (the struct's initialisers are the
+// compiled defaults).  All but the last two stand in for an sp_upload_params / sp_build_params field
+// left automatic; `timing` and `rsqrt_pack` have no field, and are not part of UploadOpts: a change
+// of SP_RSQRT_PACK alone does not make an upload with the resident options build again.
+struct UploadHooks {
+    int  stackless = 0, stack_max = 96, wide = 1, env_guide = 1, wide_closest = 1, sah_leaf = 4;
+    int  device_build = 0, device_finish = -1; // -1: the finish follows the builder
+    bool timing     = false;                   // SP_UPLOAD_TIMING (set at all): the sp_upload_timing line
+    bool rsqrt_pack = true;                    // SP_RSQRT_PACK=0: 32-bit RSQRTSS entries (comparison)
 
-int resolve_upload(const sp_upload_params* p, UploadOpts& o)
+    static UploadHooks from_env()
+    {
+        UploadHooks h;
+        int         pack = 1;
+        const std::pair<const char*, int*> ints[] = {
+            { "SP_STACKLESS", &h.stackless }, { "SP_STACK_MAX", &h.stack_max }, { "SP_WIDE", &h.wide },
+            { "SP_ENV_GUIDE", &h.env_guide }, { "SP_WIDE_CLOSEST", &h.wide_closest }, { "SP_SAH_LEAF", &h.sah_leaf },
+            { "SP_DEVICE_BUILD", &h.device_build }, { "SP_DEVICE_FINISH", &h.device_finish }, { "SP_RSQRT_PACK", &pack } };
+        for (const auto& e : ints)
+            if (const char* v = std::getenv(e.first)) *e.second = std::atoi(v);
+        h.timing     = std::getenv("SP_UPLOAD_TIMING") != nullptr;
+        h.rsqrt_pack = pack != 0;
+        return h;
+    }
+};
+
+int resolve_upload(const sp_upload_params* p, const UploadHooks& hooks, UploadOpts& o)
 {
     const sp_upload_params z{};
     if (!p) p = &z;
@@ -130,23 +150,24 @@ int resolve_upload(const sp_upload_params* p, UploadOpts& o)
     if (p->stack_max_levels < 0) return fail(SP_ERR_ARG, "stack_max_levels < 0");
     if (p->sah_leaf < 0 || p->sah_leaf > 4) return fail(SP_ERR_ARG, "sah_leaf must be 0 (automatic) or 1..4");
     o.bvh_mode  = p->bvh_mode;
-    o.stackless = p->walk == SP_WALK_STACKLESS || (p->walk == SP_WALK_AUTO && env_int("SP_STACKLESS", 0) != 0);
-    o.stack_max = p->stack_max_levels ? p->stack_max_levels : std::max(1, env_int("SP_STACK_MAX", 96));
-    o.wide      = !p->no_wide_bvh && env_int("SP_WIDE", 1) != 0;
-    o.env_guide = !p->env_replay && env_int("SP_ENV_GUIDE", 1) != 0;
-    o.wide_closest = !p->binary_closest && env_int("SP_WIDE_CLOSEST", 1) != 0;
+    o.stackless = p->walk == SP_WALK_STACKLESS || (p->walk == SP_WALK_AUTO && hooks.stackless != 0);
+    o.stack_max = p->stack_max_levels ? p->stack_max_levels : std::max(1, hooks.stack_max);
+    o.wide      = !p->no_wide_bvh && hooks.wide != 0;
+    o.env_guide = !p->env_replay && hooks.env_guide != 0;
+    o.wide_closest = !p->binary_closest && hooks.wide_closest != 0;
     // SAH leaf size limit (1..4: 8 collapsed leaves of a wide node must fit its 5-bit leaf
     // offsets; the sweep in DESIGN.md §4 found 4 best)
-    o.sah_leaf  = p->sah_leaf ? p->sah_leaf : std::max(1, std::min(4, env_int("SP_SAH_LEAF", 4)));
+    o.sah_leaf  = p->sah_leaf ? p->sah_leaf : std::max(1, std::min(4, hooks.sah_leaf));
     return SP_OK;
 }
 
 // The builder of an upload (sp_build_params): NULL or AUTO is the host builders, unless the test
 // hook SP_DEVICE_BUILD=1 asks for the device builder on a SAH-mode upload.  The finish
 // (sp_build_params_ex, told apart by struct_size): AUTO follows the builder unless the test hook
-// SP_DEVICE_FINISH=0|1 decides.
-int resolve_build(const sp_build_params* b, UploadOpts& o)
+// SP_DEVICE_FINISH=0|1 decides.  sp_upload_params is validated first.
+int resolve_opts(const sp_upload_params* p, const sp_build_params* b, const UploadHooks& hooks, UploadOpts& o)
 {
+    if (int rc = resolve_upload(p, hooks, o)) return rc;
     int builder = SP_BUILDER_AUTO, finish = SP_FINISH_AUTO;
     if (b) {
         if (b->struct_size != sizeof(sp_build_params) && b->struct_size != sizeof(sp_build_params_ex))
@@ -167,13 +188,13 @@ int resolve_build(const sp_build_params* b, UploadOpts& o)
     if (builder == SP_BUILDER_DEVICE && o.bvh_mode == 1)
         return fail(SP_ERR_ARG, "the device builder cannot make the reference order (bvh_mode 1)");
     if (builder == SP_BUILDER_AUTO)
-        builder = (o.bvh_mode == 0 && env_int("SP_DEVICE_BUILD", 0) == 1) ? SP_BUILDER_DEVICE : SP_BUILDER_HOST;
+        builder = (o.bvh_mode == 0 && hooks.device_build == 1) ? SP_BUILDER_DEVICE : SP_BUILDER_HOST;
     o.builder = builder;
     if (finish == SP_FINISH_DEVICE && o.bvh_mode == 1)
         return fail(SP_ERR_ARG, "the device finish cannot serve the reference order (bvh_mode 1)");
     if (finish == SP_FINISH_AUTO) {
-        const int hook = env_int("SP_DEVICE_FINISH", -1);
-        const bool dev = hook == 0 ? false : (hook == 1 ? true : builder == SP_BUILDER_DEVICE);
+        const int  hook = hooks.device_finish;
+        const bool dev  = hook == 0 ? false : (hook == 1 ? true : builder == SP_BUILDER_DEVICE);
         finish         = (dev && o.bvh_mode == 0) ? SP_FINISH_DEVICE : SP_FINISH_HOST;
     }
     o.finish = finish;
@@ -211,50 +232,36 @@ struct UploadTiming {
     }
 };
 
-// The BVH over the bounded part: the reference's median split (bvh_mode 1,
-// shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder -- built on the
-// current device when `on_device`, else by its host restatement (the same tree).
-// With `keep` (device builder and device finish) the tree stays on the device: the Bvh returned has
-// only its depth, and `keep` the blocks.
-sph::Bvh geometry_bvh(const sph::Scene& h, const UploadOpts& o, std::vector<int32_t>& prims, size_t& part, bool on_device = false,
-                      UploadTiming* tm = nullptr, std::vector<sph::PrimBounds>* bounds_out = nullptr, spb::DeviceTree* keep = nullptr)
-{
-    std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
-    if (tm) tm->lap(tm->ms_bounds);
-    sph::Bvh bvh;
-    if (o.bvh_mode == 1) bvh = sph::build_bvh_reference(bounds);
-    else if (o.builder != SP_BUILDER_DEVICE) bvh = sph::build_bvh_sah(bounds, o.sah_leaf);
-    else if (!on_device) bvh = sph::build_bvh_lbvh(bounds, o.sah_leaf);
-    else {
-        spb::BuildStats st;
-        std::string     err;
-        const int       rc = spb::build_lbvh_device(bounds, o.sah_leaf, bvh, st, err, tm != nullptr, keep);
-        if (rc != SP_OK) throw sph::SpError(rc, err);
-        if (tm) tm->dev = st;
-    }
-    if (tm) tm->lap(tm->ms_bvh);
-    if (bounds_out) bounds_out->swap(bounds);
-    return bvh;
-}
+// How a render walks the scene's accelerators (spd::Scene carries these five)
+struct WalkPlan {
+    bool stackless = false, wide_closest = false; // parent links, no stack; closest hits on the 8-wide BVH too
+    int  stack_depth = 0, stack_words = 0, any_stack_words = 0; // LDS words per lane
+};
 
-// SAH scenes get the 8-wide quantised BVH for any-hit queries (no_wide_bvh keeps the binary walk)
-bool wide_enabled(const UploadOpts& o) { return o.bvh_mode != 1 && o.wide; }
-
+// The walk of a scene from its options and the depths of its trees.  wide_depth 0: no 8-wide BVH (one
+// that exists has a record and a level, from either finish: its depth says as much as its record
+// count); `stackless` depends on the binary depths alone, so it is known before the wide tree, which
+// is built only for a scene that keeps its stack.
 // Traversal-stack budget: a BVH deeper than stack_max levels (default 96) is walked without a
 // stack (parent links, sp_path.hpp bvh_next) instead of failing.  96 entries x 4 B x 64 lanes x 4
 // waves = 96 KB of LDS, which leaves room for the 16 KB RSQRTSS table and a second block per CU.
-bool stackless_for(const UploadOpts& o, int depth) { return o.stackless || depth + 1 > o.stack_max; }
-
-// Scene ctor's light accelerator (base/Scene.h:29): sphere lights first (libstdc++
-// std::partition order), the reference BVH over them; the rest are unbounded
-sph::Bvh light_bvh(const sph::Scene& h, std::vector<int32_t>& lids, size_t& lpart)
+// Words of LDS traversal stack per lane: the binary walks push at most one deferred child per
+// level; the wide walks one child group per level, and the closest-hit form keeps each group's
+// entry distance in the upper half.  SAH scenes walk the 8-wide BVH for every query (any-hit since
+// round 1, closest hit since round 3: DESIGN.md §9g); then no query walks the binary geometry BVH,
+// so its depth no longer sizes the stack -- only the wide and the light BVH's do (lucy 30 -> 22
+// words: a fourth 4-wave block fits a CU's LDS).
+WalkPlan walk_plan(const UploadOpts& o, int geom_depth, int light_depth, int wide_depth)
 {
-    lids.resize(h.lights.size());
-    for (size_t i = 0; i < lids.size(); ++i) lids[i] = (int32_t)i;
-    lpart = sph::stl_partition(lids, 0, lids.size(), [&](int32_t i) { return h.lights[i].kind == SP_LIGHT_SPHERE; });
-    std::vector<sph::PrimBounds> lb;
-    for (size_t i = 0; i < lpart; ++i) lb.push_back(sphere_bounds(from_desc(h.lights[lids[i]].object_to_world)));
-    return sph::build_bvh_reference(lb);
+    WalkPlan w;
+    w.stackless = o.stackless || std::max(geom_depth, light_depth) + 1 > o.stack_max;
+    if (w.stackless) return w; // deeper than the LDS budget: no stack words at all
+    w.wide_closest = o.wide_closest && wide_depth != 0;
+    w.stack_depth  = w.wide_closest ? std::max(2 * (wide_depth + 1), light_depth + 1)
+                                    : std::max(geom_depth, std::max(wide_depth, light_depth)) + 1;
+    w.stack_words     = w.stack_depth;
+    w.any_stack_words = std::max(wide_depth == 0 ? geom_depth : wide_depth, light_depth) + 1;
+    return w;
 }
 
 // Per-slot primitive records in the binary tree's order: slot_code, and slot_tri = 3 x float4 with
@@ -293,10 +300,79 @@ std::vector<uint32_t> parent_links(const std::vector<sph::BvhNode>& nodes)
     return par;
 }
 
-struct DevBuf {
-    void*  p     = nullptr;
-    size_t bytes = 0;
+// Everything the host knows about a scene's accelerators under given options: build_trees fills the
+// first half, finish_host the arrays a render reads (for the callers that want them made here).
+struct HostAccel {
+    std::vector<int32_t>         prims, lids; // Scene ctor order: `part` bounded primitives, `lpart` sphere lights first
+    size_t                       part = 0, lpart = 0;
+    std::vector<sph::PrimBounds> bounds;       // of the bounded primitives
+    sph::Bvh                     bvh, lbvh;    // geometry (only max_depth when the tree stays on the device), lights
+    size_t                       n_nodes = 0, n_slots = 0; // the geometry tree's, wherever it is
+    bool                         want_wide = false;
+    WalkPlan                     walk; // after build_trees as for no wide tree (stackless is final); then with its depth
+    sph::WideBvh                 wide;
+    std::vector<float4>          slot_tri, wslot_tri;
+    std::vector<uint32_t>        slot_code, parents, light_parents;
 };
+
+enum class BuildOn { HOST, DEVICE }; // where SP_BUILDER_DEVICE runs: its host restatement, or the current device
+
+// Bounds; the BVH over the bounded part -- the reference's median split (bvh_mode 1,
+// shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder (one tree,
+// from the device or its host restatement); the light BVH; and from their depths whether the scene
+// is walked without a stack (then with the light tree's parent links, which either finish needs)
+// or gets the 8-wide BVH (SAH scenes; no_wide_bvh keeps the binary walk).  With `keep` (device
+// builder and device finish) the geometry tree stays on the device, in `keep`.
+void build_trees(const sph::Scene& h, HostAccel& a, const UploadOpts& o, BuildOn where, UploadTiming* tm = nullptr,
+                 spb::DeviceTree* keep = nullptr)
+{
+    a.bounds = bounded_prims(h, a.prims, a.part);
+    if (tm) tm->lap(tm->ms_bounds);
+    if (o.bvh_mode == 1) a.bvh = sph::build_bvh_reference(a.bounds);
+    else if (o.builder != SP_BUILDER_DEVICE) a.bvh = sph::build_bvh_sah(a.bounds, o.sah_leaf);
+    else if (where == BuildOn::HOST) a.bvh = sph::build_bvh_lbvh(a.bounds, o.sah_leaf);
+    else {
+        spb::BuildStats st;
+        std::string     err;
+        const int       rc = spb::build_lbvh_device(a.bounds, o.sah_leaf, a.bvh, tm ? tm->dev : st, err, tm != nullptr, keep);
+        if (rc != SP_OK) throw sph::SpError(rc, err);
+    }
+    const bool kept = keep && keep->nodes;
+    a.n_nodes       = kept ? keep->n_nodes : a.bvh.nodes.size();
+    a.n_slots       = kept ? keep->n_slots : a.bvh.prim_order.size();
+    if (tm) tm->lap(tm->ms_bvh);
+    // Scene ctor's light accelerator (base/Scene.h:29): sphere lights first (libstdc++
+    // std::partition order), the reference BVH over them; the rest are unbounded
+    a.lids.resize(h.lights.size());
+    for (size_t i = 0; i < a.lids.size(); ++i) a.lids[i] = (int32_t)i;
+    a.lpart = sph::stl_partition(a.lids, 0, a.lids.size(), [&](int32_t i) { return h.lights[i].kind == SP_LIGHT_SPHERE; });
+    std::vector<sph::PrimBounds> lb;
+    for (size_t i = 0; i < a.lpart; ++i) lb.push_back(sphere_bounds(from_desc(h.lights[a.lids[i]].object_to_world)));
+    a.lbvh      = sph::build_bvh_reference(lb);
+    a.walk      = walk_plan(o, a.bvh.max_depth, a.lbvh.max_depth, 0);
+    a.want_wide = o.bvh_mode != 1 && o.wide && a.n_nodes != 0 && !a.walk.stackless;
+    if (a.walk.stackless) a.light_parents = parent_links(a.lbvh.nodes);
+    if (tm) tm->lap(tm->ms_copies); // (lights: counted with the copies)
+}
+
+// The host finish: records, the 8-wide tree with its own copy of the records in its slot order,
+// and the geometry tree's parent links for a stackless walk.  The level-wise collapse stands in
+// for the device finish (the same bytes: tests/golden/wide_hashes.json).
+void finish_host(const sph::Scene& h, HostAccel& a, const UploadOpts& o, UploadTiming* tm = nullptr)
+{
+    pack_records(h, a.prims, a.bvh.prim_order, a.slot_tri, a.slot_code);
+    if (a.walk.stackless) a.parents = parent_links(a.bvh.nodes);
+    if (tm) tm->lap(tm->ms_pack);
+    if (a.want_wide) {
+        a.wide = o.finish == SP_FINISH_DEVICE ? sph::build_wide_levels(a.bvh) : sph::build_wide(a.bvh);
+        if (tm) tm->lap(tm->ms_wide);
+        a.wslot_tri.resize(a.wide.slot_of.size() * 3);
+        for (size_t i = 0; i < a.wide.slot_of.size(); ++i)
+            for (int k = 0; k < 3; ++k) a.wslot_tri[3 * i + k] = a.slot_tri[3 * (size_t)a.wide.slot_of[i] + k];
+        if (tm) tm->lap(tm->ms_pack);
+    }
+    a.walk = walk_plan(o, a.bvh.max_depth, a.lbvh.max_depth, a.wide.depth);
+}
 
 static_assert(splan::MT_N == spm::MT_N && splan::MT_GEN_WORDS == spd::MT_GEN_WORDS && splan::WF_MAX_LIGHTS == spd::WF_MAX_LIGHTS,
               "sp_plan.hpp's copies of the layout constants");
@@ -436,6 +512,13 @@ struct RenderScratch {
     int           stage_next = 0;
     int           n_cu = 0;     // the device's compute units (0: not asked yet)
 };
+
+// Sizes of the resident accelerators: what the check and info calls need to read them back
+struct ResidentSizes {
+    int    geom_depth = 0, light_depth = 0, wide_depth = 0;
+    size_t geom_nodes = 0, geom_slots = 0;
+    size_t wide_records = 0, wide_slots = 0; // 8-wide BVH (0: none)
+};
 } // namespace
 
 struct sp_scene {
@@ -444,15 +527,11 @@ struct sp_scene {
     std::vector<sp_env_image>   env_descs; // desc.env_images
     std::vector<sp_material_desc> mat_descs; // desc.materials
     // device residency
-    int                  device   = -1;
-    int                  bvh_mode = -1;
+    int                  device   = -1; // >= 0 only after an upload that built everything
     UploadOpts           opts{};    // effective accelerator options of the resident upload
-    std::vector<DevBuf>  bufs;
+    std::vector<DeviceScratch> bufs; // every device array of the resident scene
     spd::Scene           dev{};
-    int                  geom_depth = 0, light_depth = 0;
-    size_t               geom_nodes = 0, geom_slots = 0;
-    size_t               wide_records = 0, wide_slots = 0; // 8-wide BVH (0: none)
-    int                  wide_depth = 0;
+    ResidentSizes        sizes;
     // One scene, many host threads (the reference's render() shares one Scene across N threads,
     // main.cpp:122-130): the render scratch is per scene, so calls are serialised -- on the
     // host by `mu`, and on the device by making each call's stream wait for the previous call's
@@ -471,24 +550,35 @@ struct sp_scene {
     void release()
     {
         if (device >= 0) (void)hipSetDevice(device);
-        for (auto& b : bufs) (void)hipFree(b.p);
         bufs.clear();
         scratch = RenderScratch{};
-        device = -1; bvh_mode = -1;
+        sizes   = ResidentSizes{};
+        dev     = spd::Scene{};
+        device  = -1;
     }
     ~sp_scene() { release(); }
+
+    // takes over a device block made elsewhere (sp_build.hip, sp_finish.hip): `p` is null afterwards
+    template <typename T>
+    void adopt(void*& p, size_t bytes, const T** out)
+    {
+        *out = static_cast<const T*>(p);
+        if (!p) return;
+        bufs.emplace_back(); // (first: a failed push leaves `p` with its owner)
+        bufs.back().ptr = p;
+        bufs.back().cap = bytes;
+        p               = nullptr;
+    }
 
     template <typename T>
     int upload(const std::vector<T>& v, const T** out)
     {
         *out = nullptr;
         if (v.empty()) return SP_OK;
-        DevBuf b;
-        b.bytes = v.size() * sizeof(T);
-        SP_HIP(hipMalloc(&b.p, b.bytes));
-        SP_HIP(hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
-        bufs.push_back(b);
-        *out = static_cast<const T*>(b.p);
+        bufs.emplace_back();
+        SP_HIP(bufs.back().reserve(v.size() * sizeof(T)));
+        SP_HIP(hipMemcpy(bufs.back().ptr, v.data(), bufs.back().cap, hipMemcpyHostToDevice));
+        *out = bufs.back().as<T>();
         return SP_OK;
     }
 };
@@ -848,44 +938,37 @@ float sp_host_rsqrt_emulated(float x)
     return spm::rsqrtss_emulated(x, t);
 }
 
-// Words of LDS traversal stack per lane.  The binary walks push at most one deferred child per
-// level; the wide walks one child group per level, and the closest-hit form keeps each group's
-// entry distance in the upper half.  Once closest hits walk the wide BVH (SAH scenes), no query
-// walks the binary geometry BVH, so its depth no longer sizes the stack -- only the wide and the
-// light BVH's do (lucy 30 -> 22 words: a fourth 4-wave block fits a CU's LDS).
-static int stack_entries(int depth, int wide_depth, int light_depth, bool wide_closest)
-{
-    if (wide_closest) return std::max(2 * (wide_depth + 1), light_depth + 1);
-    return std::max(depth, std::max(wide_depth, light_depth)) + 1;
-}
+// ---- sp_scene_upload* -----------------------------------------------------------------------------
 
-static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params* up_params, const sp_build_params* build)
+// One upload, resolved: what its steps share
+struct UploadCall {
+    sp_scene*       s;
+    int             device;
+    UploadHooks     hooks;
+    UploadOpts      opts;
+    UploadTiming    timing;
+    UploadTiming*   tm = nullptr; // &timing under SP_UPLOAD_TIMING
+    HostAccel       accel;
+    spb::DeviceTree dtree; // device builder + device finish: the binary tree never comes back
+    bool device_finish() const { return opts.finish == SP_FINISH_DEVICE; }
+};
+#define SP_TRY(call) do { if (int rc__ = (call)) return rc__; } while (0)
+
+// Arguments, in the order their errors are promised: (the scene, by the caller,) sp_upload_params,
+// sp_build_params, the device count, the device's range.  Changes no state.  `resident`: nothing to do.
+static int validate_upload(UploadCall& c, const sp_upload_params* params, const sp_build_params* build, bool& resident)
 {
-    if (!s) return fail(SP_ERR_ARG, "null scene");
-    UploadOpts opts;
-    if (int rc0 = resolve_upload(up_params, opts)) return rc0;
-    if (int rc0 = resolve_build(build, opts)) return rc0;
-    const int bvh_mode = opts.bvh_mode;
+    SP_TRY(resolve_opts(params, build, c.hooks, c.opts));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SP_ERR_HIP, "no HIP device");
-    if (device < 0 || device >= ndev) return fail(SP_ERR_ARG, "device out of range");
-    if (s->device == device && s->opts == opts) return SP_OK;
-    s->release();
-    ++s->generation;
-    SP_HIP(hipSetDevice(device));
-    s->device   = device;
-    s->bvh_mode = bvh_mode;
-    s->opts     = opts;
-    const sph::Scene& h = *s->host;
-    spd::Scene&       d = s->dev;
-    d                   = spd::Scene{};
+    if (c.device < 0 || c.device >= ndev) return fail(SP_ERR_ARG, "device out of range");
+    resident = c.s->device == c.device && c.s->opts == c.opts;
+    return SP_OK;
+}
 
-    const auto& rc = sph::rsqrt_active();
-    if (rc.entries.empty()) return fail(SP_ERR_UNSUPPORTED, "RSQRTSS table capture failed");
-    if (!rc.verified) return fail(SP_ERR_UNSUPPORTED, "RSQRTSS table could not be verified on this host CPU");
-
-    // ---- materials (nested clearcoat is not produced by the scenes on this path)
-    std::vector<spd::Material> mats;
+// (nested clearcoat is not produced by the scenes on this path)
+static int convert_materials(const sph::Scene& h, std::vector<spd::Material>& mats)
+{
     for (auto& m : h.materials) {
         spd::Material x{};
         x.kind           = m.d.kind;
@@ -902,22 +985,11 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
             return fail(SP_ERR_UNSUPPORTED, "clearcoat over clearcoat");
         mats.push_back(x);
     }
+    return SP_OK;
+}
 
-    // ---- geometry: Scene ctor partition (base/Scene.h:29) then BVH over the bounded part
-    std::vector<int32_t> prims;
-    size_t               part = 0;
-    UploadTiming         timing;
-    UploadTiming*        tm   = std::getenv("SP_UPLOAD_TIMING") ? &timing : nullptr;
-    const bool           dev_finish = opts.finish == SP_FINISH_DEVICE;
-    spb::DeviceTree      dtree; // device builder + device finish: the binary tree never comes back
-    struct OrderGuard {         // its order is build scratch: freed after the finish, whichever way
-        spb::DeviceTree& t;
-        ~OrderGuard() { if (t.order) (void)hipFree(t.order); }
-    } order_guard{ dtree };
-    const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part, true, tm, nullptr, dev_finish ? &dtree : nullptr);
-    if (dtree.nodes) s->bufs.push_back(DevBuf{ dtree.nodes, (size_t)dtree.n_nodes * sizeof(sph::BvhNode) });
-    const size_t n_nodes = dtree.nodes ? dtree.n_nodes : bvh.nodes.size();
-    const size_t n_slots = dtree.nodes ? dtree.n_slots : bvh.prim_order.size();
+static std::vector<spd::Shape> convert_shapes(const sph::Scene& h)
+{
     std::vector<spd::Shape> shapes;
     for (auto& sh : h.shapes) {
         spd::Shape x{};
@@ -928,16 +1000,11 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
         x.kind     = sh.kind;
         shapes.push_back(x);
     }
-    std::vector<int32_t> unbounded;
-    for (size_t i = part; i < prims.size(); ++i) unbounded.push_back(h.prim_index[prims[i]]);
-    std::vector<float4>   slot_tri;
-    std::vector<uint32_t> slot_code;
-    if (!dev_finish) pack_records(h, prims, bvh.prim_order, slot_tri, slot_code);
-    std::vector<spd::Node> nodes(bvh.nodes.size());
-    static_assert(sizeof(spd::Node) == sizeof(sph::BvhNode), "node layout");
-    std::memcpy(nodes.data(), bvh.nodes.data(), nodes.size() * sizeof(spd::Node));
-    if (tm) tm->lap(tm->ms_pack);
-    // ---- lights: Scene::m_lights order + accelerator (partition by boundedness)
+    return shapes;
+}
+
+static std::vector<spd::Light> convert_lights(const sph::Scene& h) // Scene::m_lights order
+{
     std::vector<spd::Light> lights;
     for (auto& l : h.lights) {
         spd::Light x{};
@@ -949,34 +1016,16 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
         x.nrm      = from_desc(l.normal_to_world);
         lights.push_back(x);
     }
-    std::vector<int32_t> lids;
-    size_t               lpart = 0;
-    const sph::Bvh       lbvh  = light_bvh(h, lids, lpart);
-    std::vector<int32_t> unbounded_lights(lids.begin() + (long)lpart, lids.end());
-    std::vector<uint32_t> light_slot(lbvh.prim_order.size());
-    for (size_t sl = 0; sl < light_slot.size(); ++sl) light_slot[sl] = (uint32_t)lids[lbvh.prim_order[sl]];
-    std::vector<spd::Node> lnodes(lbvh.nodes.size());
-    std::memcpy(lnodes.data(), lbvh.nodes.data(), lnodes.size() * sizeof(spd::Node));
+    return lights;
+}
 
-    // SAH: 8-wide quantised BVH for any-hit queries (SP_WIDE=0 keeps the binary walk); a
-    // stackless scene walks the binary BVH only
-    const bool          stackless = stackless_for(opts, std::max(bvh.max_depth, lbvh.max_depth));
-    sph::WideBvh        wide;
-    std::vector<float4> wslot_tri;
-    if (tm) tm->lap(tm->ms_copies); // (lights: counted with the copies)
-    const bool want_wide = wide_enabled(opts) && n_nodes != 0 && !stackless;
-    if (want_wide && !dev_finish) {
-        wide = sph::build_wide(bvh);
-        if (tm) tm->lap(tm->ms_wide);
-        wslot_tri.resize(wide.slot_of.size() * 3);
-        for (size_t i = 0; i < wide.slot_of.size(); ++i)
-            for (int k = 0; k < 3; ++k) wslot_tri[3 * i + k] = slot_tri[3 * (size_t)wide.slot_of[i] + k];
-        if (tm) tm->lap(tm->ms_pack);
-    }
-
-    // ---- upload
-    int rc2 = SP_OK;
-    auto up = [&](auto& vec, auto** ptr) { if (rc2 == SP_OK) rc2 = s->upload(vec, ptr); };
+// Camera, the unbounded list, the binary tree (adopted where the device built it), normals, indices
+// (the device finish reads them), triangle materials, shapes, lights and the light accelerator
+static int upload_scene_arrays(UploadCall& c)
+{
+    const sph::Scene& h = *c.s->host;
+    const HostAccel&  a = c.accel;
+    spd::Scene&       d = c.s->dev;
     d.camera    = h.camera;
     d.width     = h.image_width;
     d.height    = h.image_height;
@@ -986,84 +1035,107 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     sph::rsequence_alphas(a1, a2);
     d.alpha2_0 = a2[0];
     d.alpha2_1 = a2[1];
+    std::vector<int32_t> unbounded;
+    for (size_t i = a.part; i < a.prims.size(); ++i) unbounded.push_back(h.prim_index[a.prims[i]]);
     d.n_unbounded = (int)unbounded.size();
-    up(unbounded, &d.unbounded);
-    d.n_nodes = (int)n_nodes;
-    if (dtree.nodes) d.nodes = static_cast<const spd::Node*>(dtree.nodes);
-    else up(nodes, &d.nodes);
-    d.wnodes    = nullptr;
-    d.wslot_tri = nullptr;
-    if (!wide.words.empty()) {
-        std::vector<uint4> wn(wide.words.size() / 4);
-        std::memcpy(wn.data(), wide.words.data(), wide.words.size() * 4);
-        up(wn, &d.wnodes);
-        up(wslot_tri, &d.wslot_tri);
-    }
-    if (!dev_finish) {
-        up(slot_tri, &d.slot_tri);
-        up(slot_code, &d.slot_code);
+    SP_TRY(c.s->upload(unbounded, &d.unbounded));
+    d.n_nodes = (int)a.n_nodes;
+    static_assert(sizeof(spd::Node) == sizeof(sph::BvhNode), "node layout");
+    if (c.dtree.nodes) c.s->adopt(c.dtree.nodes, a.n_nodes * sizeof(sph::BvhNode), &d.nodes);
+    else {
+        std::vector<spd::Node> nodes(a.bvh.nodes.size());
+        std::memcpy(nodes.data(), a.bvh.nodes.data(), nodes.size() * sizeof(spd::Node));
+        SP_TRY(c.s->upload(nodes, &d.nodes));
     }
     std::vector<float> nrm(h.normals.size() * 3);
     for (size_t i = 0; i < h.normals.size(); ++i) { nrm[3 * i] = h.normals[i].x; nrm[3 * i + 1] = h.normals[i].y; nrm[3 * i + 2] = h.normals[i].z; }
-    up(nrm, &d.normals);
-    up(h.indices, &d.indices);
-    size_t wide_records = wide.words.size() / 20, wide_slots = wide.slot_of.size();
-    int    wide_depth   = wide.depth;
-    d.parents           = nullptr;
-    if (dev_finish && rc2 == SP_OK) {
-        // the finish on the device (sp_finish.hip): the same arrays from the resident binary tree
-        if (tm) tm->lap(tm->ms_copies);
-        std::vector<uint32_t> codes(part);
-        for (size_t i = 0; i < part; ++i) codes[i] = code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]);
-        spf::FinishIn in;
-        in.d_nodes      = reinterpret_cast<const sph::BvhNode*>(d.nodes);
-        in.n_nodes      = (uint32_t)n_nodes;
-        in.d_order      = static_cast<const uint32_t*>(dtree.order);
-        in.h_order      = bvh.prim_order.data();
-        in.n_slots      = (uint32_t)n_slots;
-        in.h_codes      = codes.data();
-        in.n_prims      = (uint32_t)part;
-        in.h_verts      = h.vertices.data();
-        in.n_verts      = h.vertices.size();
-        in.d_indices    = d.indices;
-        in.n_indices    = h.indices.size();
-        in.want_wide    = want_wide;
-        in.want_parents = stackless;
-        spf::FinishOut   fo;
-        spf::FinishStats fs;
-        std::string      ferr;
-        const int        frc = spf::finish_device(in, fo, fs, ferr, tm != nullptr);
-        if (frc != SP_OK) throw sph::SpError(frc, ferr);
-        if (dtree.order) (void)hipFree(dtree.order);
-        dtree.order = nullptr;
-        if (tm) tm->fin = fs;
-        const std::pair<void*, size_t> got[] = { { fo.wnodes, fo.wnodes_bytes }, { fo.wslot_tri, fo.wslot_tri_bytes },
-                                                 { fo.slot_tri, fo.slot_tri_bytes }, { fo.slot_code, fo.slot_code_bytes },
-                                                 { fo.parents, fo.parents_bytes } };
-        for (const auto& g : got)
-            if (g.first) s->bufs.push_back(DevBuf{ g.first, g.second });
-        d.wnodes     = static_cast<const uint4*>(fo.wnodes);
-        d.wslot_tri  = static_cast<const float4*>(fo.wslot_tri);
-        d.slot_tri   = static_cast<const float4*>(fo.slot_tri);
-        d.slot_code  = static_cast<const uint32_t*>(fo.slot_code);
-        d.parents    = static_cast<const uint32_t*>(fo.parents);
-        wide_records = fo.records;
-        wide_slots   = fo.wide_slots;
-        wide_depth   = fo.depth;
-        if (tm) tm->lap(tm->ms_wide);
-    }
-    up(h.tri_material, &d.tri_material);
-    up(shapes, &d.shapes);
-    d.n_lights = (int)lights.size();
-    up(lights, &d.lights);
+    SP_TRY(c.s->upload(nrm, &d.normals));
+    SP_TRY(c.s->upload(h.indices, &d.indices));
+    SP_TRY(c.s->upload(h.tri_material, &d.tri_material));
+    SP_TRY(c.s->upload(convert_shapes(h), &d.shapes));
+    d.n_lights = (int)h.lights.size();
+    SP_TRY(c.s->upload(convert_lights(h), &d.lights));
+    // the light accelerator (partition by boundedness): unbounded lights, nodes, slot -> light
+    std::vector<int32_t>  unbounded_lights(a.lids.begin() + (long)a.lpart, a.lids.end());
+    std::vector<uint32_t> light_slot(a.lbvh.prim_order.size());
+    for (size_t sl = 0; sl < light_slot.size(); ++sl) light_slot[sl] = (uint32_t)a.lids[a.lbvh.prim_order[sl]];
+    std::vector<spd::Node> lnodes(a.lbvh.nodes.size());
+    std::memcpy(lnodes.data(), a.lbvh.nodes.data(), lnodes.size() * sizeof(spd::Node));
     d.n_unbounded_lights = (int)unbounded_lights.size();
-    up(unbounded_lights, &d.unbounded_lights);
+    SP_TRY(c.s->upload(unbounded_lights, &d.unbounded_lights));
     d.n_light_nodes = (int)lnodes.size();
-    up(lnodes, &d.light_nodes);
-    up(light_slot, &d.light_slot);
-    // image environment lights: the constructor's tables (sp_envmap.cpp), then the EnvMap records
+    SP_TRY(c.s->upload(lnodes, &d.light_nodes));
+    SP_TRY(c.s->upload(light_slot, &d.light_slot));
+    return c.s->upload(a.light_parents, &d.light_parents); // (empty unless stackless)
+}
+
+// The finish's arrays as finish_host made them.  Like run_device_finish it fills wnodes, wslot_tri,
+// slot_tri, slot_code and parents, and leaves the wide tree's sizes in s->sizes.
+static int upload_finish_host(UploadCall& c)
+{
+    const HostAccel& a = c.accel;
+    spd::Scene&      d = c.s->dev;
+    std::vector<uint4> wn(a.wide.words.size() / 4);
+    std::memcpy(wn.data(), a.wide.words.data(), a.wide.words.size() * 4);
+    SP_TRY(c.s->upload(wn, &d.wnodes));
+    SP_TRY(c.s->upload(a.wslot_tri, &d.wslot_tri));
+    SP_TRY(c.s->upload(a.slot_tri, &d.slot_tri));
+    SP_TRY(c.s->upload(a.slot_code, &d.slot_code));
+    SP_TRY(c.s->upload(a.parents, &d.parents));
+    c.s->sizes.wide_records = a.wide.words.size() / 20;
+    c.s->sizes.wide_slots   = a.wide.slot_of.size();
+    c.s->sizes.wide_depth   = a.wide.depth;
+    return SP_OK;
+}
+
+// The finish on the device (sp_finish.hip): the same arrays from the resident binary tree and the
+// resident indices.  The tree's order is build scratch: freed as soon as the finish has read it.
+static int run_device_finish(UploadCall& c)
+{
+    const sph::Scene& h = *c.s->host;
+    HostAccel&        a = c.accel;
+    spd::Scene&       d = c.s->dev;
+    if (c.tm) c.tm->lap(c.tm->ms_copies);
+    std::vector<uint32_t> codes(a.part);
+    for (size_t i = 0; i < a.part; ++i) codes[i] = code_of(h.prim_kind[a.prims[i]], h.prim_index[a.prims[i]]);
+    spf::FinishIn in;
+    in.d_nodes      = reinterpret_cast<const sph::BvhNode*>(d.nodes);
+    in.n_nodes      = (uint32_t)a.n_nodes;
+    in.d_order      = static_cast<const uint32_t*>(c.dtree.order);
+    in.h_order      = a.bvh.prim_order.data();
+    in.n_slots      = (uint32_t)a.n_slots;
+    in.h_codes      = codes.data();
+    in.n_prims      = (uint32_t)a.part;
+    in.h_verts      = h.vertices.data();
+    in.n_verts      = h.vertices.size();
+    in.d_indices    = d.indices;
+    in.n_indices    = h.indices.size();
+    in.want_wide    = a.want_wide;
+    in.want_parents = a.walk.stackless;
+    spf::FinishOut fo;
+    std::string    err;
+    const int      rc = spf::finish_device(in, fo, c.timing.fin, err, c.tm != nullptr);
+    c.dtree.free_order();
+    if (rc != SP_OK) return fail(rc, err);
+    c.s->sizes.wide_records = fo.records;
+    c.s->sizes.wide_slots   = fo.wide_slots;
+    c.s->sizes.wide_depth   = fo.depth;
+    c.s->adopt(fo.wnodes, fo.wnodes_bytes, &d.wnodes);
+    c.s->adopt(fo.wslot_tri, fo.wslot_tri_bytes, &d.wslot_tri);
+    c.s->adopt(fo.slot_tri, fo.slot_tri_bytes, &d.slot_tri);
+    c.s->adopt(fo.slot_code, fo.slot_code_bytes, &d.slot_code);
+    c.s->adopt(fo.parents, fo.parents_bytes, &d.parents);
+    a.walk = walk_plan(c.opts, a.bvh.max_depth, a.lbvh.max_depth, fo.depth);
+    if (c.tm) c.tm->lap(c.tm->ms_wide);
+    return SP_OK;
+}
+
+// Image environment lights: the constructor's tables (sp_envmap.cpp), then the EnvMap records
+static int upload_envs(UploadCall& c)
+{
+    spd::Scene&              d = c.s->dev;
     std::vector<spd::EnvMap> envs;
-    for (const auto& e : h.env_images) {
+    for (const auto& e : c.s->host->env_images) {
         const sph::EnvMap m = sph::build_env_map(e);
         spd::EnvMap       x{};
         x.l2w = e.light_to_world;
@@ -1071,31 +1143,32 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
         x.w = m.w; x.h = m.h; x.nu = m.nu; x.nv = m.nv;
         std::vector<float4> rad((size_t)m.w * m.h);
         for (size_t i = 0; i < rad.size(); ++i) rad[i] = make_float4(m.radiance[3 * i], m.radiance[3 * i + 1], m.radiance[3 * i + 2], 0.0f);
-        up(rad, &x.radiance);
-        up(m.cond_func, &x.cond_func);
-        up(m.cond_cdf, &x.cond_cdf);
-        up(m.cond_int, &x.cond_int);
-        up(m.marg_func, &x.marg_func);
-        up(m.marg_cdf, &x.marg_cdf);
+        SP_TRY(c.s->upload(rad, &x.radiance));
+        SP_TRY(c.s->upload(m.cond_func, &x.cond_func));
+        SP_TRY(c.s->upload(m.cond_cdf, &x.cond_cdf));
+        SP_TRY(c.s->upload(m.cond_int, &x.cond_int));
+        SP_TRY(c.s->upload(m.marg_func, &x.marg_func));
+        SP_TRY(c.s->upload(m.marg_cdf, &x.marg_cdf));
         x.marg_int   = m.marg_int;
-        x.cond_guide = nullptr;
-        x.marg_guide = nullptr;
         x.cond_bits  = m.cond_bits;
         x.marg_bits  = m.marg_bits;
-        if (m.guided && opts.env_guide) { // else the exact upper_bound replay (identical results)
-            up(m.cond_guide, &x.cond_guide);
-            up(m.marg_guide, &x.marg_guide);
+        if (m.guided && c.opts.env_guide) { // else the exact upper_bound replay (identical results)
+            SP_TRY(c.s->upload(m.cond_guide, &x.cond_guide));
+            SP_TRY(c.s->upload(m.marg_guide, &x.marg_guide));
         }
         envs.push_back(x);
     }
-    d.envs = nullptr;
-    up(envs, &d.envs);
-    up(mats, &d.materials);
-    // RSQRTSS table as 16-bit device entries when every entry has the same sign and exponent and
-    // at least 7 trailing zero mantissa bits (Intel and AMD hosts alike: exponent 126, 12
-    // significant bits): half the LDS each shading block copies it into (sp_math.h).
-    int      rs_shift = 23;
-    uint32_t rs_hi    = rc.entries[0] & 0xff800000u;
+    return c.s->upload(envs, &d.envs);
+}
+
+// RSQRTSS table as 16-bit device entries when every entry has the same sign and exponent and
+// at least 7 trailing zero mantissa bits (Intel and AMD hosts alike: exponent 126, 12
+// significant bits): half the LDS each shading block copies it into (sp_math.h).
+static int upload_rsqrt_table(UploadCall& c, const sph::RsqrtCapture& rc)
+{
+    spd::Scene& d        = c.s->dev;
+    int         rs_shift = 23;
+    uint32_t    rs_hi    = rc.entries[0] & 0xff800000u;
     for (uint32_t e : rc.entries) {
         if ((e & 0xff800000u) != rs_hi) {
             rs_shift = 0;
@@ -1103,58 +1176,44 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
         }
         while (rs_shift > 0 && (e & ((1u << rs_shift) - 1u))) --rs_shift;
     }
-    if (const char* v = std::getenv("SP_RSQRT_PACK")) // 0: 32-bit entries (comparison)
-        if (std::atoi(v) == 0) rs_shift = 0;
+    if (!c.hooks.rsqrt_pack) rs_shift = 0; // 32-bit entries (comparison)
     if (rs_shift < 7) rs_shift = 0;
-    {
-        const uint32_t hdr[spd::RSQ_HDR] = { (uint32_t)rc.bits, rc.zero_result, rc.denorm_result, (uint32_t)rs_shift,
-                                             rs_shift ? rs_hi : 0u, 0u, 0u, 0u };
-        std::vector<uint32_t> words(hdr, hdr + spd::RSQ_HDR);
-        if (rs_shift) {
-            std::vector<uint16_t> packed(rc.entries.size());
-            for (size_t i = 0; i < packed.size(); ++i) packed[i] = (uint16_t)((rc.entries[i] & 0x7fffffu) >> rs_shift);
-            words.resize(spd::RSQ_HDR + (packed.size() + 1) / 2, 0u);
-            std::memcpy(words.data() + spd::RSQ_HDR, packed.data(), packed.size() * sizeof(uint16_t));
-        } else {
-            words.insert(words.end(), rc.entries.begin(), rc.entries.end());
-        }
-        up(words, &d.rsqrt_entries);
+    const uint32_t hdr[spd::RSQ_HDR] = { (uint32_t)rc.bits, rc.zero_result, rc.denorm_result, (uint32_t)rs_shift,
+                                         rs_shift ? rs_hi : 0u, 0u, 0u, 0u };
+    std::vector<uint32_t> words(hdr, hdr + spd::RSQ_HDR);
+    if (rs_shift) {
+        std::vector<uint16_t> packed(rc.entries.size());
+        for (size_t i = 0; i < packed.size(); ++i) packed[i] = (uint16_t)((rc.entries[i] & 0x7fffffu) >> rs_shift);
+        words.resize(spd::RSQ_HDR + (packed.size() + 1) / 2, 0u);
+        std::memcpy(words.data() + spd::RSQ_HDR, packed.data(), packed.size() * sizeof(uint16_t));
+    } else {
+        words.insert(words.end(), rc.entries.begin(), rc.entries.end());
     }
-    if (rc2 != SP_OK) return rc2;
+    SP_TRY(c.s->upload(words, &d.rsqrt_entries));
     d.rsqrt_shift  = rs_shift;
     d.rsqrt_hi     = rs_shift ? rs_hi : 0u;
     d.rsqrt_bits   = rc.bits;
     d.rsqrt_zero   = rc.zero_result;
     d.rsqrt_denorm = rc.denorm_result;
-    s->geom_depth  = bvh.max_depth;
-    s->light_depth = lbvh.max_depth;
-    s->geom_nodes  = n_nodes;
-    s->geom_slots  = n_slots;
-    s->wide_records = wide_records;
-    s->wide_slots   = wide_slots;
-    s->wide_depth   = wide_depth;
-    // SAH scenes walk the 8-wide BVH for every query: any-hit since round 1 (shadow stage 0.82 ->
-    // 0.53 ms), closest hit since round 3 with octant-ordered slots, near-first entry and group
-    // distances (bunny 3110 -> 3200, lucy 2175 -> 2280 Mrays/s).  Its stack keeps a
-    // distance per entry in the upper half.
-    d.ordered     = bvh_mode == 1 ? 0 : 1; // reference order is part of the bit-exact contract
-    d.wide_closest = (opts.wide_closest && wide_records != 0) ? 1 : 0;
-    d.stack_depth  = stack_entries(bvh.max_depth, wide_depth, lbvh.max_depth, d.wide_closest != 0);
-    d.stackless   = stackless ? 1 : 0;
-    d.merge_queries = 1; // per render: SP_RENDER_PER_LANE_QUERIES clears it
-    d.light_parents = nullptr;
-    if (d.stackless) { // deeper than the LDS budget: parent links instead of a stack
-        std::vector<uint32_t> lpar = parent_links(lbvh.nodes);
-        if (!dev_finish) { // (the device finish has linked the geometry's)
-            std::vector<uint32_t> par = parent_links(bvh.nodes);
-            up(par, &d.parents);
-        }
-        up(lpar, &d.light_parents);
-        if (rc2 != SP_OK) return rc2;
-        d.stack_depth = 0;
-    }
-    d.stack_words     = d.stack_depth;
-    d.any_stack_words = d.stackless ? 0 : std::max(wide_records == 0 ? bvh.max_depth : wide_depth, lbvh.max_depth) + 1;
+    return SP_OK;
+}
+
+static void apply_walk_plan(UploadCall& c)
+{
+    const WalkPlan& w = c.accel.walk;
+    spd::Scene&     d = c.s->dev;
+    d.ordered         = c.opts.bvh_mode == 1 ? 0 : 1; // reference order is part of the bit-exact contract
+    d.wide_closest    = w.wide_closest ? 1 : 0;
+    d.stackless       = w.stackless ? 1 : 0;
+    d.stack_depth     = w.stack_depth;
+    d.stack_words     = w.stack_words;
+    d.any_stack_words = w.any_stack_words;
+    d.merge_queries   = 1; // per render: SP_RENDER_PER_LANE_QUERIES clears it
+}
+
+// what every render call expects to find (the rest of RenderScratch grows on demand)
+static int create_render_handles(sp_scene* s)
+{
     RenderScratch& r = s->scratch;
     SP_HIP(r.tile_counter.reserve(sizeof(int32_t)));
     SP_HIP(r.counters.reserve(8 * sizeof(unsigned long long)));
@@ -1162,42 +1221,93 @@ static int scene_upload_impl(sp_scene* s, int32_t device, const sp_upload_params
     SP_HIP(hipEventCreate(&r.ev1[0]));
     SP_HIP(hipEventCreateWithFlags(&r.ev_done[0], hipEventDisableTiming));
     for (hipEvent_t& e : r.ev_tiles.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (tm) {
-        tm->lap(tm->ms_copies);
-        const spb::BuildStats& b = tm->dev;
-        std::fprintf(stderr,
-                     "sp_upload_timing {\"builder\": \"%s\", \"bvh_mode\": %d, \"prims\": %zu, \"nodes\": %zu, \"depth\": %d, "
-                     "\"stackless\": %d, \"bounds_ms\": %.3f, \"bvh_ms\": %.3f, \"wide_ms\": %.3f, \"pack_ms\": %.3f, \"copies_ms\": %.3f, "
-                     "\"device\": {\"bounds_up_ms\": %.3f, \"codes_ms\": %.3f, \"sort_ms\": %.3f, \"hierarchy_ms\": %.3f, \"fit_ms\": %.3f, "
-                     "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}, "
-                     "\"finish\": \"%s\", \"device_finish\": {\"inputs_up_ms\": %.3f, \"collapse_ms\": %.3f, \"sums_ms\": %.3f, "
-                     "\"bases_ms\": %.3f, \"emit_ms\": %.3f, \"pack_ms\": %.3f, \"parents_ms\": %.3f, \"levels\": %d, "
-                     "\"peak_scratch_bytes\": %zu}}\n",
-                     opts.builder == SP_BUILDER_DEVICE ? "device" : "host", opts.bvh_mode, n_slots, n_nodes,
-                     bvh.max_depth, d.stackless, tm->ms_bounds, tm->ms_bvh, tm->ms_wide, tm->ms_pack, tm->ms_copies, b.ms_bounds_up,
-                     b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes,
-                     dev_finish ? "device" : "host", tm->fin.ms_inputs_up, tm->fin.ms_collapse, tm->fin.ms_sums, tm->fin.ms_bases,
-                     tm->fin.ms_emit, tm->fin.ms_pack, tm->fin.ms_parents, tm->fin.levels, tm->fin.peak_bytes);
-    }
     return SP_OK;
 }
 
-// No C++ exception crosses the C ABI: host-side failures (allocation, BVH encoding limits)
-// come back as error codes with sp_last_error() set.
+static void print_upload_timing(const UploadCall& c)
+{
+    const UploadTiming&     t = *c.tm;
+    const spb::BuildStats&  b = t.dev;
+    const spf::FinishStats& f = t.fin;
+    std::fprintf(stderr,
+                 "sp_upload_timing {\"builder\": \"%s\", \"bvh_mode\": %d, \"prims\": %zu, \"nodes\": %zu, \"depth\": %d, "
+                 "\"stackless\": %d, \"bounds_ms\": %.3f, \"bvh_ms\": %.3f, \"wide_ms\": %.3f, \"pack_ms\": %.3f, \"copies_ms\": %.3f, "
+                 "\"device\": {\"bounds_up_ms\": %.3f, \"codes_ms\": %.3f, \"sort_ms\": %.3f, \"hierarchy_ms\": %.3f, \"fit_ms\": %.3f, "
+                 "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}, "
+                 "\"finish\": \"%s\", \"device_finish\": {\"inputs_up_ms\": %.3f, \"collapse_ms\": %.3f, \"sums_ms\": %.3f, "
+                 "\"bases_ms\": %.3f, \"emit_ms\": %.3f, \"pack_ms\": %.3f, \"parents_ms\": %.3f, \"levels\": %d, "
+                 "\"peak_scratch_bytes\": %zu}}\n",
+                 c.opts.builder == SP_BUILDER_DEVICE ? "device" : "host", c.opts.bvh_mode, c.accel.n_slots, c.accel.n_nodes,
+                 c.accel.bvh.max_depth, c.s->dev.stackless, t.ms_bounds, t.ms_bvh, t.ms_wide, t.ms_pack, t.ms_copies, b.ms_bounds_up,
+                 b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes,
+                 c.device_finish() ? "device" : "host", f.ms_inputs_up, f.ms_collapse, f.ms_sums, f.ms_bases, f.ms_emit, f.ms_pack,
+                 f.ms_parents, f.levels, f.peak_bytes);
+}
+
+// Everything after the arguments; `device` and `opts`, which make the scene resident, are set last
+static int build_residency(UploadCall& c)
+{
+    sp_scene*         s = c.s;
+    const sph::Scene& h = *s->host;
+    HostAccel&        a = c.accel;
+    SP_HIP(hipSetDevice(c.device));
+    const auto& rc = sph::rsqrt_active();
+    if (rc.entries.empty()) return fail(SP_ERR_UNSUPPORTED, "RSQRTSS table capture failed");
+    if (!rc.verified) return fail(SP_ERR_UNSUPPORTED, "RSQRTSS table could not be verified on this host CPU");
+    std::vector<spd::Material> mats;
+    SP_TRY(convert_materials(h, mats));
+    c.timing = UploadTiming{}; // the stage times start here
+    build_trees(h, a, c.opts, BuildOn::DEVICE, c.tm, c.device_finish() ? &c.dtree : nullptr);
+    std::vector<sph::PrimBounds>().swap(a.bounds); // nothing below reads them: not held beside the records
+    if (!c.device_finish()) finish_host(h, a, c.opts, c.tm);
+    SP_TRY(upload_scene_arrays(c));
+    SP_TRY(c.device_finish() ? run_device_finish(c) : upload_finish_host(c));
+    SP_TRY(upload_envs(c));
+    SP_TRY(s->upload(mats, &s->dev.materials));
+    SP_TRY(upload_rsqrt_table(c, rc));
+    s->sizes.geom_depth  = a.bvh.max_depth;
+    s->sizes.light_depth = a.lbvh.max_depth;
+    s->sizes.geom_nodes  = a.n_nodes;
+    s->sizes.geom_slots  = a.n_slots;
+    apply_walk_plan(c);
+    SP_TRY(create_render_handles(s));
+    if (c.tm) {
+        c.tm->lap(c.tm->ms_copies);
+        print_upload_timing(c);
+    }
+    s->opts   = c.opts;
+    s->device = c.device;
+    return SP_OK;
+}
+
+// No C++ exception crosses the C ABI: host-side failures (allocation, BVH encoding limits) come
+// back as error codes with sp_last_error() set.  Refused arguments leave the scene as it was; a
+// build that fails half way, by code or by exception, leaves no resident scene.
 int sp_scene_upload_with(sp_scene* s, int32_t device, const sp_upload_params* params, const sp_build_params* build)
 {
     if (!s) return fail(SP_ERR_ARG, "null scene");
     std::lock_guard<std::mutex> lock(s->mu);
+    bool building = false;
+    int  rc       = SP_OK;
     try {
-        return scene_upload_impl(s, device, params, build);
-    } catch (const sph::SpError& e) {
-        s->release(); // a build that failed half way leaves no resident scene
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
+        UploadCall c{ s, device, UploadHooks::from_env() };
+        bool       resident = false;
+        SP_TRY(validate_upload(c, params, build, resident));
+        if (resident) return SP_OK;
+        if (c.hooks.timing) c.tm = &c.timing;
+        building = true;
         s->release();
-        return fail(SP_ERR_UNSUPPORTED, std::string("scene upload failed: ") + e.what());
+        ++s->generation;
+        rc = build_residency(c);
+    } catch (const sph::SpError& e) {
+        rc = fail(e.code, e.what());
+    } catch (const std::exception& e) {
+        rc = fail(SP_ERR_UNSUPPORTED, std::string("scene upload failed: ") + e.what());
     }
+    if (rc != SP_OK && building) s->release();
+    return rc;
 }
+#undef SP_TRY
 
 int sp_scene_upload_ex(sp_scene* s, int32_t device, const sp_upload_params* params)
 {
@@ -2559,31 +2669,27 @@ int sp_write_pfm(const char* path, int32_t width, int32_t height, const float* i
     return SP_OK;
 }
 
+// ---- what an upload would build (host only), and what a resident scene holds ------------------------
+
 int sp_scene_bvh_build_info(const sp_scene* s, int32_t bvh_mode, sp_bvh_info* out)
 {
     if (!s || !out) return fail(SP_ERR_ARG, "null argument");
-    if (bvh_mode != 0 && bvh_mode != 1) return fail(SP_ERR_ARG, "bvh_mode must be 0 (SAH) or 1 (reference)");
     try {
-        const sph::Scene&    h = *s->host;
-        std::vector<int32_t> prims;
-        size_t               part = 0;
-        sp_upload_params up{};
+        sp_upload_params up{}; // (resolve_opts refuses a bvh_mode that is neither 0 nor 1)
         up.bvh_mode = bvh_mode;
         UploadOpts opts;
-        if (int rc0 = resolve_upload(&up, opts)) return rc0;
-        if (int rc0 = resolve_build(nullptr, opts)) return rc0;
-        const sph::Bvh       bvh  = geometry_bvh(h, opts, prims, part);
-        *out                      = sp_bvh_info{};
-        out->depth                = bvh.max_depth;
-        out->nodes                = (int64_t)bvh.nodes.size();
-        out->slots                = (int64_t)bvh.prim_order.size();
-        std::vector<int32_t> lids;
-        size_t               lpart = 0;
-        out->light_depth           = light_bvh(h, lids, lpart).max_depth;
-        const bool stackless       = stackless_for(opts, std::max(out->depth, out->light_depth));
-        if (wide_enabled(opts) && !bvh.nodes.empty() && !stackless) out->wide_depth = sph::build_wide(bvh).depth;
-        out->stack_depth = stackless ? 0 : stack_entries(out->depth, out->wide_depth, out->light_depth,
-                                                          out->wide_depth && opts.wide_closest);
+        if (int rc = resolve_opts(&up, nullptr, UploadHooks::from_env(), opts)) return rc;
+        HostAccel a;
+        build_trees(*s->host, a, opts, BuildOn::HOST);
+        std::vector<sph::PrimBounds>().swap(a.bounds);
+        *out             = sp_bvh_info{};
+        out->depth       = a.bvh.max_depth;
+        out->nodes       = (int64_t)a.n_nodes;
+        out->slots       = (int64_t)a.n_slots;
+        out->light_depth = a.lbvh.max_depth;
+        // the wide tree for its depth alone, no records (both collapses give the same tree)
+        if (a.want_wide) out->wide_depth = sph::build_wide(a.bvh).depth;
+        out->stack_depth = walk_plan(opts, out->depth, out->light_depth, out->wide_depth).stack_depth;
         return SP_OK;
     } catch (const std::exception& e) {
         return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
@@ -2610,68 +2716,34 @@ int fill_check(const sph::Bvh& bvh, const std::vector<sph::PrimBounds>& bounds, 
     out->hash             = c.hash;
     return SP_OK;
 }
-} // namespace
 
-int sp_scene_bvh_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build, sp_bvh_check* out)
+// sp_wide_check from the arrays a render reads
+int fill_wide_check(const HostAccel& a, int finish, sp_wide_check* out)
 {
-    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
-    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
-    UploadOpts opts;
-    if (int rc0 = resolve_upload(params, opts)) return rc0;
-    if (int rc0 = resolve_build(build, opts)) return rc0;
-    try {
-        std::vector<int32_t>         prims;
-        size_t                       part = 0;
-        std::vector<sph::PrimBounds> bounds;
-        const sph::Bvh               bvh = geometry_bvh(*s->host, opts, prims, part, false, nullptr, &bounds);
-        return fill_check(bvh, bounds, opts, out);
-    } catch (const sph::SpError& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
+    const uint32_t sz = out->struct_size;
+    *out              = sp_wide_check{};
+    out->struct_size  = sz;
+    out->finish       = finish;
+    if (!a.wide.words.empty()) {
+        const sph::WideCheck c = sph::check_wide(a.wide, a.bvh.prim_order, a.bounds);
+        out->records          = c.records;
+        out->holes            = c.holes;
+        out->slots            = c.slots;
+        out->depth            = c.depth;
+        out->errors           = c.errors;
+        out->first_error_kind = c.first_error_kind;
+        out->first_error_node = c.first_error_node;
+        out->hash_nodes       = c.hash_nodes;
     }
+    uint64_t h = sph::fnv1a64(a.slot_tri.data(), a.slot_tri.size() * sizeof(float4));
+    h          = sph::fnv1a64(a.slot_code.data(), a.slot_code.size() * sizeof(uint32_t), h);
+    out->hash_records = sph::fnv1a64(a.wslot_tri.data(), a.wslot_tri.size() * sizeof(float4), h);
+    out->hash_parents = a.walk.stackless ? sph::fnv1a64(a.parents.data(), a.parents.size() * sizeof(uint32_t)) : 0;
+    return SP_OK;
 }
 
-int sp_scene_bvh_check(sp_scene* s, sp_bvh_check* out)
-{
-    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
-    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
-    try {
-        SP_HIP(hipSetDevice(s->device));
-        sph::Bvh bvh;
-        bvh.nodes.resize(s->geom_nodes);
-        bvh.max_depth = s->geom_depth;
-        std::vector<uint32_t> codes(s->geom_slots);
-        SP_HIP(hipDeviceSynchronize()); // queued renders read these arrays; nothing writes them
-        if (!bvh.nodes.empty()) SP_HIP(hipMemcpy(bvh.nodes.data(), s->dev.nodes, bvh.nodes.size() * sizeof(sph::BvhNode), hipMemcpyDeviceToHost));
-        if (!codes.empty()) SP_HIP(hipMemcpy(codes.data(), s->dev.slot_code, codes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        // slot -> bounded primitive: each primitive's code (kind, index) names it
-        const sph::Scene&            h = *s->host;
-        std::vector<int32_t>         prims;
-        size_t                       part = 0;
-        std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
-        std::vector<std::pair<uint32_t, int32_t>> by_code(part);
-        for (size_t i = 0; i < part; ++i) by_code[i] = { code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]), (int32_t)i };
-        std::sort(by_code.begin(), by_code.end());
-        std::vector<uint8_t> taken(part, 0);
-        bvh.prim_order.resize(codes.size());
-        for (size_t sl = 0; sl < codes.size(); ++sl) {
-            auto it = std::lower_bound(by_code.begin(), by_code.end(), std::make_pair(codes[sl], (int32_t)0));
-            while (it != by_code.end() && it->first == codes[sl] && taken[(size_t)(it - by_code.begin())]) ++it; // a scene may list a primitive twice
-            if (it == by_code.end() || it->first != codes[sl]) bvh.prim_order[sl] = -1; // the checker reports it
-            else { taken[(size_t)(it - by_code.begin())] = 1; bvh.prim_order[sl] = it->second; }
-        }
-        return fill_check(bvh, bounds, s->opts, out);
-    } catch (const std::exception& e) {
-        return fail(SP_ERR_UNSUPPORTED, std::string("BVH check failed: ") + e.what());
-    }
-}
-
-namespace {
 // slot -> index into `by` of the entry with that code; entries sharing a code (a scene may list a
-// primitive twice) are handed out in order, -1 when none is left
+// primitive twice) are handed out in order, -1 when none is left (the checkers report it)
 void match_codes(const std::vector<uint32_t>& codes, const std::vector<uint32_t>& by, std::vector<int32_t>& out)
 {
     std::vector<std::pair<uint32_t, int32_t>> by_code(by.size());
@@ -2688,65 +2760,94 @@ void match_codes(const std::vector<uint32_t>& codes, const std::vector<uint32_t>
     }
 }
 
-// sp_wide_check from the arrays a render reads
-int fill_wide_check(const sph::WideBvh& wide, const std::vector<int32_t>& prim_order, const std::vector<sph::PrimBounds>& bounds,
-                    const std::vector<float4>& slot_tri, const std::vector<uint32_t>& slot_code, const std::vector<float4>& wslot_tri,
-                    const std::vector<uint32_t>& parents, bool stackless, int finish, sp_wide_check* out)
+// The resident scene's accelerators read back into `a`, as far as the checks look: bounds, the
+// binary tree, its records (slot_code alone unless `finish`), and with `finish` the wide tree, its
+// records and the parent links.  Each primitive's code (kind, index) names it: slot -> bounded
+// primitive, and wide slot -> slot.
+int download_accel(const sp_scene* s, HostAccel& a, bool finish)
 {
-    const uint32_t sz = out->struct_size;
-    *out              = sp_wide_check{};
-    out->struct_size  = sz;
-    out->finish       = finish;
-    if (!wide.words.empty()) {
-        const sph::WideCheck c = sph::check_wide(wide, prim_order, bounds);
-        out->records          = c.records;
-        out->holes            = c.holes;
-        out->slots            = c.slots;
-        out->depth            = c.depth;
-        out->errors           = c.errors;
-        out->first_error_kind = c.first_error_kind;
-        out->first_error_node = c.first_error_node;
-        out->hash_nodes       = c.hash_nodes;
-    }
-    uint64_t h = sph::fnv1a64(slot_tri.data(), slot_tri.size() * sizeof(float4));
-    h          = sph::fnv1a64(slot_code.data(), slot_code.size() * sizeof(uint32_t), h);
-    out->hash_records = sph::fnv1a64(wslot_tri.data(), wslot_tri.size() * sizeof(float4), h);
-    out->hash_parents = stackless ? sph::fnv1a64(parents.data(), parents.size() * sizeof(uint32_t)) : 0;
+    SP_HIP(hipSetDevice(s->device));
+    SP_HIP(hipDeviceSynchronize()); // queued renders read these arrays; nothing writes them
+    auto down = [&](auto& vec, const void* src) -> hipError_t {
+        if (vec.empty()) return hipSuccess;
+        if (!src) return hipErrorInvalidValue;
+        return hipMemcpy(vec.data(), src, vec.size() * sizeof(vec[0]), hipMemcpyDeviceToHost);
+    };
+    const sph::Scene&    h  = *s->host;
+    const spd::Scene&    d  = s->dev;
+    const ResidentSizes& sz = s->sizes;
+    a.bounds                = bounded_prims(h, a.prims, a.part);
+    a.bvh.max_depth         = sz.geom_depth;
+    a.bvh.nodes.resize(sz.geom_nodes);
+    a.slot_code.resize(sz.geom_slots);
+    SP_HIP(down(a.bvh.nodes, d.nodes));
+    SP_HIP(down(a.slot_code, d.slot_code));
+    std::vector<uint32_t> prim_codes(a.part);
+    for (size_t i = 0; i < a.part; ++i) prim_codes[i] = code_of(h.prim_kind[a.prims[i]], h.prim_index[a.prims[i]]);
+    match_codes(a.slot_code, prim_codes, a.bvh.prim_order);
+    if (!finish) return SP_OK;
+    a.walk.stackless = d.stackless != 0;
+    a.slot_tri.resize(sz.geom_slots * 3);
+    a.parents.resize(d.stackless ? sz.geom_nodes : 0);
+    a.wslot_tri.resize(d.wnodes ? sz.wide_slots * 3 : 0);
+    a.wide.words.resize(d.wnodes ? sz.wide_records * 20 : 0);
+    a.wide.depth = d.wnodes ? sz.wide_depth : 0;
+    SP_HIP(down(a.wide.words, d.wnodes));
+    SP_HIP(down(a.slot_tri, d.slot_tri));
+    SP_HIP(down(a.wslot_tri, d.wslot_tri));
+    SP_HIP(down(a.parents, d.parents));
+    std::vector<uint32_t> wcodes(a.wslot_tri.size() / 3);
+    for (size_t i = 0; i < wcodes.size(); ++i) std::memcpy(&wcodes[i], &a.wslot_tri[3 * i].w, 4);
+    match_codes(wcodes, a.slot_code, a.wide.slot_of);
     return SP_OK;
 }
+
+// The body of the four checks.  With `build`: what an upload with these options would make, on the
+// host alone; without: the resident scene read back (the caller holds its lock).  Then the binary
+// tree's check or, given `wide`, the finish's.
+int check_scene(const sp_scene* s, const UploadOpts* build, sp_bvh_check* bvh, sp_wide_check* wide)
+{
+    const UploadOpts& opts = build ? *build : s->opts;
+    try {
+        HostAccel a;
+        if (build) {
+            build_trees(*s->host, a, opts, BuildOn::HOST);
+            if (wide) finish_host(*s->host, a, opts);
+        } else if (int rc = download_accel(s, a, wide != nullptr)) return rc;
+        return wide ? fill_wide_check(a, opts.finish, wide) : fill_check(a.bvh, a.bounds, opts, bvh);
+    } catch (const std::exception& e) { // a build keeps its own code; a read-back has none to keep
+        const sph::SpError* se = build ? dynamic_cast<const sph::SpError*>(&e) : nullptr;
+        if (se) return fail(se->code, e.what());
+        return fail(SP_ERR_UNSUPPORTED, std::string(build ? "BVH build" : wide ? "wide BVH check" : "BVH check") + " failed: " + e.what());
+    }
+}
 } // namespace
+
+int sp_scene_bvh_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build, sp_bvh_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
+    UploadOpts opts;
+    if (int rc = resolve_opts(params, build, UploadHooks::from_env(), opts)) return rc;
+    return check_scene(s, &opts, out, nullptr);
+}
+
+int sp_scene_bvh_check(sp_scene* s, sp_bvh_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
+    return check_scene(s, nullptr, out, nullptr);
+}
 
 int sp_scene_wide_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build, sp_wide_check* out)
 {
     if (!s || !out) return fail(SP_ERR_ARG, "null argument");
     if (out->struct_size != sizeof(sp_wide_check)) return fail(SP_ERR_ARG, "sp_wide_check.struct_size is not a known size");
     UploadOpts opts;
-    if (int rc0 = resolve_upload(params, opts)) return rc0;
-    if (int rc0 = resolve_build(build, opts)) return rc0;
-    try {
-        const sph::Scene&            h = *s->host;
-        std::vector<int32_t>         prims, lids;
-        size_t                       part = 0, lpart = 0;
-        std::vector<sph::PrimBounds> bounds;
-        const sph::Bvh               bvh = geometry_bvh(h, opts, prims, part, false, nullptr, &bounds);
-        const bool stackless = stackless_for(opts, std::max(bvh.max_depth, light_bvh(h, lids, lpart).max_depth));
-        std::vector<float4>   slot_tri, wslot_tri;
-        std::vector<uint32_t> slot_code, parents;
-        pack_records(h, prims, bvh.prim_order, slot_tri, slot_code);
-        sph::WideBvh wide;
-        if (wide_enabled(opts) && !bvh.nodes.empty() && !stackless) {
-            wide = opts.finish == SP_FINISH_DEVICE ? sph::build_wide_levels(bvh) : sph::build_wide(bvh);
-            wslot_tri.resize(wide.slot_of.size() * 3);
-            for (size_t i = 0; i < wide.slot_of.size(); ++i)
-                for (int k = 0; k < 3; ++k) wslot_tri[3 * i + k] = slot_tri[3 * (size_t)wide.slot_of[i] + k];
-        }
-        if (stackless) parents = parent_links(bvh.nodes);
-        return fill_wide_check(wide, bvh.prim_order, bounds, slot_tri, slot_code, wslot_tri, parents, stackless, opts.finish, out);
-    } catch (const sph::SpError& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SP_ERR_UNSUPPORTED, std::string("BVH build failed: ") + e.what());
-    }
+    if (int rc = resolve_opts(params, build, UploadHooks::from_env(), opts)) return rc;
+    return check_scene(s, &opts, nullptr, out);
 }
 
 int sp_scene_wide_check(sp_scene* s, sp_wide_check* out)
@@ -2755,47 +2856,14 @@ int sp_scene_wide_check(sp_scene* s, sp_wide_check* out)
     if (out->struct_size != sizeof(sp_wide_check)) return fail(SP_ERR_ARG, "sp_wide_check.struct_size is not a known size");
     std::lock_guard<std::mutex> lock(s->mu);
     if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
-    try {
-        SP_HIP(hipSetDevice(s->device));
-        SP_HIP(hipDeviceSynchronize()); // queued renders read these arrays; nothing writes them
-        auto down = [&](auto& vec, const void* src) -> hipError_t {
-            if (vec.empty()) return hipSuccess;
-            if (!src) return hipErrorInvalidValue;
-            return hipMemcpy(vec.data(), src, vec.size() * sizeof(vec[0]), hipMemcpyDeviceToHost);
-        };
-        const spd::Scene&     d = s->dev;
-        sph::WideBvh          wide;
-        std::vector<float4>   slot_tri(s->geom_slots * 3), wslot_tri(d.wnodes ? s->wide_slots * 3 : 0);
-        std::vector<uint32_t> slot_code(s->geom_slots), parents(d.stackless ? s->geom_nodes : 0);
-        wide.words.resize(d.wnodes ? s->wide_records * 20 : 0);
-        wide.depth = d.wnodes ? s->wide_depth : 0;
-        SP_HIP(down(wide.words, d.wnodes));
-        SP_HIP(down(slot_tri, d.slot_tri));
-        SP_HIP(down(wslot_tri, d.wslot_tri));
-        SP_HIP(down(slot_code, d.slot_code));
-        SP_HIP(down(parents, d.parents));
-        // slot -> bounded primitive and wide slot -> slot: each primitive's code (kind, index) names it
-        const sph::Scene&            h = *s->host;
-        std::vector<int32_t>         prims;
-        size_t                       part = 0;
-        std::vector<sph::PrimBounds> bounds = bounded_prims(h, prims, part);
-        std::vector<uint32_t>        prim_codes(part), wcodes(wslot_tri.size() / 3);
-        for (size_t i = 0; i < part; ++i) prim_codes[i] = code_of(h.prim_kind[prims[i]], h.prim_index[prims[i]]);
-        for (size_t i = 0; i < wcodes.size(); ++i) std::memcpy(&wcodes[i], &wslot_tri[3 * i].w, 4);
-        std::vector<int32_t> prim_order;
-        match_codes(slot_code, prim_codes, prim_order);
-        match_codes(wcodes, slot_code, wide.slot_of);
-        return fill_wide_check(wide, prim_order, bounds, slot_tri, slot_code, wslot_tri, parents, d.stackless != 0, s->opts.finish, out);
-    } catch (const std::exception& e) {
-        return fail(SP_ERR_UNSUPPORTED, std::string("wide BVH check failed: ") + e.what());
-    }
+    return check_scene(s, nullptr, nullptr, out);
 }
 
 int sp_scene_device_bytes(const sp_scene* s, int64_t* bytes)
 {
     if (!s || !bytes || s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
     int64_t b = 0;
-    for (const auto& d : s->bufs) b += (int64_t)d.bytes;
+    for (const auto& d : s->bufs) b += (int64_t)d.cap;
     *bytes = b;
     return SP_OK;
 }
@@ -2803,9 +2871,9 @@ int sp_scene_device_bytes(const sp_scene* s, int64_t* bytes)
 int sp_scene_bvh_info(const sp_scene* s, int32_t* depth, int64_t* nodes, int64_t* slots)
 {
     if (!s || s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
-    if (depth) *depth = s->geom_depth;
-    if (nodes) *nodes = (int64_t)s->geom_nodes;
-    if (slots) *slots = (int64_t)s->geom_slots;
+    if (depth) *depth = s->sizes.geom_depth;
+    if (nodes) *nodes = (int64_t)s->sizes.geom_nodes;
+    if (slots) *slots = (int64_t)s->sizes.geom_slots;
     return SP_OK;
 }
 

@@ -221,15 +221,13 @@ __global__ __launch_bounds__(BLOCK) void fw_parents(const Node* __restrict__ nod
 
 uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) / BLOCK); }
 
-// the outputs: freed unless handed over
+// the caller's outputs while they are filled: emptied again unless the finish ends well
 struct Outputs {
-    FinishOut o;
-    bool      keep = false;
+    FinishOut& o;
+    bool       keep = false;
     ~Outputs()
     {
-        if (keep) return;
-        for (void* p : { o.wnodes, o.wslot_tri, o.slot_tri, o.slot_code, o.parents })
-            if (p) (void)hipFree(p);
+        if (!keep) o.reset();
     }
 };
 
@@ -237,8 +235,8 @@ struct Outputs {
 
 int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::string& err, bool timed)
 {
-    out = FinishOut{};
-    st  = FinishStats{};
+    out.reset();
+    st = FinishStats{};
     using clock = std::chrono::steady_clock;
     auto t0     = clock::now();
     auto lap    = [&](double& ms) {
@@ -248,7 +246,7 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
         t0 = t1;
     };
     spb::Arena mem;
-    Outputs    res;
+    Outputs    res{ out };
     auto       failed = [&](const char* what, hipError_t e) {
         err = std::string("device finish: ") + what + ": " + hipGetErrorString(e);
         (void)hipGetLastError();
@@ -398,7 +396,6 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
     lap(st.ms_pack);
     st.peak_bytes = mem.peak;
     res.keep      = true;
-    out           = res.o;
 #undef SPF_HIP
     return SP_OK;
 }

@@ -6,6 +6,8 @@
 
 #include "../host/sp_host.hpp"
 
+#include <hip/hip_runtime.h>
+
 #include <string>
 
 namespace spf {
@@ -31,12 +33,28 @@ struct FinishIn {
     bool                want_wide = false, want_parents = false;
 };
 
-// Device buffers the caller takes over (hipFree) on SP_OK; nullptr where there is nothing.
+// Device buffers for the caller to take over on SP_OK; nullptr where there is nothing.  It owns
+// them: what the caller has not taken (sp_scene::adopt nulls the pointer it takes) is freed with it.
 struct FinishOut {
     void *   wnodes = nullptr, *wslot_tri = nullptr, *slot_tri = nullptr, *slot_code = nullptr, *parents = nullptr;
     size_t   wnodes_bytes = 0, wslot_tri_bytes = 0, slot_tri_bytes = 0, slot_code_bytes = 0, parents_bytes = 0;
     uint32_t records = 0, wide_slots = 0;
     int      depth = 0;
+
+    FinishOut() = default;
+    FinishOut(const FinishOut&) = delete;
+    FinishOut& operator=(const FinishOut&) = delete;
+    ~FinishOut() { reset(); }
+    void reset()
+    {
+        for (void** p : { &wnodes, &wslot_tri, &slot_tri, &slot_code, &parents }) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        wnodes_bytes = wslot_tri_bytes = slot_tri_bytes = slot_code_bytes = parents_bytes = 0;
+        records = wide_slots = 0;
+        depth   = 0;
+    }
 };
 
 // Runs on the current device.  SP_OK, or SP_ERR_HIP with `err` set: nothing stays allocated and

@@ -133,6 +133,39 @@ def test_depth_is_consistent_with_the_stack_decision(sets, monkeypatch):
         monkeypatch.delenv("SP_DEVICE_BUILD")
 
 
+@pytest.mark.parametrize("hook", ["default", "stack_max", "wide_closest_off"])
+@pytest.mark.parametrize("builder", ["host", "device"])
+@pytest.mark.parametrize("name", ["wedge_strip", "tri1025", "mixed"])
+def test_walk_plan_is_one_across_entry_points(sets, monkeypatch, name, builder, hook):
+    # sp_scene_bvh_build_info and sp_scene_wide_build_check both go through build_trees and
+    # walk_plan: what one reports as the stack, the other shows as parent links or a wide tree
+    scene = sp.Scene.from_file(sets[name][0])
+    depth = scene.bvh_build_check(builder=builder)["depth"]
+    if builder == "device":
+        monkeypatch.setenv("SP_DEVICE_BUILD", "1")  # (the finish follows: the level-wise collapse)
+    if hook == "stack_max":
+        monkeypatch.setenv("SP_STACK_MAX", str(max(1, depth - 1)))
+    if hook == "wide_closest_off":
+        monkeypatch.setenv("SP_WIDE_CLOSEST", "0")
+    info = scene.bvh_build_info(0)
+    chk = scene.wide_build_check()
+    print(name, builder, hook, info, chk)
+    assert info["depth"] == depth and chk["errors"] == 0
+    assert chk["finish"] == builder
+    assert (info["stack_depth"] == 0) == (chk["hash_parents"] != 0), (info, chk)
+    assert (info["wide_depth"] == 0) == (chk["records"] == 0), (info, chk)
+    assert info["wide_depth"] == chk["depth"]
+    stackless = hook == "stack_max" or max(depth, info["light_depth"]) + 1 > 96
+    assert (info["stack_depth"] == 0) == stackless
+    if stackless:
+        assert chk["records"] == 0  # a scene without a stack walks the binary tree only
+    elif hook == "wide_closest_off":
+        assert info["stack_depth"] == max(depth, info["wide_depth"], info["light_depth"]) + 1
+    else:
+        assert info["wide_depth"] > 0
+        assert info["stack_depth"] == max(2 * (info["wide_depth"] + 1), info["light_depth"] + 1)
+
+
 def test_device_build_hook_is_ignored_for_the_reference_order(scene_dir, monkeypatch):
     scene = sp.Scene.from_file(os.path.join(scene_dir, "bunny.sp"))
     plain = scene.bvh_build_check(builder="auto", bvh_mode=1)
