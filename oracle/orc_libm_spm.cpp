@@ -11,4 +11,8 @@ float orc_powf(float x, float y) { return spm::lm_powf(x, y); }
 float orc_erff(float x) { return spm::lm_erff(x); }
 float orc_acosf(float x) { return spm::lm_acosf(x); }
 float orc_atan2f(float y, float x) { return spm::lm_atan2f(y, x); }
+float orc_atanf(float x) { return spm::lm_atanf(x); }
+void  orc_sincosf(float x, float* s, float* c) { spm::lm_sincosf(x, s, c); }
+float orc_fmod1(float x) { return spm::fmod1(x); }
+float orc_roundf(float x) { return spm::round_f(x); }
 }

@@ -32,6 +32,10 @@ float orc_powf(float, float);
 float orc_erff(float);
 float orc_acosf(float);
 float orc_atan2f(float, float);
+float orc_atanf(float);
+void  orc_sincosf(float, float*, float*);
+float orc_fmod1(float);  /* std::fmod(x, 1.0f) */
+float orc_roundf(float); /* std::round */
 
 /* ------------------------------------------------------------------ math (math/*.h) */
 typedef struct { float x, y, z; } V3;
@@ -340,10 +344,9 @@ static int plane_isect(const Aff* w2o, const Lin* nrm, const Ray* ray, float tmi
     return 1;
 }
 /* Triangle::intersect_impl (shapes/Triangle.h:97) */
-static int tri_isect(const sp_scene_desc* sd, int tri, const Ray* ray, float tmin, float tmax, Isect* out)
+/* the arithmetic of Triangle::intersect_impl from the three corners: t, beta, gamma of a hit */
+static int tri_core(V3 p0, V3 p1, V3 p2, const Ray* ray, float tmin, float tmax, float* t_out, float* beta_out, float* gamma_out)
 {
-    const uint32_t* id = sd->indices + 3 * tri;
-    V3 p0 = from3(sd->vertices + 3 * id[0]), p1 = from3(sd->vertices + 3 * id[1]), p2 = from3(sd->vertices + 3 * id[2]);
     float A = p0.x - p1.x, B = p0.y - p1.y, C = p0.z - p1.z;
     float D = p0.x - p2.x, E = p0.y - p2.y, F = p0.z - p2.z;
     float G = ray->d.x, H = ray->d.y, I = ray->d.z;
@@ -358,6 +361,15 @@ static int tri_isect(const sp_scene_desc* sd, int tri, const Ray* ray, float tmi
     if (gamma <= 0.0f || beta + gamma >= 1.0f) return 0;
     float t = -fmaf(F, AKJB, fmaf(E, JCAL, D * BLKC)) / denom;
     if (t < tmin || t > tmax) return 0;
+    *t_out = t; *beta_out = beta; *gamma_out = gamma;
+    return 1;
+}
+static int tri_isect(const sp_scene_desc* sd, int tri, const Ray* ray, float tmin, float tmax, Isect* out)
+{
+    const uint32_t* id = sd->indices + 3 * tri;
+    V3 p0 = from3(sd->vertices + 3 * id[0]), p1 = from3(sd->vertices + 3 * id[1]), p2 = from3(sd->vertices + 3 * id[2]);
+    float t, beta, gamma;
+    if (!tri_core(p0, p1, p2, ray, tmin, tmax, &t, &beta, &gamma)) return 0;
     if (out) {
         V3 n0 = from3(sd->normals + 3 * id[0]), n1 = from3(sd->normals + 3 * id[1]), n2 = from3(sd->normals + 3 * id[2]);
         float alpha = 1.0f - beta - gamma;
@@ -682,9 +694,8 @@ static V3 cosine_hemisphere(P2 u)
 
 /* ONB (math/ONB.h) */
 typedef struct { V3 u, v, w; } Onb;
-static Onb onb_from_v(V3 n)
+static Onb onb_of_unit(V3 v)
 {
-    V3 v = vnormalize(n);
     float sign = copysignf(1.0f, v.z);
     float a = -1.0f / (sign + v.z);
     float b = v.x * v.y * a;
@@ -693,6 +704,7 @@ static Onb onb_from_v(V3 n)
     Onb o = { b2, v, b1 };
     return o;
 }
+static Onb onb_from_v(V3 n) { return onb_of_unit(vnormalize(n)); }
 static V3 to_world(const Onb* o, V3 a) { return vadd(vadd(fmulv(a.x, o->u), fmulv(a.y, o->v)), fmulv(a.z, o->w)); }
 static V3 to_onb(const Onb* o, V3 a) { return v3(vdot(a, o->u), vdot(a, o->v), vdot(a, o->w)); }
 
@@ -1451,3 +1463,156 @@ void orc_mt_stream(uint32_t seed, int n, float* out)
     for (int i = 0; i < n; ++i) out[i] = canonical(&s);
 }
 float orc_rsqrt(float x) { return rsqrt_ref(x); }
+
+/* ------------------------------------------------------------------ leaf functions, row by row
+ * orc_unit: evaluates one leaf function of this oracle on n rows of 32-bit words, for the device
+ * unit tests (tests/cpp/device_units.hip evaluates the product's function of the same meaning on
+ * the same rows).  The row formats are tabled in tests/_units.py; 0 on success, -1 for a name
+ * this oracle does not know. */
+static inline float    w2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static inline uint32_t f2w(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static inline V3       w2v(const uint32_t* w) { return v3(w2f(w[0]), w2f(w[1]), w2f(w[2])); }
+static inline void     v2w(uint32_t* w, V3 v) { w[0] = f2w(v.x); w[1] = f2w(v.y); w[2] = f2w(v.z); }
+static Aff w2aff(const uint32_t* w) { Aff a = { w2v(w), w2v(w + 3), w2v(w + 6), w2v(w + 9) }; return a; }
+/* difference_of_products and cross (math/Vector3.h:769): cd = c*d; err = fnmadd(c,d,cd); fmsub(a,b,cd) + err */
+static inline float dop1_ref(float a, float b, float c, float d)
+{
+    float cd = c * d, err = fmaf(-c, d, cd), dop = fmaf(a, b, -cd);
+    return dop + err;
+}
+static inline V3 vcross(V3 a, V3 b)
+{
+    return v3(dop1_ref(a.y, b.z, a.z, b.y), dop1_ref(a.z, b.x, a.x, b.z), dop1_ref(a.x, b.y, a.y, b.x));
+}
+static sp_material_desc unit_material(float ax, float ay, float ior)
+{
+    sp_material_desc m;
+    memset(&m, 0, sizeof m);
+    m.kind = SP_MAT_GLOSSY; m.base = -1;
+    m.microfacet_r[0] = 1.0f; m.microfacet_r[1] = 0.5f; m.microfacet_r[2] = 0.25f;
+    m.alpha_x = ax; m.alpha_y = ay; m.microfacet_ior = ior; m.sample_visible_area = 1;
+    return m;
+}
+
+enum { U_EXPF, U_LOGF, U_SINF, U_COSF, U_ERFF, U_ACOSF, U_ATANF, U_FMOD1, U_ROUNDF, U_SINCOSF, U_SINCOSF_BOUNDED,
+       U_POWF, U_ATAN2F, U_POWF_UNIT, U_DIV, U_SQRT, U_FMA, U_MULADD, U_SQRT_UNIT, U_DOT, U_CROSS, U_DOP1,
+       U_RSQRTSS, U_RSQRT_REF, U_FRESNEL, U_ERFINV, U_BECK11, U_BECK11_PRE, U_UNIFORM_SPHERE, U_UNIFORM_HEMISPHERE,
+       U_CONCENTRIC_DISK, U_COSINE_HEMISPHERE, U_ONB_OF_UNIT, U_BECK_D, U_BECK_LAMBDA, U_BECK_PDF, U_MF_EVAL, U_MF_PDF,
+       U_SPHERICAL_PHI, U_RAY_OFFSET, U_TRI_HIT, U_SPHERE_T, U_PLANE_T, U_BOX_HIT, U_COUNT };
+static const struct { const char* name; int k, m; } unit_fns[U_COUNT] = {
+    { "expf", 1, 1 }, { "logf", 1, 1 }, { "sinf", 1, 1 }, { "cosf", 1, 1 }, { "erff", 1, 1 }, { "acosf", 1, 1 },
+    { "atanf", 1, 1 }, { "fmod1", 1, 1 }, { "roundf", 1, 1 }, { "sincosf", 1, 2 }, { "sincosf_bounded", 1, 2 },
+    { "powf", 2, 1 }, { "atan2f", 2, 1 }, { "powf_unit", 2, 2 }, { "div", 2, 1 }, { "sqrt", 1, 1 }, { "fma", 3, 1 },
+    { "muladd", 3, 1 }, { "sqrt_unit", 1, 1 }, { "dot", 6, 1 }, { "cross", 6, 3 }, { "dop1", 4, 1 },
+    { "rsqrtss", 1, 1 }, { "rsqrt_ref", 1, 1 }, { "fresnel", 3, 1 }, { "erfinv", 1, 1 }, { "beck11", 3, 2 },
+    { "beck11_pre", 7, 4 }, { "uniform_sphere", 2, 3 }, { "uniform_hemisphere", 2, 3 }, { "concentric_disk", 2, 2 },
+    { "cosine_hemisphere", 2, 3 }, { "onb_of_unit", 3, 9 }, { "beck_D", 5, 1 }, { "beck_lambda", 5, 1 },
+    { "beck_pdf", 8, 1 }, { "mf_eval", 9, 3 }, { "mf_pdf", 8, 1 }, { "spherical_phi", 3, 1 }, { "ray_offset", 6, 1 },
+    { "tri_hit", 17, 4 }, { "sphere_t", 20, 2 }, { "plane_t", 20, 2 }, { "box_hit", 14, 1 },
+};
+
+/* words per row of `function`: inputs in *k, outputs in *m; -1 for an unknown name */
+int orc_unit_arity(const char* function, int* k, int* m)
+{
+    for (int f = 0; f < U_COUNT; ++f)
+        if (strcmp(function, unit_fns[f].name) == 0) { *k = unit_fns[f].k; *m = unit_fns[f].m; return 0; }
+    return -1;
+}
+
+int orc_unit(const char* function, const uint32_t* in, int64_t n, uint32_t* out)
+{
+    int fn = -1;
+    for (int f = 0; f < U_COUNT; ++f)
+        if (strcmp(function, unit_fns[f].name) == 0) fn = f;
+    if (fn < 0) return -1;
+    const int k = unit_fns[fn].k, m = unit_fns[fn].m;
+    for (int64_t r = 0; r < n; ++r) {
+        const uint32_t* w = in + r * k;
+        uint32_t*       o = out + r * m;
+        float           x[20];
+        for (int i = 0; i < k; ++i) x[i] = w2f(w[i]);
+        memset(o, 0, (size_t)m * 4);
+        switch (fn) {
+        case U_EXPF: o[0] = f2w(orc_expf(x[0])); break;
+        case U_LOGF: o[0] = f2w(orc_logf(x[0])); break;
+        case U_SINF: o[0] = f2w(orc_sinf(x[0])); break;
+        case U_COSF: o[0] = f2w(orc_cosf(x[0])); break;
+        case U_ERFF: o[0] = f2w(orc_erff(x[0])); break;
+        case U_ACOSF: o[0] = f2w(orc_acosf(x[0])); break;
+        case U_ATANF: o[0] = f2w(orc_atanf(x[0])); break;
+        case U_FMOD1: o[0] = f2w(orc_fmod1(x[0])); break;
+        case U_ROUNDF: o[0] = f2w(orc_roundf(x[0])); break;
+        case U_SINCOSF: { float s, c; orc_sincosf(x[0], &s, &c); o[0] = f2w(s); o[1] = f2w(c); break; }
+        case U_SINCOSF_BOUNDED: o[0] = f2w(orc_sinf(x[0])); o[1] = f2w(orc_cosf(x[0])); break;
+        case U_POWF: o[0] = f2w(orc_powf(x[0], x[1])); break;
+        case U_ATAN2F: o[0] = f2w(orc_atan2f(x[0], x[1])); break;
+        case U_POWF_UNIT: o[0] = o[1] = f2w(orc_powf(x[0], x[1])); break;
+        case U_DIV: o[0] = f2w(x[0] / x[1]); break;
+        case U_SQRT: case U_SQRT_UNIT: o[0] = f2w(sqrtf(x[0])); break;
+        case U_FMA: o[0] = f2w(fmaf(x[0], x[1], x[2])); break;
+        case U_MULADD: { const float p = x[0] * x[1]; o[0] = f2w(p + x[2]); break; } /* built with -ffp-contract=off */
+        case U_DOT: o[0] = f2w(vdot(w2v(w), w2v(w + 3))); break;
+        case U_CROSS: v2w(o, vcross(w2v(w), w2v(w + 3))); break;
+        case U_DOP1: o[0] = f2w(dop1_ref(x[0], x[1], x[2], x[3])); break;
+        case U_RSQRTSS: o[0] = f2w(_mm_cvtss_f32(_mm_rsqrt_ss(_mm_set_ss(x[0])))); break;
+        case U_RSQRT_REF: o[0] = f2w(rsqrt_ref(x[0])); break;
+        case U_FRESNEL: o[0] = f2w(fresnel(x[0], x[1], x[2])); break;
+        case U_ERFINV: o[0] = f2w(erfinv_ref(x[0])); break;
+        case U_BECK11: { P2 s = beck11(x[0], x[1], x[2]); o[0] = f2w(s.x); o[1] = f2w(s.y); break; }
+        case U_BECK11_PRE: { /* wo, alpha_x, alpha_y, U1, U2: beckmann_sample's stretch, then beckmann_sample11 */
+            V3 wo = w2v(w);
+            V3 wi = (wo.y < 0.0f) ? vneg(wo) : wo;
+            V3 st = vnormalize(v3(x[3] * wi.x, wi.y, x[4] * wi.z));
+            P2 s  = beck11(st.y, x[5], x[6]);
+            o[0] = o[2] = f2w(s.x); o[1] = o[3] = f2w(s.y);
+            break;
+        }
+        case U_UNIFORM_SPHERE: { P2 u = { x[0], x[1] }; v2w(o, uniform_sphere(u)); break; }
+        case U_UNIFORM_HEMISPHERE: { P2 u = { x[0], x[1] }; v2w(o, uniform_hemisphere(u)); break; }
+        case U_CONCENTRIC_DISK: { P2 u = { x[0], x[1] }; P2 d = concentric(u); o[0] = f2w(d.x); o[1] = f2w(d.y); break; }
+        case U_COSINE_HEMISPHERE: { P2 u = { x[0], x[1] }; v2w(o, cosine_hemisphere(u)); break; }
+        case U_ONB_OF_UNIT: { Onb b = onb_of_unit(w2v(w)); v2w(o, b.u); v2w(o + 3, b.v); v2w(o + 6, b.w); break; }
+        case U_BECK_D: { sp_material_desc md = unit_material(x[0], x[1], 1.5f); o[0] = f2w(bD(&md, w2v(w + 2))); break; }
+        case U_BECK_LAMBDA: { sp_material_desc md = unit_material(x[0], x[1], 1.5f); o[0] = f2w(blambda(&md, w2v(w + 2))); break; }
+        case U_BECK_PDF: { sp_material_desc md = unit_material(x[0], x[1], 1.5f); o[0] = f2w(bpdf(&md, w2v(w + 2), w2v(w + 5))); break; }
+        case U_MF_EVAL: {
+            sp_material_desc md = unit_material(x[0], x[1], x[2]);
+            C3 c = mf_eval(&md, w2v(w + 3), w2v(w + 6));
+            o[0] = f2w(c.r); o[1] = f2w(c.g); o[2] = f2w(c.b);
+            break;
+        }
+        case U_MF_PDF: { sp_material_desc md = unit_material(x[0], x[1], 1.5f); o[0] = f2w(mf_pdf(&md, w2v(w + 2), w2v(w + 5))); break; }
+        case U_SPHERICAL_PHI: o[0] = f2w(sph_phi(w2v(w))); break;
+        case U_RAY_OFFSET: o[0] = f2w(ray_offset(w2v(w), w2v(w + 3))); break;
+        case U_TRI_HIT: { /* p0, p1, p2, o, d, tmin, tmax -> flag, t, beta, gamma */
+            Ray ray = { w2v(w + 9), w2v(w + 12) };
+            float t, b, g;
+            if (tri_core(w2v(w), w2v(w + 3), w2v(w + 6), &ray, x[15], x[16], &t, &b, &g)) {
+                o[0] = 1u; o[1] = f2w(t); o[2] = f2w(b); o[3] = f2w(g);
+            }
+            break;
+        }
+        case U_SPHERE_T: case U_PLANE_T: { /* world_to_object (vx, vy, vz, p), o, d, tmin, tmax -> flag, t */
+            Aff w2o = w2aff(w);
+            Lin id  = { v3(1, 0, 0), v3(0, 1, 0), v3(0, 0, 1) };
+            Ray ray = { w2v(w + 12), w2v(w + 15) };
+            Isect is;
+            memset(&is, 0, sizeof is);
+            const int hit = (fn == U_SPHERE_T) ? sphere_isect(&w2o, &w2o, &id, &ray, x[18], x[19], &is)
+                                               : plane_isect(&w2o, &id, &ray, x[18], x[19], &is);
+            if (hit) { o[0] = 1u; o[1] = f2w(is.t); }
+            break;
+        }
+        case U_BOX_HIT: { /* lo, hi, o, d, tmin, tmax -> flag */
+            ONode nd;
+            memset(&nd, 0, sizeof nd);
+            for (int i = 0; i < 3; ++i) { nd.lo[i] = x[i]; nd.hi[i] = x[3 + i]; }
+            Ray ray = { w2v(w + 6), w2v(w + 9) };
+            o[0] = (uint32_t)box_p(&nd, &ray, x[12], x[13]);
+            break;
+        }
+        default: return -1;
+        }
+    }
+    return 0;
+}

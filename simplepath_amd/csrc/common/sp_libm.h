@@ -13,7 +13,8 @@
 // tools/extract_glibc_libm.py for the data and addresses) and is verified exhaustively against
 // the host libm over all 2^32 inputs (powf: structured + random pairs) by
 // tests/test_libm_exact.py.  The same source is compiled for the host and for gfx950 with
-// explicit fma() and no contraction, so the host verification carries over to the device.
+// explicit fma() and no contraction; tests/test_gpu_units.py measures the gfx950 compilation
+// itself, every function on the GPU against glibc bit for bit.
 //
 // Shape: expf, logf and powf -- the functions the glossy estimate's loops call --
 // have one exit.  glibc tests for its special arguments first and returns early; on the GPU every

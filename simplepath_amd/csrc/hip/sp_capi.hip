@@ -1,5 +1,6 @@
 // sp_capi.hip -- extern "C" boundary (include/simplepath_hip.h) and HBM residency of scenes.
 #include "sp_device.hpp"
+#include "sp_rsqrt_pack.hpp"
 #include "sp_wave.hpp"
 #include "sp_chunk.hpp"
 #include "sp_launch.hpp"
@@ -1161,34 +1162,14 @@ static int upload_envs(UploadCall& c)
     return c.s->upload(envs, &d.envs);
 }
 
-// RSQRTSS table as 16-bit device entries when every entry has the same sign and exponent and
-// at least 7 trailing zero mantissa bits (Intel and AMD hosts alike: exponent 126, 12
-// significant bits): half the LDS each shading block copies it into (sp_math.h).
+// RSQRTSS table in its device form (sp_rsqrt_pack.hpp: 16-bit entries where the table allows it)
 static int upload_rsqrt_table(UploadCall& c, const sph::RsqrtCapture& rc)
 {
-    spd::Scene& d        = c.s->dev;
-    int         rs_shift = 23;
-    uint32_t    rs_hi    = rc.entries[0] & 0xff800000u;
-    for (uint32_t e : rc.entries) {
-        if ((e & 0xff800000u) != rs_hi) {
-            rs_shift = 0;
-            break;
-        }
-        while (rs_shift > 0 && (e & ((1u << rs_shift) - 1u))) --rs_shift;
-    }
-    if (!c.hooks.rsqrt_pack) rs_shift = 0; // 32-bit entries (comparison)
-    if (rs_shift < 7) rs_shift = 0;
-    const uint32_t hdr[spd::RSQ_HDR] = { (uint32_t)rc.bits, rc.zero_result, rc.denorm_result, (uint32_t)rs_shift,
-                                         rs_shift ? rs_hi : 0u, 0u, 0u, 0u };
-    std::vector<uint32_t> words(hdr, hdr + spd::RSQ_HDR);
-    if (rs_shift) {
-        std::vector<uint16_t> packed(rc.entries.size());
-        for (size_t i = 0; i < packed.size(); ++i) packed[i] = (uint16_t)((rc.entries[i] & 0x7fffffu) >> rs_shift);
-        words.resize(spd::RSQ_HDR + (packed.size() + 1) / 2, 0u);
-        std::memcpy(words.data() + spd::RSQ_HDR, packed.data(), packed.size() * sizeof(uint16_t));
-    } else {
-        words.insert(words.end(), rc.entries.begin(), rc.entries.end());
-    }
+    spd::Scene& d = c.s->dev;
+    const std::vector<uint32_t> words = spd::rsqrt_device_words(rc.entries.data(), rc.entries.size(), rc.bits, rc.zero_result,
+                                                                rc.denorm_result, c.hooks.rsqrt_pack);
+    const int      rs_shift = (int)words[3];
+    const uint32_t rs_hi    = words[4];
     SP_TRY(c.s->upload(words, &d.rsqrt_entries));
     d.rsqrt_shift  = rs_shift;
     d.rsqrt_hi     = rs_shift ? rs_hi : 0u;

@@ -3,7 +3,8 @@
 Runs tools/libm_exhaustive.cpp (same header, compiled for the host without FP contraction) on a
 strided sample of all 2^32 inputs per function (the full sweep's log is tests/golden/
 libm_exhaustive_full.txt).  The device build compiles the identical source with explicit fma()
-and -ffp-contract=off, so host equality carries over; the GPU parity tests check it end to end."""
+and -ffp-contract=off; tests/test_gpu_units.py measures that compilation, function by function on
+the GPU against glibc, and the GPU parity tests check it end to end."""
 import os
 import subprocess
 
