@@ -102,6 +102,24 @@ public:
     void upload(int device = 0, int bvh_mode = 0) const { check(sp_scene_upload(m_s, device, bvh_mode)); }
     // ... with explicit accelerator options (sp_upload_params, ABI 4)
     void upload(int device, const sp_upload_params& params) const { check(sp_scene_upload_ex(m_s, device, &params)); }
+    // A moved mesh (sp_scene_update_mesh): num_vertices x 3 world-space positions, and normals or
+    // nullptr.  The host mesh is overwritten; a scene resident with bvh_mode 0 is refitted on the
+    // device -- its trees keep their shape, nothing is uploaded again -- and progress objects made on
+    // it become invalid.  With stage_times the call waits for the device after each stage and returns
+    // its statistics (refitted 0: the scene was not resident); without, a zeroed struct.
+    sp_refit_stats update_mesh(const float* vertices, int64_t num_vertices, const float* normals = nullptr,
+                               bool stage_times = false) const
+    {
+        sp_mesh_update u{};
+        u.struct_size  = sizeof(u);
+        u.vertices     = vertices;
+        u.normals      = normals;
+        u.num_vertices = num_vertices;
+        sp_refit_stats st{};
+        st.struct_size = sizeof(st);
+        check(sp_scene_update_mesh(m_s, &u, stage_times ? &st : nullptr));
+        return st;
+    }
     sp_scene* handle() const noexcept { return m_s; }
 
     // The reference's public Scene members (base/Scene.h:90-96), as read after loading.  They are

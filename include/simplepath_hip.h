@@ -23,6 +23,7 @@
  *                                         (shapes/BVHAccelerator.h:173), host only: statistics
  *   sp_scene_upload_with                  the same upload with the binary BVH built on the device
  *   sp_scene_bvh_check / _bvh_build_check (no counterpart: structural check of a built BVH)
+ *   sp_scene_update_mesh                  (no counterpart: a moved mesh shown by refitting the resident BVHs)
  *   sp_render_tiles                       main.cpp:77-107 `render_thread`: for each scheduled
  *                                         tile, for each pixel, num_pixel_samples x
  *                                         `integrator.integrate(camera.generate_ray(...))`,
@@ -578,6 +579,70 @@ int  sp_scene_wide_check(sp_scene* scene, sp_wide_check* out);
  * restatement of the device finish (the level-wise collapse), which makes the same arrays. */
 int  sp_scene_wide_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
                                sp_wide_check* out);
+
+/* ---- moving meshes: refit -----------------------------------------------------------------
+ * A host that moves a mesh's vertices between frames need not upload again: sp_scene_update_mesh
+ * writes the new positions into the scene and, when it is resident, refits every bounding box of
+ * the resident trees bottom-up on the device.  The topology of the trees stays (what the SAH
+ * builder chose for the first pose), nothing that stays is allocated, and the image is that of the
+ * moved mesh: a tree's shape changes how fast a ray finds its hit, not which hit it finds (up to
+ * the ties between primitives at exactly equal distance that any SAH-mode upload has).  After large
+ * deformations the kept topology traces slower than a fresh build; when to build again is the
+ * host's decision.
+ *
+ * What may change: vertex positions and, optionally, vertex normals.  Indices, materials, the
+ * number and order of primitives, spheres, planes, lights and the camera stay.
+ *
+ * Validation comes first and changes nothing -- a refused call leaves the mesh and any residency
+ * as they were -- in this order: null scene; struct sizes and reserved fields; null `vertices`;
+ * num_vertices other than the scene's.  A scene without vertices takes num_vertices = 0 (vertices
+ * may then be NULL) and the call does nothing.  Then:
+ *   - the scene's host mesh is overwritten in place: pointers from an earlier sp_scene_get_desc
+ *     stay valid and show the new values;
+ *   - a scene that is not resident is done (refitted = 0): a later upload builds from the new mesh;
+ *   - a scene resident with bvh_mode 1 is refused with SP_ERR_ARG before anything changes: the
+ *     reference order is a contract about a tree built from the current positions.  Upload again;
+ *   - a scene resident with bvh_mode 0 (either builder, either finish, any walk) is refitted in
+ *     place: the call takes the scene's lock, waits for queued renders, rewrites the primitive
+ *     records, the binary tree's boxes, the 8-wide tree's records and (when given) the normals,
+ *     waits for the refit, and invalidates every progress object made on the scene (their samples
+ *     belong to the old geometry: SP_ERR_STATE).  The tree's links, the light BVH, the walk, the
+ *     stack sizing and sp_scene_device_bytes stay.  The next upload of the scene, with the resident
+ *     options too, builds again from the current mesh.
+ * A device failure (allocation, a box that cannot be quantised, a fit that did not complete) is
+ * SP_ERR_HIP and leaves no resident scene, as after a failed upload; the host mesh is already the
+ * new one, so uploading again is the recovery.  There is no fall-back.
+ * The refitted arrays equal, byte for byte, those of the host restatement of the refit
+ * (sp_scene_refit_build_check). */
+#define SP_HAS_REFIT 1
+
+typedef struct sp_mesh_update {      /* zero-initialise; struct_size = sizeof */
+    uint32_t     struct_size;        /* a size the library does not know => SP_ERR_ARG */
+    int32_t      reserved0;          /* must be 0 */
+    const float* vertices;           /* HOST, num_vertices * 3, world space (as sp_scene_desc.vertices); required */
+    const float* normals;            /* HOST, num_vertices * 3, or NULL: keep the current normals */
+    int64_t      num_vertices;       /* must equal the scene's */
+    int32_t      reserved[4];        /* must be 0 */
+} sp_mesh_update;
+
+typedef struct sp_refit_stats {      /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  refitted;               /* 0: host mesh only (scene not resident); 1: resident arrays refitted */
+    int32_t  binary_passes, wide_passes;
+    float    ms_copy, ms_pack, ms_binary, ms_wide, ms_total;   /* device stages; filled only when asked for */
+    int64_t  scratch_bytes;          /* peak device scratch, all released before the call returns */
+} sp_refit_stats;
+
+/* stats may be NULL.  Passing stats (or setting SP_UPLOAD_TIMING) makes the call wait for the device
+ * after each stage so that ms_* hold stage times. */
+int  sp_scene_update_mesh(sp_scene* scene, const sp_mesh_update* update, sp_refit_stats* stats);
+
+/* Host only, no device: build what an upload of the scene's CURRENT mesh with these options would
+ * make, refit it to update->vertices with the host restatement of the device refit, and check the
+ * result against the NEW bounds.  Either out pointer may be NULL.  The scene is not modified.
+ * bvh_mode 1 is SP_ERR_ARG. */
+int  sp_scene_refit_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
+                                const sp_mesh_update* update, sp_bvh_check* bvh, sp_wide_check* wide);
 
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the

@@ -204,6 +204,53 @@ class Scene:
         check(lib().sp_scene_wide_build_check(self._h, C.byref(p), b, C.byref(c)))
         return self._wide_dict(c)
 
+    @staticmethod
+    def _mesh_update(vertices, normals=None):
+        """sp_mesh_update over float32 copies of the arrays, which the caller keeps alive"""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if n is not None and n.shape != v.shape:
+            raise ValueError("normals must have the shape of vertices")
+        u = _abi.sp_mesh_update()
+        u.struct_size = C.sizeof(_abi.sp_mesh_update)
+        u.vertices = v.ctypes.data_as(C.POINTER(C.c_float))
+        if n is not None:
+            u.normals = n.ctypes.data_as(C.POINTER(C.c_float))
+        u.num_vertices = v.shape[0]
+        return u, (v, n)
+
+    def update_mesh(self, vertices, normals=None, stats: bool = False):
+        """Move the mesh (sp_scene_update_mesh): vertices [num_vertices, 3] in world space, as desc()
+        holds them; normals optional.  The host mesh is overwritten in place; a scene resident with
+        bvh_mode 0 is refitted on the device -- same trees, new boxes and records, no new upload --
+        and progress objects made on it become invalid.  A scene resident with bvh_mode 1 refuses
+        (SP_ERR_ARG): upload it again.  With stats=True returns a dict of sp_refit_stats (stage times
+        in ms; the call then waits for the device after each stage), else None."""
+        u, keep = self._mesh_update(vertices, normals)
+        st = _abi.sp_refit_stats()
+        st.struct_size = C.sizeof(_abi.sp_refit_stats)
+        check(lib().sp_scene_update_mesh(self._h, C.byref(u), C.byref(st) if stats else None))
+        del keep
+        if not stats:
+            return None
+        return {k: getattr(st, k) for k, _ in _abi.sp_refit_stats._fields_ if k != "struct_size"}
+
+    def refit_build_check(self, vertices, builder="auto", finish="auto", **upload_options):
+        """Host only (sp_scene_refit_build_check): what upload(builder=..., finish=..., **upload_options)
+        of the current mesh followed by update_mesh(vertices) leaves in device memory, made by the host
+        restatement of the refit and checked against the moved mesh.  Returns (bvh_check dict,
+        wide_check dict); the scene is not modified."""
+        p = self._upload_params(**upload_options)
+        b = self._build_params(builder, finish)
+        u, keep = self._mesh_update(vertices)
+        c = _abi.sp_bvh_check()
+        c.struct_size = C.sizeof(_abi.sp_bvh_check)
+        w = _abi.sp_wide_check()
+        w.struct_size = C.sizeof(_abi.sp_wide_check)
+        check(lib().sp_scene_refit_build_check(self._h, C.byref(p), b, C.byref(u), C.byref(c), C.byref(w)))
+        del keep
+        return self._check_dict(c), self._wide_dict(w)
+
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()
         check(lib().sp_scene_bvh_info(self._h, C.byref(d), C.byref(n), C.byref(s)))

@@ -157,6 +157,19 @@ class sp_bvh_check(C.Structure):
                 ("hash", C.c_uint64)]
 
 
+class sp_mesh_update(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32),
+                ("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
+                ("num_vertices", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class sp_refit_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("refitted", C.c_int32),
+                ("binary_passes", C.c_int32), ("wide_passes", C.c_int32),
+                ("ms_copy", C.c_float), ("ms_pack", C.c_float), ("ms_binary", C.c_float), ("ms_wide", C.c_float),
+                ("ms_total", C.c_float), ("scratch_bytes", C.c_int64)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -223,6 +236,9 @@ SIGNATURES = {
                                            C.POINTER(sp_bvh_check)]),
     "sp_scene_wide_check": (C.c_int, [C.c_void_p, C.POINTER(sp_wide_check)]),
     "sp_scene_wide_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.c_void_p, C.POINTER(sp_wide_check)]),
+    "sp_scene_update_mesh": (C.c_int, [C.c_void_p, C.POINTER(sp_mesh_update), C.POINTER(sp_refit_stats)]),
+    "sp_scene_refit_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.POINTER(sp_build_params),
+                                             C.POINTER(sp_mesh_update), C.POINTER(sp_bvh_check), C.POINTER(sp_wide_check)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

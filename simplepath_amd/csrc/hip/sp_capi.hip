@@ -7,6 +7,8 @@
 #include "sp_plan.hpp"
 #include "sp_build.hpp"
 #include "sp_finish.hpp"
+#include "sp_refit.hpp"
+#include "../common/sp_refit.h"
 #include "../host/sp_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -44,16 +46,11 @@ uint32_t code_of(int kind, int index) { return ((uint32_t)kind << spd::CODE_SHIF
 // BBox3 of a primitive (shapes/Triangle.h:228, shapes/Shape.h:290 for transformed shapes)
 sph::PrimBounds tri_bounds(const sph::Scene& s, int t)
 {
+    // BBox::extend per vertex, min(p, m_min): spr::tri_box (sp_refit.h), shared with the device refit
+    const spm::f3*  v   = s.vertices.data();
+    const spr::Box  box = spr::tri_box(&v[s.indices[3 * t]].x, &v[s.indices[3 * t + 1]].x, &v[s.indices[3 * t + 2]].x);
     sph::PrimBounds b;
-    for (int i = 0; i < 3; ++i) { b.lo[i] = INFINITY; b.hi[i] = -INFINITY; }
-    for (int k = 0; k < 3; ++k) {
-        const spm::f3 p   = s.vertices[s.indices[3 * t + k]];
-        const float   v[3] = { p.x, p.y, p.z };
-        for (int i = 0; i < 3; ++i) {
-            b.lo[i] = spm::sse_min(v[i], b.lo[i]); // BBox::extend: min(p, m_min)
-            b.hi[i] = spm::sse_max(v[i], b.hi[i]);
-        }
-    }
+    for (int i = 0; i < 3; ++i) { b.lo[i] = box.lo[i]; b.hi[i] = box.hi[i]; }
     return b;
 }
 
@@ -547,9 +544,13 @@ struct sp_scene {
     // counts every change that invalidates a progress object made on this scene (sp_progress):
     // a new upload (the device scene is rebuilt) and sp_scene_set_resolution
     uint64_t             generation = 0;
+    // the resident trees were refitted (sp_scene_update_mesh): their topology is an earlier pose's, so
+    // an upload with the resident options builds again instead of finding the scene resident
+    bool                 refitted = false;
 
     void release()
     {
+        refitted = false;
         if (device >= 0) (void)hipSetDevice(device);
         bufs.clear();
         scratch = RenderScratch{};
@@ -963,7 +964,7 @@ static int validate_upload(UploadCall& c, const sp_upload_params* params, const 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SP_ERR_HIP, "no HIP device");
     if (c.device < 0 || c.device >= ndev) return fail(SP_ERR_ARG, "device out of range");
-    resident = c.s->device == c.device && c.s->opts == c.opts;
+    resident = c.s->device == c.device && c.s->opts == c.opts && !c.s->refitted;
     return SP_OK;
 }
 
@@ -2838,6 +2839,184 @@ int sp_scene_wide_check(sp_scene* s, sp_wide_check* out)
     std::lock_guard<std::mutex> lock(s->mu);
     if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
     return check_scene(s, nullptr, nullptr, out);
+}
+
+// ---- moving meshes: refit ------------------------------------------------------------
+
+namespace {
+// sp_mesh_update against the scene's mesh, in the order the header promises (the scene itself is the
+// caller's): struct size, reserved fields, null vertices, the vertex count.  Changes nothing.
+int validate_update(const sph::Scene& h, const sp_mesh_update* u)
+{
+    if (!u) return fail(SP_ERR_ARG, "null sp_mesh_update");
+    if (u->struct_size != sizeof(sp_mesh_update)) return fail(SP_ERR_ARG, "sp_mesh_update.struct_size is not a known size");
+    if (u->reserved0 != 0 || u->reserved[0] != 0 || u->reserved[1] != 0 || u->reserved[2] != 0 || u->reserved[3] != 0)
+        return fail(SP_ERR_ARG, "sp_mesh_update.reserved must be 0");
+    if (!u->vertices && !(h.vertices.empty() && u->num_vertices == 0)) return fail(SP_ERR_ARG, "sp_mesh_update.vertices is null");
+    if (u->num_vertices != (int64_t)h.vertices.size()) return fail(SP_ERR_ARG, "sp_mesh_update.num_vertices is not the scene's");
+    return SP_OK;
+}
+
+void copy_f3(std::vector<spm::f3>& to, const float* from)
+{
+    static_assert(sizeof(spm::f3) == 12, "f3 packing");
+    if (!to.empty()) std::memcpy(to.data(), from, to.size() * sizeof(spm::f3));
+}
+
+// what bounded_prims and pack_records read of a scene, with other vertex positions
+sph::Scene moved_mesh(const sph::Scene& h, const float* vertices)
+{
+    sph::Scene m;
+    m.vertices   = h.vertices;
+    m.indices    = h.indices;
+    m.shapes     = h.shapes;
+    m.prim_kind  = h.prim_kind;
+    m.prim_index = h.prim_index;
+    copy_f3(m.vertices, vertices);
+    return m;
+}
+
+// The host restatement of the device refit (sp_refit.hip) on the arrays finish_host made: the
+// records again from the moved mesh, every binary box by lbvh_fit_boxes, every wide record by
+// refit_wide.  Topology, prim_order and slot_of stay; a.bounds become the new bounds.
+void refit_host(HostAccel& a, const sph::Scene& moved)
+{
+    a.bounds = bounded_prims(moved, a.prims, a.part);
+    pack_records(moved, a.prims, a.bvh.prim_order, a.slot_tri, a.slot_code);
+    for (size_t i = 0; i < a.wide.slot_of.size(); ++i)
+        for (int k = 0; k < 3; ++k) a.wslot_tri[3 * i + k] = a.slot_tri[3 * (size_t)a.wide.slot_of[i] + k];
+    sph::lbvh_fit_boxes(a.bvh, a.bounds);
+    if (a.wide.words.empty()) return;
+    std::vector<sph::PrimBounds> by_wide_slot(a.wide.slot_of.size());
+    for (size_t i = 0; i < by_wide_slot.size(); ++i)
+        by_wide_slot[i] = a.bounds[(size_t)a.bvh.prim_order[(size_t)a.wide.slot_of[i]]];
+    sph::refit_wide(a.wide, by_wide_slot);
+}
+
+// bounds by shape index for the device: the host's sphere_bounds values (a plane has none)
+std::vector<sph::PrimBounds> shape_bounds(const sph::Scene& h)
+{
+    std::vector<sph::PrimBounds> out(h.shapes.size());
+    for (size_t i = 0; i < out.size(); ++i) {
+        if (h.shapes[i].kind == SP_PRIM_SPHERE) out[i] = sphere_bounds(from_desc(h.shapes[i].object_to_world));
+        else
+            for (int d = 0; d < 3; ++d) { out[i].lo[d] = INFINITY; out[i].hi[d] = -INFINITY; }
+    }
+    return out;
+}
+
+// the resident arrays follow the host mesh (already the new one); the caller holds the lock
+int refit_resident(sp_scene* s, bool with_normals, bool timed, spr::RefitStats& st)
+{
+    const sph::Scene& h = *s->host;
+    const spd::Scene& d = s->dev;
+    SP_HIP(hipSetDevice(s->device));
+    SP_HIP(hipDeviceSynchronize()); // queued renders read the arrays this rewrites
+    const std::vector<sph::PrimBounds> shapes = shape_bounds(h);
+    spr::RefitIn in;
+    in.d_nodes     = reinterpret_cast<sph::BvhNode*>(const_cast<spd::Node*>(d.nodes));
+    in.n_nodes     = (uint32_t)s->sizes.geom_nodes;
+    in.geom_depth  = s->sizes.geom_depth;
+    in.d_slot_tri  = const_cast<float4*>(d.slot_tri);
+    in.d_slot_code = d.slot_code;
+    in.n_slots     = (uint32_t)s->sizes.geom_slots;
+    if (d.wnodes) {
+        in.d_wnodes    = reinterpret_cast<uint32_t*>(const_cast<uint4*>(d.wnodes));
+        in.records     = (uint32_t)s->sizes.wide_records;
+        in.wide_depth  = s->sizes.wide_depth;
+        in.d_wslot_tri = const_cast<float4*>(d.wslot_tri);
+        in.wide_slots  = (uint32_t)s->sizes.wide_slots;
+    }
+    in.d_indices      = d.indices;
+    in.n_indices      = h.indices.size();
+    in.h_verts        = h.vertices.data();
+    in.n_verts        = h.vertices.size();
+    in.h_normals      = with_normals ? h.normals.data() : nullptr;
+    in.d_normals      = const_cast<float*>(d.normals);
+    in.h_shape_bounds = shapes.data();
+    in.n_shapes       = (uint32_t)shapes.size();
+    std::string err;
+    const int   rc = spr::refit_device(in, st, err, timed);
+    return rc == SP_OK ? SP_OK : fail(rc, err);
+}
+} // namespace
+
+int sp_scene_update_mesh(sp_scene* s, const sp_mesh_update* u, sp_refit_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null scene");
+    if (stats && stats->struct_size != sizeof(sp_refit_stats)) return fail(SP_ERR_ARG, "sp_refit_stats.struct_size is not a known size");
+    std::lock_guard<std::mutex> lock(s->mu);
+    sph::Scene&                 h = *s->host;
+    if (int rc = validate_update(h, u)) return rc;
+    if (s->device >= 0 && s->opts.bvh_mode == 1)
+        return fail(SP_ERR_ARG, "a scene resident in the reference order (bvh_mode 1) cannot be refitted: upload it again");
+    if (stats) {
+        *stats             = sp_refit_stats{};
+        stats->struct_size = sizeof(sp_refit_stats);
+    }
+    if (h.vertices.empty()) return SP_OK;
+    copy_f3(h.vertices, u->vertices);
+    if (u->normals && h.normals.size() == h.vertices.size()) copy_f3(h.normals, u->normals);
+    if (s->device < 0) return SP_OK;
+    const bool      env_timing = UploadHooks::from_env().timing;
+    spr::RefitStats st;
+    int             rc = SP_OK;
+    ++s->generation; // the samples of every progress object belong to the old geometry
+    try {
+        rc = refit_resident(s, u->normals != nullptr && h.normals.size() == h.vertices.size(), stats != nullptr || env_timing, st);
+    } catch (const std::exception& e) {
+        rc = fail(SP_ERR_UNSUPPORTED, std::string("mesh update failed: ") + e.what());
+    }
+    if (rc != SP_OK) {
+        (void)hipGetLastError();
+        s->release(); // as after a failed upload: no resident scene; the host mesh is the new one
+        return rc;
+    }
+    s->refitted = true;
+    if (stats) {
+        stats->refitted      = 1;
+        stats->binary_passes = st.binary_passes;
+        stats->wide_passes   = st.wide_passes;
+        stats->ms_copy       = (float)st.ms_copy;
+        stats->ms_pack       = (float)st.ms_pack;
+        stats->ms_binary     = (float)st.ms_binary;
+        stats->ms_wide       = (float)st.ms_wide;
+        stats->ms_total      = (float)st.ms_total;
+        stats->scratch_bytes = (int64_t)st.peak_bytes;
+    }
+    if (env_timing)
+        std::fprintf(stderr,
+                     "sp_refit_timing {\"nodes\": %zu, \"slots\": %zu, \"records\": %zu, \"binary_passes\": %d, \"wide_passes\": %d, "
+                     "\"copy_ms\": %.3f, \"pack_ms\": %.3f, \"binary_ms\": %.3f, \"wide_ms\": %.3f, \"total_ms\": %.3f, "
+                     "\"peak_scratch_bytes\": %zu}\n",
+                     s->sizes.geom_nodes, s->sizes.geom_slots, s->sizes.wide_records, st.binary_passes, st.wide_passes, st.ms_copy,
+                     st.ms_pack, st.ms_binary, st.ms_wide, st.ms_total, st.peak_bytes);
+    return SP_OK;
+}
+
+int sp_scene_refit_build_check(const sp_scene* s, const sp_upload_params* params, const sp_build_params* build,
+                               const sp_mesh_update* u, sp_bvh_check* bvh, sp_wide_check* wide)
+{
+    if (!s) return fail(SP_ERR_ARG, "null scene");
+    if (bvh && bvh->struct_size != sizeof(sp_bvh_check)) return fail(SP_ERR_ARG, "sp_bvh_check.struct_size is not a known size");
+    if (wide && wide->struct_size != sizeof(sp_wide_check)) return fail(SP_ERR_ARG, "sp_wide_check.struct_size is not a known size");
+    if (int rc = validate_update(*s->host, u)) return rc;
+    UploadOpts opts;
+    if (int rc = resolve_opts(params, build, UploadHooks::from_env(), opts)) return rc;
+    if (opts.bvh_mode == 1) return fail(SP_ERR_ARG, "the reference order (bvh_mode 1) is not refitted");
+    try {
+        HostAccel a;
+        build_trees(*s->host, a, opts, BuildOn::HOST);
+        finish_host(*s->host, a, opts);
+        refit_host(a, moved_mesh(*s->host, u->vertices));
+        if (bvh) fill_check(a.bvh, a.bounds, opts, bvh);
+        if (wide) fill_wide_check(a, opts.finish, wide);
+        return SP_OK;
+    } catch (const sph::SpError& e) {
+        return fail(e.code, e.what());
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("refit check failed: ") + e.what());
+    }
 }
 
 int sp_scene_device_bytes(const sp_scene* s, int64_t* bytes)

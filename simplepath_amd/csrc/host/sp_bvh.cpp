@@ -8,6 +8,7 @@
 #include "sp_host.hpp"
 #include "../common/sp_lbvh.h"
 #include "../common/sp_wide.h"
+#include "../common/sp_refit.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -570,6 +571,40 @@ WideBvh build_wide_levels(const Bvh& bvh)
             spw::write_slots(nodes, v.c, v.leaf_base, out.slot_of.data());
         }
     return out;
+}
+
+// ------------------------------------------------------------------------- wide refit
+// Records sit behind their parents (child_base is taken from a running count in both collapses),
+// so the array walked backwards meets every child before its parent.
+void refit_wide(WideBvh& wide, const std::vector<PrimBounds>& slot_bounds)
+{
+    std::vector<uint32_t>& W    = wide.words;
+    const size_t           nrec = W.size() / 20, nslots = slot_bounds.size();
+    std::vector<spr::Box>  exact(nrec, spr::empty_box());
+    for (size_t r = nrec; r-- > 0;) {
+        uint32_t*      w     = &W[20 * r];
+        const uint32_t imask = spr::rec_imask(w), occupied = spr::rec_occupied(w);
+        spr::Box       slot[8];
+        for (int s = 0; s < 8; ++s) {
+            slot[s] = spr::empty_box();
+            if ((imask >> s) & 1u) {
+                const uint64_t c = (uint64_t)w[4] + (uint32_t)s;
+                if (c <= r || c >= nrec) throw std::runtime_error(spw::error_text(spw::ERR_LINKS));
+                slot[s] = exact[c];
+                continue;
+            }
+            const uint32_t meta = spr::rec_meta(w, s), cnt = meta >> 5, off = meta & 31u;
+            if ((uint64_t)w[5] + off + cnt > nslots) throw std::runtime_error(spw::error_text(spw::ERR_LINKS));
+            for (uint32_t j = 0; j < cnt; ++j) {
+                const PrimBounds& b = slot_bounds[(size_t)w[5] + off + j];
+                spr::Box          pb;
+                for (int a = 0; a < 3; ++a) { pb.lo[a] = b.lo[a]; pb.hi[a] = b.hi[a]; }
+                spr::fold(slot[s], pb);
+            }
+        }
+        const int e = spr::refit_record(w, slot, occupied, exact[r]);
+        if (e != spw::OK) throw std::runtime_error(spw::error_text(e));
+    }
 }
 
 // ------------------------------------------------------------------------- wide checker

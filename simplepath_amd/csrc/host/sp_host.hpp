@@ -210,6 +210,12 @@ WideBvh build_wide(const Bvh& bvh);
 // (sp_finish.hip): collapse top-down one level at a time, subtree sums bottom-up, bases top-down,
 // then every record at its final index.  Equal to build_wide word for word.
 WideBvh build_wide_levels(const Bvh& bvh);
+// Refit (sp_refit.h): every record's grid and quantised boxes again from the bounds
+// of the primitives in wide-slot order, children before parents; the topology (imask, bases, meta
+// bytes, slot_of, depth) stays.  The host restatement of the device refit's wide half; the binary
+// half is lbvh_fit_boxes.  Throws when a child link does not point behind its record or a box
+// cannot be quantised.
+void refit_wide(WideBvh& wide, const std::vector<PrimBounds>& slot_bounds);
 
 // Structural check of an 8-wide BVH against the binary tree's primitive order and the primitive
 // bounds (sp_wide_check): what is wrong is counted in `errors`, the first finding kept.
