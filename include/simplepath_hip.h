@@ -489,10 +489,26 @@ int  sp_adaptive_import(sp_progress* progress, const sp_pixel_noise* h_noise, in
  * environment variable SP_DEVICE_BUILD=1 (a test hook like SP_WIDE) turns AUTO into DEVICE for
  * bvh_mode 0.  An explicit SP_BUILDER_DEVICE with bvh_mode 1 is SP_ERR_ARG: the reference order is a
  * host contract.  A device build that cannot allocate or sort returns SP_ERR_HIP; it never falls back
- * to the host.  The same scene uploaded with another builder is uploaded again. */
+ * to the host.  The same scene uploaded with another builder is uploaded again.
+ *
+ * SP_BUILDER_DEVICE_SAH builds the host builder's binned SAH tree on the device: the same nodes and
+ * the same primitive order byte for byte, so everything downstream -- both finishes, the refit, the
+ * images, the trace rate -- is that of SP_BUILDER_HOST, at a fraction of the build time.  Large nodes
+ * are split level by level, small ranges by one thread each.  It serves bvh_mode 0 only (bvh_mode 1:
+ * SP_ERR_ARG); SP_FINISH_AUTO resolves to the device finish as for SP_BUILDER_DEVICE; a failed build
+ * is SP_ERR_HIP, leaves no resident scene and never falls back to the host; 2^30 primitives or more
+ * are SP_ERR_UNSUPPORTED, the host builder's limit.  A bound that is not finite (an infinite or NaN
+ * vertex or transform: the scene loader does not refuse them) makes a NaN centroid, whose folds
+ * depend on their order: the device SAH builder detects it in its first pass and returns
+ * SP_ERR_UNSUPPORTED, leaving no resident scene; build such a scene with SP_BUILDER_HOST.
+ * SP_DEVICE_BUILD=2 turns AUTO into DEVICE_SAH for bvh_mode 0 (1 keeps its meaning; an explicit
+ * builder is never overridden; SP_SAH_SMALL=n sets the size of the ranges one thread builds, which
+ * does not reach the tree).  HOST and DEVICE_SAH are different options although their bytes are
+ * equal: changing between them uploads again.  The value 3 is not a builder and stays SP_ERR_ARG. */
 #define SP_HAS_DEVICE_BUILD 1
+#define SP_HAS_DEVICE_SAH 1
 
-enum { SP_BUILDER_AUTO = 0, SP_BUILDER_HOST = 1, SP_BUILDER_DEVICE = 2 };
+enum { SP_BUILDER_AUTO = 0, SP_BUILDER_HOST = 1, SP_BUILDER_DEVICE = 2, SP_BUILDER_DEVICE_SAH = 4 };
 typedef struct sp_build_params {      /* zero-initialise; struct_size = sizeof */
     uint32_t struct_size;             /* a size the library does not know => SP_ERR_ARG */
     int32_t  builder;                 /* SP_BUILDER_* */
@@ -509,7 +525,7 @@ int  sp_scene_upload_with(sp_scene* scene, int32_t device, const sp_upload_param
  * 1 child range, 2 reached twice, 3 unreachable, 4 leaf count, 5 slots, 6 prim_order, 7 box, 8 depth. */
 typedef struct sp_bvh_check {         /* struct_size set by the caller */
     uint32_t struct_size;
-    int32_t  builder;                 /* builder that made the tree: SP_BUILDER_HOST or _DEVICE */
+    int32_t  builder;                 /* builder that made the tree: SP_BUILDER_HOST, _DEVICE or _DEVICE_SAH */
     int64_t  nodes, leaves, slots;
     int32_t  depth, max_leaf;         /* levels as sp_bvh_info.depth; largest leaf */
     int64_t  errors;                  /* 0 = every invariant holds */
@@ -520,7 +536,8 @@ typedef struct sp_bvh_check {         /* struct_size set by the caller */
 /* Uploaded scene: copies the binary geometry BVH and the slot codes back from the device and checks them. */
 int  sp_scene_bvh_check(sp_scene* scene, sp_bvh_check* out);
 /* Host only, no device: builds what an upload with these options would build and checks it; builder
- * DEVICE runs the host restatement of the device algorithm, which makes the same tree bit for bit. */
+ * DEVICE or DEVICE_SAH runs the host restatement of that device algorithm, which makes the same tree
+ * bit for bit (DEVICE_SAH: the level-wise form; bounds that are not finite are SP_ERR_UNSUPPORTED). */
 int  sp_scene_bvh_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
                               sp_bvh_check* out);
 
@@ -530,7 +547,7 @@ int  sp_scene_bvh_build_check(const sp_scene* scene, const sp_upload_params* par
  * does this on one core; the device finish does it in kernels on the binary tree resident in device
  * memory, level by level, and writes the same bytes: every array equals the host's bit for bit, so
  * renders are identical.  SP_FINISH_AUTO is the device finish when the builder resolves to
- * SP_BUILDER_DEVICE and the host finish otherwise, so a default upload is untouched.
+ * SP_BUILDER_DEVICE or SP_BUILDER_DEVICE_SAH and the host finish otherwise, so a default upload is untouched.
  * SP_FINISH_DEVICE goes with either builder for bvh_mode 0; with bvh_mode 1 it is SP_ERR_ARG.  A
  * device finish that fails (allocation, more than 2^24 records or 64 levels, a leaf that does not
  * fit a meta byte, a failed quantisation) is SP_ERR_HIP and leaves no resident scene.  The

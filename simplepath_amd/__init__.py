@@ -145,12 +145,14 @@ class Scene:
         image: the parent-link walk, the LDS-stack depth budget, the image-light guide tables, the
         SAH leaf size.  On the SAH BVH, wide_bvh / binary_closest choose the 8-wide or binary walks,
         which can only differ in which of two primitives at exactly equal distance wins.
-        builder "auto" | "host" | "device" (sp_build_params): "device" builds a linear BVH on the
-        GPU instead of the SAH one on the host -- a much shorter upload, a somewhat slower trace,
-        and again the same image up to such ties.
+        builder "auto" | "host" | "device" | "device_sah" (sp_build_params): "device" builds a
+        linear BVH on the GPU instead of the SAH one on the host -- a much shorter upload, a
+        somewhat slower trace, and again the same image up to such ties.  "device_sah" builds the
+        host's SAH tree on the GPU, byte for byte: the host build's images and trace rate after a
+        short upload (bounds that are not finite are SP_ERR_UNSUPPORTED).
         finish "auto" | "host" | "device" (sp_build_params_ex): where the 8-wide collapse, the
         primitive records and the parent links are made from the binary tree.  Both make the same
-        bytes; "auto" is "device" with the device builder and "host" otherwise."""
+        bytes; "auto" is "device" with a device builder and "host" otherwise."""
         p = self._upload_params(bvh_mode, stackless, stack_max_levels, wide_bvh, env_replay, sah_leaf, binary_closest)
         b = self._build_params(builder, finish)
         check(lib().sp_scene_upload_with(self._h, device, C.byref(p), b))
@@ -172,7 +174,8 @@ class Scene:
 
     def bvh_build_check(self, builder="auto", **upload_options) -> dict:
         """The same check on what upload(builder=..., **upload_options) would build, on the host
-        alone (sp_scene_bvh_build_check); "device" runs the host restatement of the device builder."""
+        alone (sp_scene_bvh_build_check); "device" and "device_sah" run the host restatement of that
+        device builder."""
         p = self._upload_params(**upload_options)
         b = self._build_params(builder)
         c = _abi.sp_bvh_check()

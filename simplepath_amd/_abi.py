@@ -123,8 +123,9 @@ class sp_bvh_info(C.Structure):
                 ("stack_depth", C.c_int32), ("nodes", C.c_int64), ("slots", C.c_int64)]
 
 
-SP_BUILDER_AUTO, SP_BUILDER_HOST, SP_BUILDER_DEVICE = 0, 1, 2
-BUILDERS = {"auto": SP_BUILDER_AUTO, "host": SP_BUILDER_HOST, "device": SP_BUILDER_DEVICE}
+SP_BUILDER_AUTO, SP_BUILDER_HOST, SP_BUILDER_DEVICE, SP_BUILDER_DEVICE_SAH = 0, 1, 2, 4
+BUILDERS = {"auto": SP_BUILDER_AUTO, "host": SP_BUILDER_HOST, "device": SP_BUILDER_DEVICE,
+            "device_sah": SP_BUILDER_DEVICE_SAH}
 
 
 class sp_build_params(C.Structure):

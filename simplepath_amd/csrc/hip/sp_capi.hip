@@ -6,9 +6,11 @@
 #include "sp_launch.hpp"
 #include "sp_plan.hpp"
 #include "sp_build.hpp"
+#include "sp_sah_build.hpp"
 #include "sp_finish.hpp"
 #include "sp_refit.hpp"
 #include "../common/sp_refit.h"
+#include "../common/sp_sah.h"
 #include "../host/sp_host.hpp"
 
 #include <hip/hip_runtime.h>
@@ -101,7 +103,7 @@ struct UploadOpts {
     bool env_guide  = true;  // image-light guide tables
     bool wide_closest = true;  // closest-hit queries on the 8-wide BVH as well
     int  sah_leaf   = 4;
-    int  builder    = SP_BUILDER_HOST; // SP_BUILDER_HOST or SP_BUILDER_DEVICE (sp_build_params, resolved)
+    int  builder    = SP_BUILDER_HOST; // SP_BUILDER_HOST, _DEVICE or _DEVICE_SAH (sp_build_params, resolved)
     int  finish     = SP_FINISH_HOST;  // SP_FINISH_HOST or SP_FINISH_DEVICE (sp_build_params_ex, resolved)
     bool operator==(const UploadOpts& o) const
     {
@@ -112,12 +114,14 @@ struct UploadOpts {
 };
 
 // The SP_* test hooks of the upload path, read once per call (the struct's initialisers are the
-// compiled defaults).  All but the last two stand in for an sp_upload_params / sp_build_params field
-// left automatic; `timing` and `rsqrt_pack` have no field, and are not part of UploadOpts: a change
-// of SP_RSQRT_PACK alone does not make an upload with the resident options build again.
+// compiled defaults).  All but the last three stand in for an sp_upload_params / sp_build_params field
+// left automatic; `sah_small`, `timing` and `rsqrt_pack` have no field, and are not part of UploadOpts:
+// a change of SP_RSQRT_PACK alone does not make an upload with the resident options build again, and
+// SP_SAH_SMALL does not reach the tree at all.
 struct UploadHooks {
     int  stackless = 0, stack_max = 96, wide = 1, env_guide = 1, wide_closest = 1, sah_leaf = 4;
     int  device_build = 0, device_finish = -1; // -1: the finish follows the builder
+    int  sah_small    = 0;                     // SP_SAH_SMALL: the device SAH builder's hand-over size (0: its default)
     bool timing     = false;                   // SP_UPLOAD_TIMING (set at all): the sp_upload_timing line
     bool rsqrt_pack = true;                    // SP_RSQRT_PACK=0: 32-bit RSQRTSS entries (comparison)
 
@@ -128,7 +132,8 @@ struct UploadHooks {
         const std::pair<const char*, int*> ints[] = {
             { "SP_STACKLESS", &h.stackless }, { "SP_STACK_MAX", &h.stack_max }, { "SP_WIDE", &h.wide },
             { "SP_ENV_GUIDE", &h.env_guide }, { "SP_WIDE_CLOSEST", &h.wide_closest }, { "SP_SAH_LEAF", &h.sah_leaf },
-            { "SP_DEVICE_BUILD", &h.device_build }, { "SP_DEVICE_FINISH", &h.device_finish }, { "SP_RSQRT_PACK", &pack } };
+            { "SP_DEVICE_BUILD", &h.device_build }, { "SP_DEVICE_FINISH", &h.device_finish }, { "SP_SAH_SMALL", &h.sah_small },
+            { "SP_RSQRT_PACK", &pack } };
         for (const auto& e : ints)
             if (const char* v = std::getenv(e.first)) *e.second = std::atoi(v);
         h.timing     = std::getenv("SP_UPLOAD_TIMING") != nullptr;
@@ -160,7 +165,7 @@ int resolve_upload(const sp_upload_params* p, const UploadHooks& hooks, UploadOp
 }
 
 // The builder of an upload (sp_build_params): NULL or AUTO is the host builders, unless the test
-// hook SP_DEVICE_BUILD=1 asks for the device builder on a SAH-mode upload.  The finish
+// hook SP_DEVICE_BUILD=1 (linear BVH) or =2 (device SAH) asks for a device builder on a SAH-mode upload.  The finish
 // (sp_build_params_ex, told apart by struct_size): AUTO follows the builder unless the test hook
 // SP_DEVICE_FINISH=0|1 decides.  sp_upload_params is validated first.
 int resolve_opts(const sp_upload_params* p, const sp_build_params* b, const UploadHooks& hooks, UploadOpts& o)
@@ -179,20 +184,24 @@ int resolve_opts(const sp_upload_params* p, const sp_build_params* b, const Uplo
                 return fail(SP_ERR_ARG, "finish must be SP_FINISH_AUTO, SP_FINISH_HOST or SP_FINISH_DEVICE");
             finish = x->finish;
         }
-        if (b->builder != SP_BUILDER_AUTO && b->builder != SP_BUILDER_HOST && b->builder != SP_BUILDER_DEVICE)
-            return fail(SP_ERR_ARG, "builder must be SP_BUILDER_AUTO, SP_BUILDER_HOST or SP_BUILDER_DEVICE");
+        if (b->builder != SP_BUILDER_AUTO && b->builder != SP_BUILDER_HOST && b->builder != SP_BUILDER_DEVICE &&
+            b->builder != SP_BUILDER_DEVICE_SAH)
+            return fail(SP_ERR_ARG, "builder must be SP_BUILDER_AUTO, SP_BUILDER_HOST, SP_BUILDER_DEVICE or SP_BUILDER_DEVICE_SAH");
         builder = b->builder;
     }
-    if (builder == SP_BUILDER_DEVICE && o.bvh_mode == 1)
-        return fail(SP_ERR_ARG, "the device builder cannot make the reference order (bvh_mode 1)");
+    if ((builder == SP_BUILDER_DEVICE || builder == SP_BUILDER_DEVICE_SAH) && o.bvh_mode == 1)
+        return fail(SP_ERR_ARG, "the device builders cannot make the reference order (bvh_mode 1)");
     if (builder == SP_BUILDER_AUTO)
-        builder = (o.bvh_mode == 0 && hooks.device_build == 1) ? SP_BUILDER_DEVICE : SP_BUILDER_HOST;
+        builder = o.bvh_mode != 0 ? SP_BUILDER_HOST
+                  : hooks.device_build == 1 ? SP_BUILDER_DEVICE
+                  : hooks.device_build == 2 ? SP_BUILDER_DEVICE_SAH
+                                            : SP_BUILDER_HOST;
     o.builder = builder;
     if (finish == SP_FINISH_DEVICE && o.bvh_mode == 1)
         return fail(SP_ERR_ARG, "the device finish cannot serve the reference order (bvh_mode 1)");
     if (finish == SP_FINISH_AUTO) {
         const int  hook = hooks.device_finish;
-        const bool dev  = hook == 0 ? false : (hook == 1 ? true : builder == SP_BUILDER_DEVICE);
+        const bool dev  = hook == 0 ? false : (hook == 1 ? true : builder == SP_BUILDER_DEVICE || builder == SP_BUILDER_DEVICE_SAH);
         finish         = (dev && o.bvh_mode == 0) ? SP_FINISH_DEVICE : SP_FINISH_HOST;
     }
     o.finish = finish;
@@ -220,6 +229,7 @@ std::vector<sph::PrimBounds> bounded_prims(const sph::Scene& h, std::vector<int3
 struct UploadTiming {
     double          ms_bounds = 0, ms_bvh = 0, ms_wide = 0, ms_pack = 0, ms_copies = 0;
     spb::BuildStats dev{};
+    spb::SahStats   sah{};
     spf::FinishStats fin{};
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void lap(double& ms)
@@ -313,7 +323,7 @@ struct HostAccel {
     std::vector<uint32_t>        slot_code, parents, light_parents;
 };
 
-enum class BuildOn { HOST, DEVICE }; // where SP_BUILDER_DEVICE runs: its host restatement, or the current device
+enum class BuildOn { HOST, DEVICE }; // where a device builder runs: its host restatement, or the current device
 
 // Bounds; the BVH over the bounded part -- the reference's median split (bvh_mode 1,
 // shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder (one tree,
@@ -322,12 +332,26 @@ enum class BuildOn { HOST, DEVICE }; // where SP_BUILDER_DEVICE runs: its host r
 // or gets the 8-wide BVH (SAH scenes; no_wide_bvh keeps the binary walk).  With `keep` (device
 // builder and device finish) the geometry tree stays on the device, in `keep`.
 void build_trees(const sph::Scene& h, HostAccel& a, const UploadOpts& o, BuildOn where, UploadTiming* tm = nullptr,
-                 spb::DeviceTree* keep = nullptr)
+                 spb::DeviceTree* keep = nullptr, int sah_small = 0)
 {
     a.bounds = bounded_prims(h, a.prims, a.part);
     if (tm) tm->lap(tm->ms_bounds);
     if (o.bvh_mode == 1) a.bvh = sph::build_bvh_reference(a.bounds);
-    else if (o.builder != SP_BUILDER_DEVICE) a.bvh = sph::build_bvh_sah(a.bounds, o.sah_leaf);
+    else if (o.builder == SP_BUILDER_DEVICE_SAH) {
+        // the host's SAH tree from the device (sp_sah_build.hip) or its level-wise restatement;
+        // both refuse bounds that are not finite, whose tree depends on the order of the folds
+        if (where == BuildOn::HOST) {
+            for (const sph::PrimBounds& b : a.bounds)
+                if (!sah::finite_bounds(b.lo, b.hi)) throw sph::SpError(SP_ERR_UNSUPPORTED, "device SAH build: a primitive's bounds are not finite");
+            a.bvh = sph::build_bvh_sah_levels(a.bounds, o.sah_leaf);
+        } else {
+            spb::SahStats st;
+            std::string   err;
+            const int     rc = spb::build_sah_device(a.bounds, o.sah_leaf, a.bvh, tm ? tm->sah : st, err, tm != nullptr, keep,
+                                                     (uint32_t)std::max(0, sah_small));
+            if (rc != SP_OK) throw sph::SpError(rc, err);
+        }
+    } else if (o.builder != SP_BUILDER_DEVICE) a.bvh = sph::build_bvh_sah(a.bounds, o.sah_leaf);
     else if (where == BuildOn::HOST) a.bvh = sph::build_bvh_lbvh(a.bounds, o.sah_leaf);
     else {
         spb::BuildStats st;
@@ -1210,18 +1234,23 @@ static void print_upload_timing(const UploadCall& c)
 {
     const UploadTiming&     t = *c.tm;
     const spb::BuildStats&  b = t.dev;
+    const spb::SahStats&    q = t.sah;
     const spf::FinishStats& f = t.fin;
     std::fprintf(stderr,
                  "sp_upload_timing {\"builder\": \"%s\", \"bvh_mode\": %d, \"prims\": %zu, \"nodes\": %zu, \"depth\": %d, "
                  "\"stackless\": %d, \"bounds_ms\": %.3f, \"bvh_ms\": %.3f, \"wide_ms\": %.3f, \"pack_ms\": %.3f, \"copies_ms\": %.3f, "
                  "\"device\": {\"bounds_up_ms\": %.3f, \"codes_ms\": %.3f, \"sort_ms\": %.3f, \"hierarchy_ms\": %.3f, \"fit_ms\": %.3f, "
                  "\"copy_back_ms\": %.3f, \"passes\": %d, \"peak_scratch_bytes\": %zu}, "
+                 "\"device_sah\": {\"bounds_up_ms\": %.3f, \"levels_ms\": %.3f, \"subtrees_ms\": %.3f, \"number_ms\": %.3f, "
+                 "\"emit_ms\": %.3f, \"copy_back_ms\": %.3f, \"levels\": %d, \"level_nodes\": %u, \"subtrees\": %u, "
+                 "\"peak_scratch_bytes\": %zu}, "
                  "\"finish\": \"%s\", \"device_finish\": {\"inputs_up_ms\": %.3f, \"collapse_ms\": %.3f, \"sums_ms\": %.3f, "
                  "\"bases_ms\": %.3f, \"emit_ms\": %.3f, \"pack_ms\": %.3f, \"parents_ms\": %.3f, \"levels\": %d, "
                  "\"peak_scratch_bytes\": %zu}}\n",
-                 c.opts.builder == SP_BUILDER_DEVICE ? "device" : "host", c.opts.bvh_mode, c.accel.n_slots, c.accel.n_nodes,
+                 c.opts.builder == SP_BUILDER_DEVICE ? "device" : (c.opts.builder == SP_BUILDER_DEVICE_SAH ? "device_sah" : "host"), c.opts.bvh_mode, c.accel.n_slots, c.accel.n_nodes,
                  c.accel.bvh.max_depth, c.s->dev.stackless, t.ms_bounds, t.ms_bvh, t.ms_wide, t.ms_pack, t.ms_copies, b.ms_bounds_up,
-                 b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes,
+                 b.ms_codes, b.ms_sort, b.ms_hierarchy, b.ms_fit, b.ms_copy_back, b.passes, b.peak_bytes, q.ms_bounds_up, q.ms_levels,
+                 q.ms_subtrees, q.ms_number, q.ms_emit, q.ms_copy_back, q.levels, q.top_nodes, q.subtrees, q.peak_bytes,
                  c.device_finish() ? "device" : "host", f.ms_inputs_up, f.ms_collapse, f.ms_sums, f.ms_bases, f.ms_emit, f.ms_pack,
                  f.ms_parents, f.levels, f.peak_bytes);
 }
@@ -1239,7 +1268,7 @@ static int build_residency(UploadCall& c)
     std::vector<spd::Material> mats;
     SP_TRY(convert_materials(h, mats));
     c.timing = UploadTiming{}; // the stage times start here
-    build_trees(h, a, c.opts, BuildOn::DEVICE, c.tm, c.device_finish() ? &c.dtree : nullptr);
+    build_trees(h, a, c.opts, BuildOn::DEVICE, c.tm, c.device_finish() ? &c.dtree : nullptr, c.hooks.sah_small);
     std::vector<sph::PrimBounds>().swap(a.bounds); // nothing below reads them: not held beside the records
     if (!c.device_finish()) finish_host(h, a, c.opts, c.tm);
     SP_TRY(upload_scene_arrays(c));

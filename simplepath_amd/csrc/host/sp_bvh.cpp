@@ -7,6 +7,7 @@
 // SAH (Wald 2007) with the same node format; it changes only the visiting order.
 #include "sp_host.hpp"
 #include "../common/sp_lbvh.h"
+#include "../common/sp_sah.h"
 #include "../common/sp_wide.h"
 #include "../common/sp_refit.h"
 
@@ -110,15 +111,8 @@ struct SahBuilder {
     std::vector<float>             cx, cy, cz;
     std::vector<BvhNode>           nodes;
     int                            max_leaf;
-    float                          trav_cost = 1.0f; // node visit cost in triangle tests
     int                            max_depth = 0;
 
-    static float area(const Box& b)
-    {
-        const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-        if (!(dx >= 0.0f)) return 0.0f;
-        return 2.0f * (dx * dy + dy * dz + dz * dx);
-    }
     const float* cen(int d) const { return d == 0 ? cx.data() : (d == 1 ? cy.data() : cz.data()); }
 
     uint32_t build(size_t first, size_t last, int depth)
@@ -145,71 +139,43 @@ struct SahBuilder {
             return me;
         };
         if (n <= 1) return make_leaf();
-        constexpr int BINS = 32;
-        float best_cost = INFINITY;
-        int   best_dim = -1, best_bin = -1;
+        sah::Box nb;
+        for (int i = 0; i < 3; ++i) { nb.lo[i] = bb.lo[i]; nb.hi[i] = bb.hi[i]; }
+        sah::Best best;
         for (int d = 0; d < 3; ++d) {
             const float lo = cb.lo[d], hi = cb.hi[d];
             if (!(hi > lo)) continue;
-            const float  k = BINS * (1.0f - 1e-5f) / (hi - lo);
-            Box          bins[BINS];
-            int          cnt[BINS] = {};
-            for (auto& b : bins) b = empty_box();
+            const float  k = sah::scale(lo, hi);
+            sah::Box     bins[sah::BINS];
+            int          cnt[sah::BINS] = {};
+            for (auto& b : bins) b = sah::empty_box();
             const float* c = cen(d);
             for (size_t i = first; i < last; ++i) {
                 const int32_t id = ids[i];
-                int           bi = static_cast<int>((c[id] - lo) * k);
-                bi               = std::min(std::max(bi, 0), BINS - 1);
+                const int     bi = sah::bin_of(c[id], lo, k);
                 cnt[bi]++;
-                bins[bi] = merge(bins[bi], bounds[id]);
+                sah::grow(bins[bi], bounds[id].lo, bounds[id].hi);
             }
-            float right_area[BINS];
-            int   right_cnt[BINS];
-            Box   acc = empty_box();
-            int   ac  = 0;
-            for (int b = BINS - 1; b > 0; --b) {
-                PrimBounds pb;
-                for (int i = 0; i < 3; ++i) { pb.lo[i] = bins[b].lo[i]; pb.hi[i] = bins[b].hi[i]; }
-                if (cnt[b]) acc = merge(acc, pb);
-                ac += cnt[b];
-                right_area[b] = area(acc);
-                right_cnt[b]  = ac;
-            }
-            acc = empty_box();
-            ac  = 0;
-            for (int b = 0; b < BINS - 1; ++b) {
-                PrimBounds pb;
-                for (int i = 0; i < 3; ++i) { pb.lo[i] = bins[b].lo[i]; pb.hi[i] = bins[b].hi[i]; }
-                if (cnt[b]) acc = merge(acc, pb);
-                ac += cnt[b];
-                if (ac == 0 || right_cnt[b + 1] == 0) continue;
-                const float cost = area(acc) * ac + right_area[b + 1] * right_cnt[b + 1];
-                if (cost < best_cost) { best_cost = cost; best_dim = d; best_bin = b; }
-            }
+            sah::sweep(d, cnt, bins, best);
         }
-        const float leaf_cost = area(bb) * static_cast<float>(n);
-        // traversal cost ~ 1 triangle test per node visit; stop when the split does not pay
-        if (best_dim < 0 || (n <= static_cast<size_t>(max_leaf) && best_cost + trav_cost * area(bb) >= leaf_cost)) {
-            if (best_dim < 0 && n > static_cast<size_t>(max_leaf)) {
-                // all centroids coincide: median split by index
-                const size_t mid = first + n / 2;
-                const uint32_t l = build(first, mid, depth + 1);
-                const uint32_t r = build(mid, last, depth + 1);
-                BvhNode& nd = nodes[me];
-                for (int i = 0; i < 3; ++i) { nd.lo[i] = bb.lo[i]; nd.hi[i] = bb.hi[i]; }
-                nd.a = l; nd.b = r;
-                return me;
-            }
-            return make_leaf();
+        const sah::Decision what = sah::decide(nb, static_cast<uint32_t>(n), static_cast<uint32_t>(max_leaf), best);
+        const int           best_dim = best.dim, best_bin = best.bin;
+        if (what == sah::MEDIAN) {
+            // all centroids coincide: median split by index
+            const size_t mid = first + n / 2;
+            const uint32_t l = build(first, mid, depth + 1);
+            const uint32_t r = build(mid, last, depth + 1);
+            BvhNode& nd = nodes[me];
+            for (int i = 0; i < 3; ++i) { nd.lo[i] = bb.lo[i]; nd.hi[i] = bb.hi[i]; }
+            nd.a = l; nd.b = r;
+            return me;
         }
+        if (what == sah::LEAF) return make_leaf();
         const float  lo = cb.lo[best_dim], hi = cb.hi[best_dim];
-        const float  k  = BINS * (1.0f - 1e-5f) / (hi - lo);
+        const float  k  = sah::scale(lo, hi);
         const float* c  = cen(best_dim);
-        auto mid_it = std::stable_partition(ids.begin() + first, ids.begin() + last, [&](int32_t id) {
-            int bi = static_cast<int>((c[id] - lo) * k);
-            bi     = std::min(std::max(bi, 0), BINS - 1);
-            return bi <= best_bin;
-        });
+        auto mid_it = std::stable_partition(ids.begin() + first, ids.begin() + last,
+                                            [&](int32_t id) { return sah::goes_left(c[id], lo, k, best_bin); });
         size_t mid = static_cast<size_t>(mid_it - ids.begin());
         if (mid == first || mid == last) mid = first + n / 2;
         const uint32_t l = build(first, mid, depth + 1);
@@ -241,6 +207,135 @@ Bvh build_bvh_sah(const std::vector<PrimBounds>& bounds, int max_leaf)
     out.nodes      = std::move(b.nodes);
     out.prim_order = std::move(b.ids);
     out.max_depth  = b.max_depth;
+    return out;
+}
+
+// The same tree level by level, the host restatement of the device SAH build
+// (sp_sah_build.hip).  All open nodes of a level work on one ids array that stays stably
+// partitioned; nodes are numbered breadth first, then subtree sizes bottom-up give the pre-order
+// indices top-down (left = me + 1, right = me + 1 + nodes(left)).  What decides the tree -- node
+// box, centroid box, bins -- enters only through differences, products and comparisons, so these
+// are plain min / max reductions here, taken in reverse slot order on purpose: the sign of a zero
+// extreme may differ from the recursive fold's and must not matter.  The stored box is the
+// recursion's fold over the node's slots in the order they have when the node is split (its own
+// partition comes after), which only differs from a min / max in the sign of a zero extreme.
+Bvh build_bvh_sah_levels(const std::vector<PrimBounds>& bounds, int max_leaf)
+{
+    Bvh          out;
+    const size_t n = bounds.size();
+    if (n >= (size_t(1) << BVH_AXIS_SHIFT)) throw std::runtime_error("too many primitives for the SAH BVH");
+    if (n == 0) return out;
+    struct LNode {
+        uint32_t first, count, left = 0, right = 0, axis = 0, size = 1, pre = 0;
+        bool     leaf = true;
+        float    lo[3] = { 0.0f, 0.0f, 0.0f }, hi[3] = { 0.0f, 0.0f, 0.0f };
+    };
+    std::vector<LNode>    bfs{ LNode{ 0u, (uint32_t)n } };
+    std::vector<int32_t>  ids(n), next(n);
+    for (size_t i = 0; i < n; ++i) ids[i] = (int32_t)i;
+    std::vector<uint32_t> open{ 0u }, opened;
+    auto cen = [&](int32_t id, int d) { return sah::centre(bounds[(size_t)id].lo[d], bounds[(size_t)id].hi[d]); };
+    int  levels = 0;
+    while (!open.empty()) {
+        ++levels;
+        next = ids; // slots outside a split keep their place
+        opened.clear();
+        for (const uint32_t me : open) {
+            const uint32_t first = bfs[me].first, cnt_n = bfs[me].count, last = first + cnt_n;
+            sah::Box bb = sah::empty_box(), cb = sah::empty_box();
+            float    zlo[3] = { 0.0f, 0.0f, 0.0f }, zhi[3] = { 0.0f, 0.0f, 0.0f }; // the last slot's zero, per extreme
+            bool     has_lo[3] = {}, has_hi[3] = {};
+            for (uint32_t i = last; i-- > first;) {
+                const PrimBounds& b = bounds[(size_t)ids[i]];
+                for (int d = 0; d < 3; ++d) {
+                    bb.lo[d] = lbvh::lower(bb.lo[d], b.lo[d]);
+                    bb.hi[d] = lbvh::upper(bb.hi[d], b.hi[d]);
+                    if (b.lo[d] == 0.0f && !has_lo[d]) { has_lo[d] = true; zlo[d] = b.lo[d]; }
+                    if (b.hi[d] == 0.0f && !has_hi[d]) { has_hi[d] = true; zhi[d] = b.hi[d]; }
+                    const float c = cen(ids[i], d);
+                    cb.lo[d] = lbvh::lower(cb.lo[d], c);
+                    cb.hi[d] = lbvh::upper(cb.hi[d], c);
+                }
+            }
+            // the stored box: the recursion's fold in slot order keeps the later operand on a tie
+            // between +0 and -0, so a zero extreme has the sign of the last slot that holds a zero
+            for (int d = 0; d < 3; ++d) {
+                if (bb.lo[d] == 0.0f) bb.lo[d] = zlo[d];
+                if (bb.hi[d] == 0.0f) bb.hi[d] = zhi[d];
+                bfs[me].lo[d] = bb.lo[d];
+                bfs[me].hi[d] = bb.hi[d];
+            }
+            if (cnt_n <= 1) continue;
+            sah::Best best;
+            for (int d = 0; d < 3; ++d) {
+                const float lo = cb.lo[d], hi = cb.hi[d];
+                if (!(hi > lo)) continue;
+                const float k = sah::scale(lo, hi);
+                sah::Box    bins[sah::BINS];
+                int         cnt[sah::BINS] = {};
+                for (auto& b : bins) b = sah::empty_box();
+                for (uint32_t i = last; i-- > first;) {
+                    const PrimBounds& b  = bounds[(size_t)ids[i]];
+                    const int         bi = sah::bin_of(cen(ids[i], d), lo, k);
+                    cnt[bi]++;
+                    for (int e = 0; e < 3; ++e) {
+                        bins[bi].lo[e] = lbvh::lower(bins[bi].lo[e], b.lo[e]);
+                        bins[bi].hi[e] = lbvh::upper(bins[bi].hi[e], b.hi[e]);
+                    }
+                }
+                sah::sweep(d, cnt, bins, best);
+            }
+            const sah::Decision what = sah::decide(bb, cnt_n, (uint32_t)max_leaf, best);
+            if (what == sah::LEAF) continue;
+            uint32_t mid = first + cnt_n / 2, axis = 0;
+            if (what == sah::SPLIT) {
+                // stable partition as an exclusive scan of the predicate over the node's range
+                const float lo = cb.lo[best.dim], k = sah::scale(cb.lo[best.dim], cb.hi[best.dim]);
+                uint32_t    lefts = 0;
+                for (uint32_t i = first; i < last; ++i) lefts += sah::goes_left(cen(ids[i], best.dim), lo, k, best.bin) ? 1u : 0u;
+                axis = (uint32_t)best.dim;
+                if (lefts != 0 && lefts != cnt_n) { // (else: the order stays, halved by index)
+                    mid = first + lefts;
+                    uint32_t l = first, r = mid;
+                    for (uint32_t i = first; i < last; ++i)
+                        next[sah::goes_left(cen(ids[i], best.dim), lo, k, best.bin) ? l++ : r++] = ids[i];
+                }
+            }
+            const uint32_t l = (uint32_t)bfs.size();
+            bfs[me].leaf  = false;
+            bfs[me].axis  = axis;
+            bfs[me].left  = l;
+            bfs[me].right = l + 1;
+            bfs.push_back(LNode{ first, mid - first });
+            bfs.push_back(LNode{ mid, last - mid });
+            opened.push_back(l);
+            opened.push_back(l + 1);
+        }
+        ids.swap(next);
+        open.swap(opened);
+    }
+    // subtree sizes bottom-up (children lie behind their parent), pre-order indices top-down
+    for (size_t i = bfs.size(); i-- > 0;)
+        if (!bfs[i].leaf) bfs[i].size = 1u + bfs[bfs[i].left].size + bfs[bfs[i].right].size;
+    for (size_t i = 0; i < bfs.size(); ++i)
+        if (!bfs[i].leaf) {
+            bfs[bfs[i].left].pre  = bfs[i].pre + 1u;
+            bfs[bfs[i].right].pre = bfs[i].pre + 1u + bfs[bfs[i].left].size;
+        }
+    out.nodes.assign(bfs.size(), BvhNode{});
+    for (const LNode& b : bfs) {
+        BvhNode& nd = out.nodes[b.pre];
+        for (int d = 0; d < 3; ++d) { nd.lo[d] = b.lo[d]; nd.hi[d] = b.hi[d]; }
+        if (b.leaf) {
+            nd.a = b.first;
+            nd.b = b.count | BVH_LEAF;
+        } else {
+            nd.a = bfs[b.left].pre | b.axis << BVH_AXIS_SHIFT;
+            nd.b = bfs[b.right].pre;
+        }
+    }
+    out.prim_order = std::move(ids);
+    out.max_depth  = levels;
     return out;
 }
 

@@ -165,6 +165,9 @@ struct PrimBounds {
 Bvh build_bvh_reference(const std::vector<PrimBounds>& bounds);
 // Binned SAH construction (product default).
 Bvh build_bvh_sah(const std::vector<PrimBounds>& bounds, int max_leaf = 4);
+// The same tree level by level: the host restatement of the device SAH builder
+// (sp_sah_build.hip).  Equal to build_bvh_sah byte for byte on finite bounds.
+Bvh build_bvh_sah_levels(const std::vector<PrimBounds>& bounds, int max_leaf = 4);
 
 // Linear BVH (Morton order + Karras 2012 ranges): the host restatement of the device builder
 // (sp_build.hip), the same tree bit for bit.  max_leaf 1..4.

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Wall time of one scene upload, stage by stage, for the host and the device BVH builder.
+"""Wall time of one scene upload, stage by stage, for the host and the device BVH builders.
 
     python tools/upload_timing.py --scene bunny --scene lucy --builders host,device --repeat 2
+    python tools/upload_timing.py --scene lucy --builders host,device,device_sah --repeat 2
     python tools/upload_timing.py --scene lucy --builders host --finish device
 
 Each upload runs in a child process of its own (a fresh process: the library is loaded, the
 scene parsed, and one upload timed), with SP_UPLOAD_TIMING=1, under which the library prints its
 stage times: bounds, BVH build, 8-wide collapse, primitive-record packing, copies; and for the
 device build its own stages (bounds copy, codes, sort, hierarchy, fit passes, copy-back), the
-number of fit passes and the peak device scratch; and for the device finish (--finish device, or
-"auto" with the device builder) its stages (inputs copy, collapse levels, sums, bases, emit,
+number of fit passes and the peak device scratch; for the device SAH build ("device_sah") its
+stages (bounds copy, levels, handed-over subtrees, numbering, emission, copy-back), the level count,
+the nodes the levels split, the handed-over ranges and the peak scratch; and for the device finish (--finish device, or
+"auto" with a device builder) its stages (inputs copy, collapse levels, sums, bases, emit,
 packing, parents), the level count and its peak scratch.  Builders alternate within a repeat.  One JSON
 line per scene, builder and repeat goes to stdout."""
 import argparse
@@ -44,7 +47,7 @@ def child(path: str, builder: str, device: int, finish: str) -> None:
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scene", action="append", default=None, help="a built-in scene name or a .sp file (repeatable)")
-    ap.add_argument("--builders", default="host,device")
+    ap.add_argument("--builders", default="host,device", help="comma-separated: host, device, device_sah")
     ap.add_argument("--finish", default="auto", choices=["auto", "host", "device"])
     ap.add_argument("--repeat", type=int, default=2)
     ap.add_argument("--device", type=int, default=0)
