@@ -3,13 +3,11 @@
 // the same tree bit for bit: centroid cells, 63-bit Morton codes, and the Karras (2012) ranges.
 #pragma once
 
-#include "sp_math.h"
+#include "sp_box.h"
 
 #include <cstdint>
 
 namespace lbvh {
-
-SP_HD float centre(float lo, float hi) { return (lo + hi) / 2.0f; } // sp_bvh.cpp center_of
 
 // Centroid bounds.  The accumulator starts at +-inf and a NaN value never replaces it, so the
 // result is the min / max of the ordered values in any reduction order (up to the sign of zero).

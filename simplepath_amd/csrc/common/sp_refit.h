@@ -5,24 +5,14 @@
 // exact boxes of its slots.  Nothing here looks at the boxes a tree held before.
 #pragma once
 
+#include "sp_box.h"
 #include "sp_wide.h"
 
 namespace spr {
 
-constexpr uint32_t CODE_SHIFT = 30; // spd::CODE_SHIFT: a primitive's code is kind << 30 | index
-constexpr uint32_t CODE_MASK  = (1u << CODE_SHIFT) - 1u;
-constexpr uint32_t KIND_TRIANGLE = 0u; // SP_PRIM_TRIANGLE
-
-struct Box {
-    float lo[3], hi[3];
-};
-
-SP_HD Box empty_box()
-{
-    Box b;
-    for (int i = 0; i < 3; ++i) { b.lo[i] = INFINITY; b.hi[i] = -INFINITY; }
-    return b;
-}
+using spm::Box;
+using spm::empty_box;
+using spm::fold; // a leaf's fold (lb_emit, sph::lbvh_fit_boxes): the box so far is the first operand
 
 // BBox::extend by a point (shapes/Triangle.h:228): min(p, m_min), max(p, m_max)
 SP_HD void extend(Box& b, float x, float y, float z)
@@ -41,26 +31,6 @@ SP_HD Box tri_box(const float* p0, const float* p1, const float* p2)
     extend(b, p0[0], p0[1], p0[2]);
     extend(b, p1[0], p1[1], p1[2]);
     extend(b, p2[0], p2[1], p2[2]);
-    return b;
-}
-
-// a leaf's fold (lb_emit, sph::lbvh_fit_boxes): the box so far is the first operand
-SP_HD void fold(Box& node, const Box& b)
-{
-    for (int i = 0; i < 3; ++i) {
-        node.lo[i] = spm::sse_min(node.lo[i], b.lo[i]);
-        node.hi[i] = spm::sse_max(node.hi[i], b.hi[i]);
-    }
-}
-
-// an internal binary node: left child first
-SP_HD Box merge_children(const Box& l, const Box& r)
-{
-    Box b;
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = spm::sse_min(l.lo[i], r.lo[i]);
-        b.hi[i] = spm::sse_max(l.hi[i], r.hi[i]);
-    }
     return b;
 }
 

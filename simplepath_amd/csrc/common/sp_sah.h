@@ -5,39 +5,17 @@
 // leaf / split / median decision and the partition predicate.
 #pragma once
 
-#include "sp_math.h"
+#include "sp_box.h"
 
 #include <cmath>
 #include <cstdint>
 
 namespace sah {
 
+using spm::Box;
+using spm::empty_box;
+
 constexpr int BINS = 32;
-
-struct Box { // sph::PrimBounds
-    float lo[3], hi[3];
-};
-
-SP_HD Box empty_box()
-{
-    Box b;
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = INFINITY;
-        b.hi[i] = -INFINITY;
-    }
-    return b;
-}
-// merge (math/BBox.h:192) with _mm_min_ps / _mm_max_ps operand order: the accumulator comes first,
-// so on an exact tie between +0 and -0 the later operand wins
-SP_HD void grow(Box& acc, const float* lo, const float* hi)
-{
-    for (int i = 0; i < 3; ++i) {
-        acc.lo[i] = spm::sse_min(acc.lo[i], lo[i]);
-        acc.hi[i] = spm::sse_max(acc.hi[i], hi[i]);
-    }
-}
-
-SP_HD float centre(float lo, float hi) { return (lo + hi) / 2.0f; }
 
 // Only finite bounds have an order-independent tree: an infinite or empty bound gives a NaN
 // centroid, and folds over NaN are not associative.  The device build refuses such input.
@@ -82,7 +60,7 @@ SP_HD void sweep(int d, const int* cnt, const Box* bins, Best& best)
     Box   acc = empty_box();
     int   ac  = 0;
     for (int b = BINS - 1; b > 0; --b) {
-        if (cnt[b]) grow(acc, bins[b].lo, bins[b].hi);
+        if (cnt[b]) spm::fold(acc, bins[b]);
         ac += cnt[b];
         right_area[b] = area(acc);
         right_cnt[b]  = ac;
@@ -90,7 +68,7 @@ SP_HD void sweep(int d, const int* cnt, const Box* bins, Best& best)
     acc = empty_box();
     ac  = 0;
     for (int b = 0; b < BINS - 1; ++b) {
-        if (cnt[b]) grow(acc, bins[b].lo, bins[b].hi);
+        if (cnt[b]) spm::fold(acc, bins[b]);
         ac += cnt[b];
         if (ac == 0 || right_cnt[b + 1] == 0) continue;
         const float cost = area(acc) * ac + right_area[b + 1] * right_cnt[b + 1];

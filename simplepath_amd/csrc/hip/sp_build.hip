@@ -5,33 +5,18 @@
 // ranges with one thread per internal node, an exclusive count of the kept candidates, node
 // emission with the leaf boxes, and the internal boxes in passes.  No launch reads bytes that
 // another workgroup wrote in that same launch, except the pass words of the box fit, where a
-// stale or same-pass value only delays a node by one pass (lb_fit_pass).  No kernel spins.
-#include "sp_build.hpp"
+// stale or same-pass value only delays a node by one pass (sp_devbuild.hpp launch_fit_pass).  No
+// kernel spins.
+#include "sp_devbuild.hpp"
 #include "../common/sp_lbvh.h"
 
-#include <hip/hip_runtime.h>
-
-#include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include <algorithm>
-#include <chrono>
 
 namespace spb {
 namespace {
 
-constexpr int      BLOCK       = 256;
 constexpr uint32_t MAX_PARTIAL = 1024; // blocks of the first reduction stage
 constexpr int      MAX_PASSES  = 160;  // tree height <= 64 + 32 key bits; beyond it the build fails
-
-struct Node { // sph::BvhNode
-    float    lo[3];
-    uint32_t a;
-    float    hi[3];
-    uint32_t b;
-};
-static_assert(sizeof(Node) == sizeof(sph::BvhNode), "node layout");
 
 // min / max of six values per thread over the block; thread 0 holds the result
 __device__ void block_bounds(float v[6])
@@ -57,7 +42,7 @@ __global__ __launch_bounds__(BLOCK) void lb_centroid_bounds(const sph::PrimBound
     float v[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK)
         for (int d = 0; d < 3; ++d) {
-            const float c = lbvh::centre(bounds[i].lo[d], bounds[i].hi[d]);
+            const float c = spm::centre(bounds[i].lo[d], bounds[i].hi[d]);
             v[d]          = lbvh::lower(v[d], c);
             v[d + 3]      = lbvh::upper(v[d + 3], c);
         }
@@ -88,7 +73,7 @@ __global__ __launch_bounds__(BLOCK) void lb_codes(const sph::PrimBounds* __restr
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     uint32_t q[3];
-    for (int d = 0; d < 3; ++d) q[d] = lbvh::cell(lbvh::centre(bounds[i].lo[d], bounds[i].hi[d]), cb[d], cb[d + 3]);
+    for (int d = 0; d < 3; ++d) q[d] = lbvh::cell(spm::centre(bounds[i].lo[d], bounds[i].hi[d]), cb[d], cb[d + 3]);
     codes[i] = lbvh::code(q[0], q[1], q[2]);
     ids[i]   = i;
 }
@@ -147,69 +132,20 @@ __global__ __launch_bounds__(BLOCK) void lb_emit(const sph::PrimBounds* __restri
     pass_of[k] = 1u;
 }
 
-// Box fit, pass `pass` >= 2: an internal node whose children both carry a pass word in [1, pass)
-// merges their boxes.  Such a word was written by an earlier launch, and so was the box it
-// announces: both are visible here.  A word another workgroup writes in this launch reads as 0
-// or as `pass`, either of which only leaves the node to the next pass.
-__global__ __launch_bounds__(BLOCK) void lb_fit_pass(Node* __restrict__ nodes, uint32_t m, uint32_t* __restrict__ pass_of,
-                                                     uint32_t pass, uint32_t* __restrict__ fitted)
-{
-    const uint32_t k   = blockIdx.x * BLOCK + threadIdx.x;
-    int            did = 0;
-    if (k < m && pass_of[k] == 0u) {
-        const uint32_t l = nodes[k].a & sph::BVH_CHILD_MASK, r = nodes[k].b;
-        if (l < m && r < m) {
-            const uint32_t pl = pass_of[l], pr = pass_of[r];
-            if (pl >= 1u && pl < pass && pr >= 1u && pr < pass) {
-                for (int d = 0; d < 3; ++d) {
-                    nodes[k].lo[d] = spm::sse_min(nodes[l].lo[d], nodes[r].lo[d]);
-                    nodes[k].hi[d] = spm::sse_max(nodes[l].hi[d], nodes[r].hi[d]);
-                }
-                pass_of[k] = pass;
-                did        = 1;
-            }
-        }
-    }
-    const int total = __syncthreads_count(did);
-    if (threadIdx.x == 0 && total) atomicAdd(&fitted[pass], (uint32_t)total);
-}
-
-uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) / BLOCK); }
-
 } // namespace
 
 int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, sph::Bvh& out, BuildStats& st, std::string& err,
                       bool timed, DeviceTree* keep)
 {
-    if (keep) keep->reset();
-    out = sph::Bvh{};
-    st  = BuildStats{};
+    st             = BuildStats{};
     const size_t n = bounds.size();
-    if (n >= (size_t(1) << sph::BVH_AXIS_SHIFT)) throw sph::SpError(SP_ERR_UNSUPPORTED, "too many primitives for the linear BVH");
-    if (max_leaf < 1 || max_leaf > 4) throw sph::SpError(SP_ERR_ARG, "linear BVH: leaf size must be 1..4");
+    open_binary(n, max_leaf, "linear BVH", out, keep);
     if (n <= 1) { // nothing to sort or link: empty, or one leaf
         out = sph::build_bvh_lbvh(bounds, max_leaf);
         return SP_OK;
     }
-    using clock = std::chrono::steady_clock;
-    auto t0     = clock::now();
-    auto lap    = [&](double& ms) {
-        if (timed) (void)hipDeviceSynchronize();
-        const auto t1 = clock::now();
-        ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    };
-    Arena mem;
-    auto  failed = [&](const char* what, hipError_t e) {
-        err = std::string("device BVH build: ") + what + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return SP_ERR_HIP;
-    };
-#define SPB_HIP(call)                                         \
-    do {                                                      \
-        const hipError_t e__ = (call);                        \
-        if (e__ != hipSuccess) return failed(#call, e__);     \
-    } while (0)
+    Stage  stage("device BVH build", err, timed);
+    Arena& mem = stage.mem; // (the name the error texts carry)
 
     const uint32_t un = (uint32_t)n, total = 2u * un - 1u;
     sph::PrimBounds* d_bounds = nullptr;
@@ -224,7 +160,7 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
     SPB_HIP(mem.get(&d_id_in, n));
     SPB_HIP(mem.get(&d_order, n));
     SPB_HIP(hipMemcpy(d_bounds, bounds.data(), n * sizeof(sph::PrimBounds), hipMemcpyHostToDevice));
-    lap(st.ms_bounds_up);
+    stage.lap(st.ms_bounds_up);
 
     // ---- centroid bounds, codes
     const uint32_t nb1 = std::min(MAX_PARTIAL, blocks_for(n));
@@ -232,7 +168,7 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
     hipLaunchKernelGGL(lb_centroid_bounds_final, dim3(1), dim3(BLOCK), 0, 0, d_partial, nb1, d_cb);
     hipLaunchKernelGGL(lb_codes, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, d_bounds, un, d_cb, d_code_in, d_id_in);
     SPB_HIP(hipGetLastError());
-    lap(st.ms_codes);
+    stage.lap(st.ms_codes);
 
     // ---- stable sort of (code, id) by code
     {
@@ -242,7 +178,7 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
         SPB_HIP(mem.get(&d_tmp, tmp_bytes));
         SPB_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_code_in, d_code, d_id_in, d_order, n, 0u, 63u, hipStream_t(0)));
     }
-    lap(st.ms_sort);
+    stage.lap(st.ms_sort);
 
     // ---- ranges, kept candidates, numbering
     lbvh::Range* d_rng = nullptr;
@@ -252,21 +188,14 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
     SPB_HIP(mem.get(&d_index, total));
     hipLaunchKernelGGL(lb_hierarchy, dim3(blocks_for(n - 1)), dim3(BLOCK), 0, 0, d_code, un, (uint32_t)max_leaf, d_rng, d_keep);
     SPB_HIP(hipGetLastError());
-    {
-        size_t tmp_bytes = 0;
-        SPB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_keep, d_index, 0u, (size_t)total, rocprim::plus<uint32_t>(), hipStream_t(0)));
-        unsigned char* d_tmp = nullptr;
-        SPB_HIP(mem.get(&d_tmp, tmp_bytes));
-        SPB_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_keep, d_index, 0u, (size_t)total, rocprim::plus<uint32_t>(), hipStream_t(0)));
-    }
+    Scan scan;
+    SPB_HIP(scan.reserve(mem, total));
+    SPB_HIP(scan.run(d_keep, d_index, total));
     uint32_t last_index = 0, last_keep = 0;
     SPB_HIP(hipMemcpy(&last_index, d_index + (total - 1), 4, hipMemcpyDeviceToHost));
     SPB_HIP(hipMemcpy(&last_keep, d_keep + (total - 1), 4, hipMemcpyDeviceToHost));
     const uint32_t m = last_index + last_keep;
-    if (m == 0 || m > total) {
-        err = "device BVH build: the kept-node count is out of range";
-        return SP_ERR_HIP;
-    }
+    if (m == 0 || m > total) return stage.refuse("the kept-node count is out of range");
 
     // ---- nodes and leaf boxes, then the internal boxes in passes
     Node*     d_nodes = nullptr;
@@ -278,48 +207,24 @@ int build_lbvh_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, 
     hipLaunchKernelGGL(lb_emit, dim3(blocks_for(total)), dim3(BLOCK), 0, 0, d_bounds, d_order, d_rng, d_keep, d_index, un,
                        (uint32_t)max_leaf, m, d_nodes, d_pass);
     SPB_HIP(hipGetLastError());
-    lap(st.ms_hierarchy);
+    stage.lap(st.ms_hierarchy);
     // a binary tree with m nodes has (m - 1) / 2 internal ones
     const uint32_t internal = (m - 1u) / 2u;
     uint32_t       done     = 0;
     for (uint32_t pass = 2; done < internal; ++pass) {
-        if (pass > (uint32_t)MAX_PASSES) {
-            err = "device BVH build: the box fit did not finish";
-            return SP_ERR_HIP;
-        }
-        hipLaunchKernelGGL(lb_fit_pass, dim3(blocks_for(m)), dim3(BLOCK), 0, 0, d_nodes, m, d_pass, pass, d_fitted);
+        if (pass > (uint32_t)MAX_PASSES) return stage.refuse("the box fit did not finish");
+        launch_fit_pass(d_nodes, m, d_pass, pass, d_fitted + pass);
         SPB_HIP(hipGetLastError());
         uint32_t now = 0;
         SPB_HIP(hipMemcpy(&now, d_fitted + pass, 4, hipMemcpyDeviceToHost));
         ++st.passes;
-        if (now == 0) {
-            err = "device BVH build: a fit pass made no progress";
-            return SP_ERR_HIP;
-        }
+        if (now == 0) return stage.refuse("a fit pass made no progress");
         done += now;
     }
-    lap(st.ms_fit);
-    if (keep) {
-        mem.release(d_nodes);
-        mem.release(d_order);
-        keep->nodes   = d_nodes;
-        keep->order   = d_order;
-        keep->n_nodes = m;
-        keep->n_slots = un;
-        st.peak_bytes = mem.peak;
-        out.max_depth = st.passes + 1;
-        return SP_OK;
-    }
-
-    out.nodes.resize(m);
-    out.prim_order.resize(n);
-    SPB_HIP(hipMemcpy(out.nodes.data(), d_nodes, (size_t)m * sizeof(Node), hipMemcpyDeviceToHost));
-    static_assert(sizeof(int32_t) == sizeof(uint32_t), "prim_order");
-    SPB_HIP(hipMemcpy(out.prim_order.data(), d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    lap(st.ms_copy_back);
+    stage.lap(st.ms_fit);
     st.peak_bytes = mem.peak;
-    out.max_depth = sph::bvh_walk_depth(out.nodes);
-#undef SPB_HIP
+    if (const int rc = finish_binary(stage, d_nodes, m, d_order, un, keep, out, st.ms_copy_back)) return rc;
+    out.max_depth = keep ? st.passes + 1 : sph::bvh_walk_depth(out.nodes);
     return SP_OK;
 }
 

@@ -6,7 +6,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -16,31 +15,6 @@ struct BuildStats {
     double ms_bounds_up = 0, ms_codes = 0, ms_sort = 0, ms_hierarchy = 0, ms_fit = 0, ms_copy_back = 0;
     int    passes     = 0; // fit launches over the internal nodes
     size_t peak_bytes = 0; // device scratch alive at once, the sort's and the scan's temporaries included
-};
-
-// a build's device scratch (sp_build.hip, sp_finish.hip): freed when the build returns, whichever way
-struct Arena {
-    std::vector<void*> ptrs;
-    size_t             bytes = 0, peak = 0;
-    ~Arena()
-    {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** out, size_t count)
-    {
-        void*            p = nullptr;
-        const size_t     b = std::max<size_t>(count * sizeof(T), 16);
-        const hipError_t e = hipMalloc(&p, b);
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        bytes += b;
-        peak = std::max(peak, bytes);
-        *out = static_cast<T*>(p);
-        return hipSuccess;
-    }
-    // hands a block over to the caller, who frees it
-    void release(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
 };
 
 // A tree that stays on the device (the device finish works on it there).  It owns both blocks:

@@ -9,30 +9,15 @@
 // kernel boundary; no kernel spins or waits on a counter, and nothing is placed with atomics (the
 // error word alone is an atomicMax of the error code).
 #include "sp_finish.hpp"
-#include "sp_build.hpp"
+#include "sp_devbuild.hpp"
 #include "../common/sp_wide.h"
-
-#include <hip/hip_runtime.h>
-
-#include <rocprim/device/device_scan.hpp>
-
-#include <chrono>
-#include <vector>
 
 namespace spf {
 namespace {
 
-constexpr int      BLOCK      = 256;
-constexpr uint32_t CODE_SHIFT = 30; // spd::CODE_SHIFT
-constexpr uint32_t CODE_MASK  = (1u << CODE_SHIFT) - 1u;
-
-struct Node { // sph::BvhNode
-    float    lo[3];
-    uint32_t a;
-    float    hi[3];
-    uint32_t b;
-};
-static_assert(sizeof(Node) == sizeof(sph::BvhNode), "node layout");
+using spb::BLOCK;
+using spb::blocks_for;
+using spb::Node;
 
 // per item, in arrays of `cap` entries
 struct Items {
@@ -172,8 +157,8 @@ __global__ __launch_bounds__(BLOCK) void fw_emit(const Node* __restrict__ nodes,
     }
 }
 
-// slot_tri, slot_code: the triangle's vertices by prim_order (zero for other primitives), the
-// primitive code in p0.w
+// slot_tri, slot_code: the record (spb::packed_record) and the code of the primitive in each slot,
+// by prim_order
 __global__ __launch_bounds__(BLOCK) void fw_pack(const uint32_t* __restrict__ order, uint32_t n_slots,
                                                  const uint32_t* __restrict__ codes, uint32_t n_prims,
                                                  const float* __restrict__ verts, uint64_t n_verts,
@@ -184,16 +169,9 @@ __global__ __launch_bounds__(BLOCK) void fw_pack(const uint32_t* __restrict__ or
     if (sl >= n_slots) return;
     const uint32_t p    = order[sl];
     const uint32_t code = p < n_prims ? codes[p] : 0u;
-    const uint32_t kind = code >> CODE_SHIFT, idx = code & CODE_MASK;
     float4         v[3];
-    for (int k = 0; k < 3; ++k) v[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (kind == (uint32_t)SP_PRIM_TRIANGLE && 3ull * idx + 2ull < n_indices)
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t vi = indices[3ull * idx + k];
-            if (vi < n_verts) v[k] = make_float4(verts[3 * vi], verts[3 * vi + 1], verts[3 * vi + 2], 0.0f);
-        }
-    v[0].w          = __uint_as_float(code);
-    slot_code[sl]   = code;
+    spb::packed_record(code, verts, n_verts, indices, n_indices, v);
+    slot_code[sl] = code;
     for (int k = 0; k < 3; ++k) slot_tri[3ull * sl + k] = v[k];
 }
 
@@ -219,8 +197,6 @@ __global__ __launch_bounds__(BLOCK) void fw_parents(const Node* __restrict__ nod
     if (r < n_nodes) parents[r] = k;
 }
 
-uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) / BLOCK); }
-
 // the caller's outputs while they are filled: emptied again unless the finish ends well
 struct Outputs {
     FinishOut& o;
@@ -237,30 +213,10 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
 {
     out.reset();
     st = FinishStats{};
-    using clock = std::chrono::steady_clock;
-    auto t0     = clock::now();
-    auto lap    = [&](double& ms) {
-        if (timed) (void)hipDeviceSynchronize();
-        const auto t1 = clock::now();
-        ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    };
-    spb::Arena mem;
-    Outputs    res{ out };
-    auto       failed = [&](const char* what, hipError_t e) {
-        err = std::string("device finish: ") + what + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return SP_ERR_HIP;
-    };
-    auto refuse = [&](int code) {
-        err = std::string("device finish: ") + spw::error_text(code);
-        return SP_ERR_HIP;
-    };
-#define SPF_HIP(call)                                         \
-    do {                                                      \
-        const hipError_t e__ = (call);                        \
-        if (e__ != hipSuccess) return failed(#call, e__);     \
-    } while (0)
+    spb::Stage  stage("device finish", err, timed);
+    spb::Arena& mem = stage.mem; // (the name the error texts carry)
+    Outputs     res{ out };
+    auto        refuse = [&](int code) { return stage.refuse(spw::error_text(code)); };
     auto alloc_out = [&](void** p, size_t& bytes_out, size_t bytes) -> hipError_t {
         const hipError_t e = hipMalloc(p, bytes);
         if (e == hipSuccess) bytes_out = bytes;
@@ -268,43 +224,43 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
         return e;
     };
     if (in.n_nodes == 0 || in.n_slots == 0) return SP_OK; // no bounded primitive: no tree, no records
-    const Node* nodes = reinterpret_cast<const Node*>(in.d_nodes);
+    const Node* nodes = in.d_nodes;
 
     // ---- inputs that are not resident: the order (host builder), codes, vertex positions
     const uint32_t* d_order = in.d_order;
     if (!d_order) {
         uint32_t* p = nullptr;
-        SPF_HIP(mem.get(&p, in.n_slots));
+        SPB_HIP(mem.get(&p, in.n_slots));
         static_assert(sizeof(int32_t) == sizeof(uint32_t), "prim_order");
-        SPF_HIP(hipMemcpy(p, in.h_order, (size_t)in.n_slots * 4, hipMemcpyHostToDevice));
+        SPB_HIP(hipMemcpy(p, in.h_order, (size_t)in.n_slots * 4, hipMemcpyHostToDevice));
         d_order = p;
     }
     uint32_t* d_codes = nullptr;
     float*    d_verts = nullptr;
-    SPF_HIP(mem.get(&d_codes, in.n_prims));
-    SPF_HIP(mem.get(&d_verts, in.n_verts * 3));
-    if (in.n_prims) SPF_HIP(hipMemcpy(d_codes, in.h_codes, (size_t)in.n_prims * 4, hipMemcpyHostToDevice));
+    SPB_HIP(mem.get(&d_codes, in.n_prims));
+    SPB_HIP(mem.get(&d_verts, in.n_verts * 3));
+    if (in.n_prims) SPB_HIP(hipMemcpy(d_codes, in.h_codes, (size_t)in.n_prims * 4, hipMemcpyHostToDevice));
     static_assert(sizeof(spm::f3) == 12, "vertex layout");
-    if (in.n_verts) SPF_HIP(hipMemcpy(d_verts, in.h_verts, in.n_verts * 12, hipMemcpyHostToDevice));
-    lap(st.ms_inputs_up);
+    if (in.n_verts) SPB_HIP(hipMemcpy(d_verts, in.h_verts, in.n_verts * 12, hipMemcpyHostToDevice));
+    stage.lap(st.ms_inputs_up);
 
     // ---- records in the binary tree's order
-    SPF_HIP(alloc_out(&res.o.slot_tri, res.o.slot_tri_bytes, (size_t)in.n_slots * 3 * sizeof(float4)));
-    SPF_HIP(alloc_out(&res.o.slot_code, res.o.slot_code_bytes, (size_t)in.n_slots * sizeof(uint32_t)));
+    SPB_HIP(alloc_out(&res.o.slot_tri, res.o.slot_tri_bytes, (size_t)in.n_slots * 3 * sizeof(float4)));
+    SPB_HIP(alloc_out(&res.o.slot_code, res.o.slot_code_bytes, (size_t)in.n_slots * sizeof(uint32_t)));
     hipLaunchKernelGGL(fw_pack, dim3(blocks_for(in.n_slots)), dim3(BLOCK), 0, 0, d_order, in.n_slots, d_codes, in.n_prims, d_verts,
                        (uint64_t)in.n_verts, in.d_indices, (uint64_t)in.n_indices, static_cast<float4*>(res.o.slot_tri),
                        static_cast<uint32_t*>(res.o.slot_code));
-    SPF_HIP(hipGetLastError());
-    lap(st.ms_pack);
+    SPB_HIP(hipGetLastError());
+    stage.lap(st.ms_pack);
 
     // ---- parent links
     if (in.want_parents) {
-        SPF_HIP(alloc_out(&res.o.parents, res.o.parents_bytes, (size_t)in.n_nodes * sizeof(uint32_t)));
-        SPF_HIP(hipMemset(res.o.parents, 0, res.o.parents_bytes));
+        SPB_HIP(alloc_out(&res.o.parents, res.o.parents_bytes, (size_t)in.n_nodes * sizeof(uint32_t)));
+        SPB_HIP(hipMemset(res.o.parents, 0, res.o.parents_bytes));
         hipLaunchKernelGGL(fw_parents, dim3(blocks_for(in.n_nodes)), dim3(BLOCK), 0, 0, nodes, in.n_nodes,
                            static_cast<uint32_t*>(res.o.parents));
-        SPF_HIP(hipGetLastError());
-        lap(st.ms_parents);
+        SPB_HIP(hipGetLastError());
+        stage.lap(st.ms_parents);
     }
 
     if (in.want_wide) {
@@ -312,39 +268,35 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
         const uint32_t cap = std::max(1u, (in.n_nodes - 1u) / 2u);
         Items          it{};
         uint32_t *     d_err = nullptr, *d_next = nullptr;
-        SPF_HIP(mem.get(&it.root, cap));
-        SPF_HIP(mem.get(&it.info, cap));
-        SPF_HIP(mem.get(&it.kid, (size_t)cap * 8));
-        SPF_HIP(mem.get(&it.words, (size_t)cap * 20));
-        SPF_HIP(mem.get(&it.count, cap));
-        SPF_HIP(mem.get(&it.first, cap));
-        SPF_HIP(mem.get(&it.n_sub, cap));
-        SPF_HIP(mem.get(&it.l_sub, cap));
-        SPF_HIP(mem.get(&it.record, cap));
-        SPF_HIP(mem.get(&it.child_base, cap));
-        SPF_HIP(mem.get(&it.leaf_base, cap));
-        SPF_HIP(mem.get(&d_err, 1));
-        SPF_HIP(mem.get(&d_next, 1));
-        SPF_HIP(hipMemset(d_err, 0, 4));
-        SPF_HIP(hipMemset(it.root, 0, 4)); // item 0: the binary root
-        size_t scan_bytes = 0;
-        SPF_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, it.count, it.first, 0u, (size_t)cap, rocprim::plus<uint32_t>(), hipStream_t(0)));
-        unsigned char* d_scan = nullptr;
-        SPF_HIP(mem.get(&d_scan, scan_bytes));
+        SPB_HIP(mem.get(&it.root, cap));
+        SPB_HIP(mem.get(&it.info, cap));
+        SPB_HIP(mem.get(&it.kid, (size_t)cap * 8));
+        SPB_HIP(mem.get(&it.words, (size_t)cap * 20));
+        SPB_HIP(mem.get(&it.count, cap));
+        SPB_HIP(mem.get(&it.first, cap));
+        SPB_HIP(mem.get(&it.n_sub, cap));
+        SPB_HIP(mem.get(&it.l_sub, cap));
+        SPB_HIP(mem.get(&it.record, cap));
+        SPB_HIP(mem.get(&it.child_base, cap));
+        SPB_HIP(mem.get(&it.leaf_base, cap));
+        SPB_HIP(mem.get(&d_err, 1));
+        SPB_HIP(mem.get(&d_next, 1));
+        SPB_HIP(hipMemset(d_err, 0, 4));
+        SPB_HIP(hipMemset(it.root, 0, 4)); // item 0: the binary root
+        spb::Scan scan;
+        SPB_HIP(scan.reserve(mem, cap));
 
         // 1. top-down: one launch set per level; the host reads the next level's size
         std::vector<uint32_t> level_off{ 0u }, level_cnt{ 1u };
         for (;;) {
             const uint32_t off = level_off.back(), cnt = level_cnt.back();
             hipLaunchKernelGGL(fw_collapse, dim3(blocks_for(cnt)), dim3(BLOCK), 0, 0, nodes, in.n_nodes, it, off, cnt, d_err);
-            SPF_HIP(hipGetLastError());
-            size_t need = scan_bytes; // (the query was for the largest size)
-            SPF_HIP(rocprim::exclusive_scan(d_scan, need, it.count + off, it.first + off, 0u, (size_t)cnt, rocprim::plus<uint32_t>(),
-                                            hipStream_t(0)));
+            SPB_HIP(hipGetLastError());
+            SPB_HIP(scan.run(it.count + off, it.first + off, cnt));
             hipLaunchKernelGGL(fw_scatter, dim3(blocks_for(cnt)), dim3(BLOCK), 0, 0, it, off, cnt, cap, d_next, d_err);
-            SPF_HIP(hipGetLastError());
+            SPB_HIP(hipGetLastError());
             uint32_t next = 0;
-            SPF_HIP(hipMemcpy(&next, d_next, 4, hipMemcpyDeviceToHost));
+            SPB_HIP(hipMemcpy(&next, d_next, 4, hipMemcpyDeviceToHost));
             if (next == 0) break;
             if ((uint64_t)off + cnt + next > cap) return refuse(spw::ERR_LINKS);
             if (level_off.size() >= (size_t)spw::MAX_LEVELS) return refuse(spw::ERR_LEVELS);
@@ -353,50 +305,49 @@ int finish_device(const FinishIn& in, FinishOut& out, FinishStats& st, std::stri
         }
         const uint32_t total = level_off.back() + level_cnt.back();
         st.levels            = (int)level_off.size();
-        lap(st.ms_collapse);
+        stage.lap(st.ms_collapse);
         // 2. bottom-up: subtree sums
         for (size_t l = level_off.size(); l-- > 0;) {
             hipLaunchKernelGGL(fw_sums, dim3(blocks_for(level_cnt[l])), dim3(BLOCK), 0, 0, it, level_off[l], level_cnt[l], cap, d_err);
-            SPF_HIP(hipGetLastError());
+            SPB_HIP(hipGetLastError());
         }
-        lap(st.ms_sums);
+        stage.lap(st.ms_sums);
         // 3. top-down: bases
         for (size_t l = 0; l < level_off.size(); ++l) {
             hipLaunchKernelGGL(fw_bases, dim3(blocks_for(level_cnt[l])), dim3(BLOCK), 0, 0, it, level_off[l], level_cnt[l], cap);
-            SPF_HIP(hipGetLastError());
+            SPB_HIP(hipGetLastError());
         }
         // the error word, once; with it the root's sums
         uint32_t code = 0, n_root = 0, l_root = 0;
-        SPF_HIP(hipMemcpy(&code, d_err, 4, hipMemcpyDeviceToHost));
-        SPF_HIP(hipMemcpy(&n_root, it.n_sub, 4, hipMemcpyDeviceToHost));
-        SPF_HIP(hipMemcpy(&l_root, it.l_sub, 4, hipMemcpyDeviceToHost));
-        lap(st.ms_bases);
+        SPB_HIP(hipMemcpy(&code, d_err, 4, hipMemcpyDeviceToHost));
+        SPB_HIP(hipMemcpy(&n_root, it.n_sub, 4, hipMemcpyDeviceToHost));
+        SPB_HIP(hipMemcpy(&l_root, it.l_sub, 4, hipMemcpyDeviceToHost));
+        stage.lap(st.ms_bases);
         if (code != 0) return refuse((int)code);
         if (l_root != in.n_slots) return refuse(spw::ERR_EMPTY_LEVEL); // the levels ended with primitives left over
         const uint32_t records = 1u + n_root;
         // 4. records and slots at their final places; holes stay zero
         uint32_t* d_slot_of = nullptr;
-        SPF_HIP(mem.get(&d_slot_of, l_root));
-        SPF_HIP(hipMemset(d_slot_of, 0xff, (size_t)l_root * 4));
-        SPF_HIP(alloc_out(&res.o.wnodes, res.o.wnodes_bytes, (size_t)records * 80));
-        SPF_HIP(hipMemset(res.o.wnodes, 0, res.o.wnodes_bytes));
+        SPB_HIP(mem.get(&d_slot_of, l_root));
+        SPB_HIP(hipMemset(d_slot_of, 0xff, (size_t)l_root * 4));
+        SPB_HIP(alloc_out(&res.o.wnodes, res.o.wnodes_bytes, (size_t)records * 80));
+        SPB_HIP(hipMemset(res.o.wnodes, 0, res.o.wnodes_bytes));
         hipLaunchKernelGGL(fw_emit, dim3(blocks_for(total)), dim3(BLOCK), 0, 0, nodes, it, total, records, l_root,
                            static_cast<uint32_t*>(res.o.wnodes), d_slot_of);
-        SPF_HIP(hipGetLastError());
-        lap(st.ms_emit);
-        SPF_HIP(alloc_out(&res.o.wslot_tri, res.o.wslot_tri_bytes, (size_t)l_root * 3 * sizeof(float4)));
+        SPB_HIP(hipGetLastError());
+        stage.lap(st.ms_emit);
+        SPB_HIP(alloc_out(&res.o.wslot_tri, res.o.wslot_tri_bytes, (size_t)l_root * 3 * sizeof(float4)));
         hipLaunchKernelGGL(fw_pack_wide, dim3(blocks_for(l_root)), dim3(BLOCK), 0, 0, d_slot_of, l_root, in.n_slots,
                            static_cast<const float4*>(res.o.slot_tri), static_cast<float4*>(res.o.wslot_tri));
-        SPF_HIP(hipGetLastError());
+        SPB_HIP(hipGetLastError());
         res.o.records    = records;
         res.o.wide_slots = l_root;
         res.o.depth      = (int)level_off.size();
     }
-    SPF_HIP(hipDeviceSynchronize()); // the scratch goes away with this call
-    lap(st.ms_pack);
+    SPB_HIP(hipDeviceSynchronize()); // the scratch goes away with this call
+    stage.lap(st.ms_pack);
     st.peak_bytes = mem.peak;
     res.keep      = true;
-#undef SPF_HIP
     return SP_OK;
 }
 

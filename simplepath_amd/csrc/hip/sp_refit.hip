@@ -3,8 +3,8 @@
 //
 // Stages, each its own launch: the records of the binary tree's slots and of the wide tree's slots
 // from the new positions (the code of a slot names its primitive: slot_code, and p0.w of a wide
-// record); the leaves' boxes and, in passes, the internal boxes of the binary tree (lb_fit_pass's
-// rule); the records of the 8-wide tree bottom-up in passes of the same kind, each record quantised
+// record); the leaves' boxes and, in passes, the internal boxes of the binary tree (the linear
+// build's pass, spb::launch_fit_pass); the records of the 8-wide tree bottom-up in passes of the same kind, each record quantised
 // again from the exact boxes of its slots (sp_refit.h).  Every hand-off between workgroups is a
 // kernel boundary: a node or record is fitted in pass k only from children whose pass word, written
 // by an earlier launch, lies in [1, k).  No kernel spins or counts arrivals, nothing is placed with
@@ -12,41 +12,20 @@
 // them once, after the last pass.  The number of passes is the height of each tree, which the
 // resident scene knows.
 #include "sp_refit.hpp"
-#include "sp_build.hpp"
+#include "sp_devbuild.hpp"
 #include "../common/sp_refit.h"
-
-#include <hip/hip_runtime.h>
-
-#include <chrono>
 
 namespace spr {
 namespace {
 
-constexpr int BLOCK = 256;
-
-struct Node { // sph::BvhNode
-    float    lo[3];
-    uint32_t a;
-    float    hi[3];
-    uint32_t b;
-};
-static_assert(sizeof(Node) == sizeof(sph::BvhNode), "node layout");
+using spb::BLOCK;
+using spb::blocks_for;
+using spb::Node;
+using spb::packed_record;
+using spm::CODE_MASK;
+using spm::CODE_SHIFT;
+using spm::KIND_TRIANGLE;
 static_assert(sizeof(sph::PrimBounds) == 24, "bounds layout");
-
-// the three positions of the primitive named by `code` (fw_pack's rule: zero for what is not a
-// triangle or does not lie in the arrays), the code in p0.w
-__device__ inline void packed_record(uint32_t code, const float* __restrict__ verts, uint64_t n_verts,
-                                     const uint32_t* __restrict__ indices, uint64_t n_indices, float4 v[3])
-{
-    const uint32_t kind = code >> CODE_SHIFT, idx = code & CODE_MASK;
-    for (int k = 0; k < 3; ++k) v[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (kind == KIND_TRIANGLE && 3ull * idx + 2ull < n_indices)
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t vi = indices[3ull * idx + k];
-            if (vi < n_verts) v[k] = make_float4(verts[3 * vi], verts[3 * vi + 1], verts[3 * vi + 2], 0.0f);
-        }
-    v[0].w = __uint_as_float(code);
-}
 
 // one thread per slot of the binary tree's order
 __global__ __launch_bounds__(BLOCK) void rf_pack(const uint32_t* __restrict__ slot_code, uint32_t n_slots,
@@ -112,33 +91,6 @@ __global__ __launch_bounds__(BLOCK) void rf_leaf_boxes(Node* __restrict__ nodes,
     }
     for (int d = 0; d < 3; ++d) { nodes[k].lo[d] = box.lo[d]; nodes[k].hi[d] = box.hi[d]; }
     pass_of[k] = 1u;
-}
-
-// Box fit, pass `pass` >= 2 (lb_fit_pass's rule): an internal node whose children both carry a pass
-// word in [1, pass) merges their boxes.  Such a word was written by an earlier launch, and so was
-// the box it announces.  A word another workgroup writes in this launch reads as 0 or as `pass`;
-// either leaves the node to a later pass, where it belongs: its height is above `pass` then.
-__global__ __launch_bounds__(BLOCK) void rf_fit_pass(Node* __restrict__ nodes, uint32_t m, uint32_t* __restrict__ pass_of,
-                                                     uint32_t pass, uint32_t* __restrict__ fitted)
-{
-    const uint32_t k   = blockIdx.x * BLOCK + threadIdx.x;
-    int            did = 0;
-    if (k < m && pass_of[k] == 0u) {
-        const uint32_t l = nodes[k].a & spw::CHILD_MASK, r = nodes[k].b;
-        if (l < m && r < m) {
-            const uint32_t pl = pass_of[l], pr = pass_of[r];
-            if (pl >= 1u && pl < pass && pr >= 1u && pr < pass) {
-                for (int d = 0; d < 3; ++d) {
-                    nodes[k].lo[d] = spm::sse_min(nodes[l].lo[d], nodes[r].lo[d]);
-                    nodes[k].hi[d] = spm::sse_max(nodes[l].hi[d], nodes[r].hi[d]);
-                }
-                pass_of[k] = pass;
-                did        = 1;
-            }
-        }
-    }
-    const int total = __syncthreads_count(did);
-    if (threadIdx.x == 0 && total) atomicAdd(fitted, (uint32_t)total);
 }
 
 // what the two wide kernels share
@@ -244,34 +196,14 @@ __global__ __launch_bounds__(BLOCK) void rf_wide_pass(WideArgs g, uint32_t pass,
     if (threadIdx.x == 0 && total) atomicAdd(fitted, (uint32_t)total);
 }
 
-uint32_t blocks_for(uint64_t threads) { return (uint32_t)((threads + BLOCK - 1) / BLOCK); }
-
 } // namespace
 
 int refit_device(const RefitIn& in, RefitStats& st, std::string& err, bool timed)
 {
-    st          = RefitStats{};
-    using clock = std::chrono::steady_clock;
-    const auto start = clock::now();
-    auto       t0    = start;
-    auto       lap   = [&](double& ms) {
-        if (!timed) return;
-        (void)hipDeviceSynchronize();
-        const auto t1 = clock::now();
-        ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    };
-    spb::Arena mem;
-    auto       failed = [&](const char* what, hipError_t e) {
-        err = std::string("device refit: ") + what + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return SP_ERR_HIP;
-    };
-#define SPR_HIP(call)                                         \
-    do {                                                      \
-        const hipError_t e__ = (call);                        \
-        if (e__ != hipSuccess) return failed(#call, e__);     \
-    } while (0)
+    st               = RefitStats{};
+    const auto  start = spb::Stage::clock::now();
+    spb::Stage  stage("device refit", err, timed);
+    spb::Arena& mem = stage.mem; // (the name the error texts carry)
 
     // ---- scratch: the new positions, the shape bounds, pass words, exact boxes, three counters
     const bool             wide = in.d_wnodes != nullptr && in.records != 0;
@@ -279,20 +211,20 @@ int refit_device(const RefitIn& in, RefitStats& st, std::string& err, bool timed
     sph::PrimBounds*       d_shapes = nullptr;
     uint32_t *             d_pass = nullptr, *d_wpass = nullptr, *d_ctr = nullptr; // ctr: binary fitted, wide fitted, error
     float*                 d_exact = nullptr;
-    SPR_HIP(mem.get(&d_verts, in.n_verts * 3));
-    SPR_HIP(mem.get(&d_shapes, in.n_shapes));
-    SPR_HIP(mem.get(&d_pass, in.n_nodes));
-    SPR_HIP(mem.get(&d_ctr, 4));
+    SPB_HIP(mem.get(&d_verts, in.n_verts * 3));
+    SPB_HIP(mem.get(&d_shapes, in.n_shapes));
+    SPB_HIP(mem.get(&d_pass, in.n_nodes));
+    SPB_HIP(mem.get(&d_ctr, 4));
     if (wide) {
-        SPR_HIP(mem.get(&d_wpass, in.records));
-        SPR_HIP(mem.get(&d_exact, (size_t)in.records * 6));
+        SPB_HIP(mem.get(&d_wpass, in.records));
+        SPB_HIP(mem.get(&d_exact, (size_t)in.records * 6));
     }
-    SPR_HIP(hipMemset(d_ctr, 0, 16));
+    SPB_HIP(hipMemset(d_ctr, 0, 16));
     static_assert(sizeof(spm::f3) == 12, "vertex layout");
-    if (in.n_verts) SPR_HIP(hipMemcpy(d_verts, in.h_verts, in.n_verts * 12, hipMemcpyHostToDevice));
-    if (in.n_shapes) SPR_HIP(hipMemcpy(d_shapes, in.h_shape_bounds, (size_t)in.n_shapes * sizeof(sph::PrimBounds), hipMemcpyHostToDevice));
-    if (in.h_normals && in.d_normals && in.n_verts) SPR_HIP(hipMemcpy(in.d_normals, in.h_normals, in.n_verts * 12, hipMemcpyHostToDevice));
-    lap(st.ms_copy);
+    if (in.n_verts) SPB_HIP(hipMemcpy(d_verts, in.h_verts, in.n_verts * 12, hipMemcpyHostToDevice));
+    if (in.n_shapes) SPB_HIP(hipMemcpy(d_shapes, in.h_shape_bounds, (size_t)in.n_shapes * sizeof(sph::PrimBounds), hipMemcpyHostToDevice));
+    if (in.h_normals && in.d_normals && in.n_verts) SPB_HIP(hipMemcpy(in.d_normals, in.h_normals, in.n_verts * 12, hipMemcpyHostToDevice));
+    stage.lap(st.ms_copy);
 
     if (in.n_nodes != 0 && in.n_slots != 0) {
         // ---- records
@@ -301,20 +233,19 @@ int refit_device(const RefitIn& in, RefitStats& st, std::string& err, bool timed
         if (wide && in.wide_slots)
             hipLaunchKernelGGL(rf_pack_wide, dim3(blocks_for(in.wide_slots)), dim3(BLOCK), 0, 0, in.wide_slots, d_verts,
                                (uint64_t)in.n_verts, in.d_indices, (uint64_t)in.n_indices, in.d_wslot_tri);
-        SPR_HIP(hipGetLastError());
-        lap(st.ms_pack);
+        SPB_HIP(hipGetLastError());
+        stage.lap(st.ms_pack);
 
         // ---- the binary tree: leaves, then one pass per level above them
-        Node* nodes = reinterpret_cast<Node*>(in.d_nodes);
+        Node* nodes = in.d_nodes;
         hipLaunchKernelGGL(rf_leaf_boxes, dim3(blocks_for(in.n_nodes)), dim3(BLOCK), 0, 0, nodes, in.n_nodes, in.d_slot_tri, in.n_slots,
                            d_shapes, in.n_shapes, d_pass);
         for (int pass = 2; pass <= in.geom_depth; ++pass) {
-            hipLaunchKernelGGL(rf_fit_pass, dim3(blocks_for(in.n_nodes)), dim3(BLOCK), 0, 0, nodes, in.n_nodes, d_pass, (uint32_t)pass,
-                               d_ctr);
+            spb::launch_fit_pass(nodes, in.n_nodes, d_pass, (uint32_t)pass, d_ctr);
             ++st.binary_passes;
         }
-        SPR_HIP(hipGetLastError());
-        lap(st.ms_binary);
+        SPB_HIP(hipGetLastError());
+        stage.lap(st.ms_binary);
 
         // ---- the 8-wide tree
         if (wide) {
@@ -325,30 +256,20 @@ int refit_device(const RefitIn& in, RefitStats& st, std::string& err, bool timed
                 hipLaunchKernelGGL(rf_wide_pass, dim3(blocks_for(in.records)), dim3(BLOCK), 0, 0, g, (uint32_t)pass, d_ctr + 1);
                 ++st.wide_passes;
             }
-            SPR_HIP(hipGetLastError());
+            SPB_HIP(hipGetLastError());
         }
     }
     // the totals and the error word, once; the scratch goes away with this call
     uint32_t ctr[4] = {};
-    SPR_HIP(hipMemcpy(ctr, d_ctr, 16, hipMemcpyDeviceToHost)); // (waits for the null stream)
-    SPR_HIP(hipDeviceSynchronize());
-    lap(st.ms_wide);
+    SPB_HIP(hipMemcpy(ctr, d_ctr, 16, hipMemcpyDeviceToHost)); // (waits for the null stream)
+    SPB_HIP(hipDeviceSynchronize());
+    stage.lap(st.ms_wide);
     st.peak_bytes = mem.peak;
-    st.ms_total   = std::chrono::duration<double, std::milli>(clock::now() - start).count();
-#undef SPR_HIP
-    if (ctr[2] != 0) {
-        err = std::string("device refit: ") + spw::error_text((int)ctr[2]);
-        return SP_ERR_HIP;
-    }
+    st.ms_total   = std::chrono::duration<double, std::milli>(spb::Stage::clock::now() - start).count();
+    if (ctr[2] != 0) return stage.refuse(spw::error_text((int)ctr[2]));
     if (in.n_nodes != 0 && in.n_slots != 0) {
-        if (ctr[0] != (in.n_nodes - 1u) / 2u) {
-            err = "device refit: the box fit did not reach every internal node";
-            return SP_ERR_HIP;
-        }
-        if (wide && ctr[1] != in.records) {
-            err = "device refit: the wide fit did not reach every record";
-            return SP_ERR_HIP;
-        }
+        if (ctr[0] != (in.n_nodes - 1u) / 2u) return stage.refuse("the box fit did not reach every internal node");
+        if (wide && ctr[1] != in.records) return stage.refuse("the wide fit did not reach every record");
     }
     return SP_OK;
 }

@@ -16,21 +16,15 @@
 // holding a zero (on a tie between +0 and -0 the fold keeps the later operand).  No launch reads bytes
 // another workgroup wrote in that launch; the host reads three counters per level; no kernel spins.
 #include "sp_sah_build.hpp"
+#include "sp_devbuild.hpp"
 #include "../common/sp_sah.h"
 
-#include <hip/hip_runtime.h>
-
-#include <cstring>
-#include <rocprim/device/device_scan.hpp>
-
-#include <algorithm>
-#include <chrono>
 #include <type_traits>
 
 namespace spb {
 namespace {
 
-constexpr int      BLOCK   = SAH_BLOCK;
+static_assert(BLOCK == SAH_BLOCK, "the level kernels' workgroup");
 constexpr uint32_t NONE    = 0xffffffffu;
 constexpr uint32_t SUBREF  = 0x80000000u; // child reference: a handed-over range, not a level node
 constexpr uint32_t NB      = 18;                 // words per open node: node box, centroid box, last zeros
@@ -38,14 +32,6 @@ constexpr uint32_t TBL     = 3 * 7 * sah::BINS;  // words of bins per open node:
 constexpr uint32_t MIN_ID  = 0xff800000u;        // fmap(+inf): identity of the mapped minimum
 constexpr uint32_t MAX_ID  = 0x007fffffu;        // fmap(-inf): identity of the mapped maximum
 constexpr uint32_t PARENT_MASK = (1u << 30) - 1u;
-
-struct Node { // sph::BvhNode
-    float    lo[3];
-    uint32_t a;
-    float    hi[3];
-    uint32_t b;
-};
-static_assert(sizeof(Node) == sizeof(sph::BvhNode), "node layout");
 
 struct TopNode { // a node the level kernels split
     uint32_t first, count, left, right, axis, size, pre, height;
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(BLOCK) void sah_node_bounds(const sph::PrimBounds* 
     if (s != NONE && s < open) {
         const sph::PrimBounds b = bounds[ids[i]];
         for (int d = 0; d < 3; ++d) {
-            const uint32_t c = fmap(sah::centre(b.lo[d], b.hi[d]));
+            const uint32_t c = fmap(spm::centre(b.lo[d], b.hi[d]));
             v[d]     = fmap(b.lo[d]);
             v[3 + d] = fmap(b.hi[d]);
             v[6 + d] = c;
@@ -184,7 +170,7 @@ __device__ inline void add_to_bins(Table* t, const sph::PrimBounds& b, const uin
     for (int d = 0; d < 3; ++d) {
         const float lo = funmap(cbw[d]), hi = funmap(cbw[3 + d]);
         if (!(hi > lo)) continue;
-        const int bi = sah::bin_of(sah::centre(b.lo[d], b.hi[d]), lo, sah::scale(lo, hi));
+        const int bi = sah::bin_of(spm::centre(b.lo[d], b.hi[d]), lo, sah::scale(lo, hi));
         atomicAdd(&t[tbl(d, 0, bi)], 1u);
         for (int e = 0; e < 3; ++e) {
             atomicMin(&t[tbl(d, 1 + e, bi)], m[e]);
@@ -340,7 +326,7 @@ __global__ __launch_bounds__(BLOCK) void sah_flags(const sph::PrimBounds* __rest
     if (s != NONE && s < open && split[s].moves) {
         const Split           sp = split[s];
         const sph::PrimBounds b  = bounds[ids[i]];
-        f = sah::goes_left(sah::centre(b.lo[sp.dim], b.hi[sp.dim]), sp.lo, sp.k, sp.bin) ? 1u : 0u;
+        f = sah::goes_left(spm::centre(b.lo[sp.dim], b.hi[sp.dim]), sp.lo, sp.k, sp.bin) ? 1u : 0u;
     }
     flag[i] = f;
 }
@@ -391,9 +377,9 @@ __global__ __launch_bounds__(64) void sah_subtrees(const sph::PrimBounds* __rest
         for (uint32_t i = f; i < l; ++i) {
             const sph::PrimBounds b = bounds[ids[i]];
             float                 c[3];
-            for (int d = 0; d < 3; ++d) c[d] = sah::centre(b.lo[d], b.hi[d]);
-            sah::grow(bb, b.lo, b.hi);
-            sah::grow(cb, c, c);
+            for (int d = 0; d < 3; ++d) c[d] = spm::centre(b.lo[d], b.hi[d]);
+            spm::fold(bb, b.lo, b.hi);
+            spm::fold(cb, c, c);
         }
         const uint32_t n    = l - f;
         sah::Decision  what = sah::LEAF;
@@ -411,9 +397,9 @@ __global__ __launch_bounds__(64) void sah_subtrees(const sph::PrimBounds* __rest
                 }
                 for (uint32_t i = f; i < l; ++i) {
                     const sph::PrimBounds b  = bounds[ids[i]];
-                    const int             bi = sah::bin_of(sah::centre(b.lo[d], b.hi[d]), lo, k);
+                    const int             bi = sah::bin_of(spm::centre(b.lo[d], b.hi[d]), lo, k);
                     c[bi]++;
-                    sah::grow(bx[bi], b.lo, b.hi);
+                    spm::fold(bx[bi], b.lo, b.hi);
                 }
                 sah::sweep(d, c, bx, best);
             }
@@ -432,13 +418,13 @@ __global__ __launch_bounds__(64) void sah_subtrees(const sph::PrimBounds* __rest
                 uint32_t to    = f;
                 for (uint32_t i = f; i < l; ++i) {
                     const sph::PrimBounds b = bounds[ids[i]];
-                    if (sah::goes_left(sah::centre(b.lo[best.dim], b.hi[best.dim]), lo, k, best.bin)) tmp[to++] = ids[i];
+                    if (sah::goes_left(spm::centre(b.lo[best.dim], b.hi[best.dim]), lo, k, best.bin)) tmp[to++] = ids[i];
                 }
                 if (to != f && to != l) {
                     mid = to;
                     for (uint32_t i = f; i < l; ++i) {
                         const sph::PrimBounds b = bounds[ids[i]];
-                        if (!sah::goes_left(sah::centre(b.lo[best.dim], b.hi[best.dim]), lo, k, best.bin)) tmp[to++] = ids[i];
+                        if (!sah::goes_left(spm::centre(b.lo[best.dim], b.hi[best.dim]), lo, k, best.bin)) tmp[to++] = ids[i];
                     }
                     for (uint32_t i = f; i < l; ++i) ids[i] = tmp[i];
                 }
@@ -547,43 +533,21 @@ __global__ __launch_bounds__(64) void sah_emit_subtrees(const SubRoot* __restric
     }
 }
 
-uint32_t blocks_for(uint64_t threads, uint32_t block = BLOCK) { return (uint32_t)((threads + block - 1) / block); }
-
 } // namespace
 
 int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, sph::Bvh& out, SahStats& st, std::string& err,
                      bool timed, DeviceTree* keep, uint32_t small)
 {
-    if (keep) keep->reset();
-    out = sph::Bvh{};
-    st  = SahStats{};
+    st             = SahStats{};
     const size_t n = bounds.size();
-    if (n >= (size_t(1) << sph::BVH_AXIS_SHIFT)) throw sph::SpError(SP_ERR_UNSUPPORTED, "too many primitives for the SAH BVH");
-    if (max_leaf < 1 || max_leaf > 4) throw sph::SpError(SP_ERR_ARG, "SAH BVH: leaf size must be 1..4");
+    open_binary(n, max_leaf, "SAH BVH", out, keep);
     if (n <= 1) { // empty, or one leaf
         out = sph::build_bvh_sah_levels(bounds, max_leaf);
         return SP_OK;
     }
     small = small ? std::min(std::max(small, SAH_SMALL_MIN), SAH_SMALL_MAX) : SAH_SMALL_DEFAULT;
-    using clock = std::chrono::steady_clock;
-    auto t0     = clock::now();
-    auto lap    = [&](double& ms) {
-        if (timed) (void)hipDeviceSynchronize();
-        const auto t1 = clock::now();
-        ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    };
-    Arena mem;
-    auto  failed = [&](const char* what, hipError_t e) {
-        err = std::string("device SAH build: ") + what + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return SP_ERR_HIP;
-    };
-#define SPB_HIP(call)                                         \
-    do {                                                      \
-        const hipError_t e__ = (call);                        \
-        if (e__ != hipSuccess) return failed(#call, e__);     \
-    } while (0)
+    Stage  stage("device SAH build", err, timed);
+    Arena& mem = stage.mem; // (the name the error texts carry)
 
     const uint32_t un = (uint32_t)n;
     // every open node holds more than `small` slots, and the open nodes of a level are disjoint
@@ -605,12 +569,10 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
     SPB_HIP(mem.get(&d_bins, (size_t)open_cap * TBL));
     SPB_HIP(mem.get(&d_split, open_cap));
     SPB_HIP(mem.get(&d_cnt, 1));
-    size_t scan_bytes = 0;
-    SPB_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, d_flag, d_rank, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
-    unsigned char* d_scan = nullptr;
-    SPB_HIP(mem.get(&d_scan, scan_bytes));
+    Scan scan;
+    SPB_HIP(scan.reserve(mem, n));
     SPB_HIP(hipMemcpy(d_bounds, bounds.data(), n * sizeof(sph::PrimBounds), hipMemcpyHostToDevice));
-    lap(st.ms_bounds_up);
+    stage.lap(st.ms_bounds_up);
 
     // the nodes the levels make and the handed-over ranges: both grow with the tree
     TopNode* d_tops = nullptr;
@@ -624,11 +586,7 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
         hipError_t     e  = mem.get(&np, nc);
         if (e != hipSuccess) return e;
         if (used) e = hipMemcpy(np, ptr, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice);
-        if (ptr) {
-            mem.release(ptr);
-            mem.bytes -= std::max<size_t>((size_t)cap * sizeof(T), 16);
-            (void)hipFree(ptr);
-        }
+        if (ptr) mem.drop(ptr);
         ptr = np;
         cap = nc;
         return e;
@@ -653,10 +611,7 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
     hipLaunchKernelGGL(sah_start, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, d_bounds, un, root_open ? 1u : 0u, d_ids[0], d_seg[0], d_cnt);
     SPB_HIP(hipGetLastError());
     SPB_HIP(hipMemcpy(&c, d_cnt, sizeof c, hipMemcpyDeviceToHost));
-    if (c.bad & 1u) {
-        err = "device SAH build: a primitive's bounds are not finite";
-        return SP_ERR_UNSUPPORTED;
-    }
+    if (c.bad & 1u) return stage.refuse("a primitive's bounds are not finite", SP_ERR_UNSUPPORTED);
 
     // ---- the levels
     std::vector<uint32_t> level_begin; // of the level nodes, by level; the last entry is their count
@@ -665,10 +620,7 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
     level_begin.push_back(0u);
     while (open) {
         level_begin.push_back(c.tops);
-        if (open > open_cap) {
-            err = "device SAH build: more open nodes than slots allow";
-            return SP_ERR_HIP;
-        }
+        if (open > open_cap) return stage.refuse("more open nodes than slots allow");
         SPB_HIP(reserve(d_tops, top_cap, c.tops, c.tops + 2u * open));
         SPB_HIP(reserve(d_subs, sub_cap, c.subs, c.subs + 2u * open));
         SPB_HIP(hipMemsetAsync(&d_cnt->next_open, 0, 4, hipStream_t(0)));
@@ -679,7 +631,7 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
                            small, top_cap, sub_cap, open_cap, d_tops, d_subs, d_split, d_open[cur ^ 1], d_cnt);
         hipLaunchKernelGGL(sah_flags, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, d_bounds, d_ids[cur], d_seg[cur], un, open, d_split, d_flag);
         SPB_HIP(hipGetLastError());
-        SPB_HIP(rocprim::exclusive_scan(d_scan, scan_bytes, d_flag, d_rank, 0u, n, rocprim::plus<uint32_t>(), hipStream_t(0)));
+        SPB_HIP(scan.run(d_flag, d_rank, n));
         hipLaunchKernelGGL(sah_scatter, dim3(blocks_for(n)), dim3(BLOCK), 0, 0, d_ids[cur], d_seg[cur], un, open, d_split, d_flag, d_rank,
                            d_ids[cur ^ 1], d_seg[cur ^ 1]);
         SPB_HIP(hipGetLastError());
@@ -687,31 +639,20 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
         SPB_HIP(hipMemcpy(&c, d_cnt, sizeof c, hipMemcpyDeviceToHost));
         ++st.levels;
         if ((c.bad & 2u) || c.tops + c.subs != tops_before + subs_before + 2u * open || c.tops > top_cap || c.subs > sub_cap ||
-            c.next_open != c.tops - tops_before) {
-            err = "device SAH build: a level did not split every open node";
-            return SP_ERR_HIP;
-        }
+            c.next_open != c.tops - tops_before)
+            return stage.refuse("a level did not split every open node");
         open = c.next_open;
         cur ^= 1;
     }
     level_begin.push_back(c.tops); // level k of the level nodes: [level_begin[k], level_begin[k + 1])
-    lap(st.ms_levels);
+    stage.lap(st.ms_levels);
     // the level scratch goes before the nodes come
     const uint32_t n_tops = c.tops, n_subs = c.subs;
     st.top_nodes = n_tops;
     st.subtrees  = n_subs;
     uint32_t* d_order = d_ids[cur];
     uint32_t* d_tmp   = d_ids[cur ^ 1];
-    auto      drop    = [&](auto* p, size_t count, size_t size) {
-        mem.release(p);
-        mem.bytes -= std::max<size_t>(count * size, 16);
-        (void)hipFree(p);
-    };
-    drop(d_seg[0], n, 4);
-    drop(d_seg[1], n, 4);
-    drop(d_flag, n, 4);
-    drop(d_rank, n, 4);
-    drop(d_bins, (size_t)open_cap * TBL, 4);
+    for (uint32_t* p : { d_seg[0], d_seg[1], d_flag, d_rank, d_bins }) mem.drop(p);
 
     // ---- the handed-over ranges
     Node*  d_raw = nullptr;
@@ -721,7 +662,7 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
     hipLaunchKernelGGL(sah_subtrees, dim3(blocks_for(n_subs, 64)), dim3(64), 0, 0, d_bounds, d_order, d_tmp, d_subs, n_subs,
                        (uint32_t)max_leaf, d_raw, d_up);
     SPB_HIP(hipGetLastError());
-    lap(st.ms_subtrees);
+    stage.lap(st.ms_subtrees);
 
     // ---- sizes bottom-up, pre-order indices top-down
     const size_t n_levels = level_begin.size() - 1; // the first and the last "level" may be empty
@@ -746,11 +687,8 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
         m      = root.size;
         height = root.height;
     }
-    if (m == 0 || m > 2u * un - 1u) {
-        err = "device SAH build: the node count is out of range";
-        return SP_ERR_HIP;
-    }
-    lap(st.ms_number);
+    if (m == 0 || m > 2u * un - 1u) return stage.refuse("the node count is out of range");
+    stage.lap(st.ms_number);
 
     // ---- every node at its final index
     Node* d_nodes = nullptr;
@@ -759,26 +697,10 @@ int build_sah_device(const std::vector<sph::PrimBounds>& bounds, int max_leaf, s
     hipLaunchKernelGGL(sah_emit_subtrees, dim3(n_subs), dim3(64), 0, 0, d_subs, n_subs, d_raw, m, d_nodes);
     SPB_HIP(hipGetLastError());
     SPB_HIP(hipDeviceSynchronize());
-    lap(st.ms_emit);
+    stage.lap(st.ms_emit);
     st.peak_bytes = mem.peak;
     out.max_depth = (int)height;
-    if (keep) {
-        mem.release(d_nodes);
-        mem.release(d_order);
-        keep->nodes   = d_nodes;
-        keep->order   = d_order;
-        keep->n_nodes = m;
-        keep->n_slots = un;
-        return SP_OK;
-    }
-    out.nodes.resize(m);
-    out.prim_order.resize(n);
-    SPB_HIP(hipMemcpy(out.nodes.data(), d_nodes, (size_t)m * sizeof(Node), hipMemcpyDeviceToHost));
-    static_assert(sizeof(int32_t) == sizeof(uint32_t), "prim_order");
-    SPB_HIP(hipMemcpy(out.prim_order.data(), d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    lap(st.ms_copy_back);
-#undef SPB_HIP
-    return SP_OK;
+    return finish_binary(stage, d_nodes, m, d_order, un, keep, out, st.ms_copy_back);
 }
 
 } // namespace spb

@@ -24,18 +24,9 @@
 namespace sph {
 
 namespace {
-struct Box {
-    float lo[3], hi[3];
-};
-Box empty_box()
-{
-    Box b;
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = INFINITY;
-        b.hi[i] = -INFINITY;
-    }
-    return b;
-}
+using spm::Box;
+using spm::empty_box;
+static_assert(spw::LEAF == BVH_LEAF && spw::CHILD_MASK == BVH_CHILD_MASK, "sp_wide.h reads sph::BvhNode links");
 // merge (math/BBox.h:192) with _mm_min_ps / _mm_max_ps operand order
 Box merge(const Box& a, const PrimBounds& b)
 {
@@ -139,8 +130,6 @@ struct SahBuilder {
             return me;
         };
         if (n <= 1) return make_leaf();
-        sah::Box nb;
-        for (int i = 0; i < 3; ++i) { nb.lo[i] = bb.lo[i]; nb.hi[i] = bb.hi[i]; }
         sah::Best best;
         for (int d = 0; d < 3; ++d) {
             const float lo = cb.lo[d], hi = cb.hi[d];
@@ -154,11 +143,11 @@ struct SahBuilder {
                 const int32_t id = ids[i];
                 const int     bi = sah::bin_of(c[id], lo, k);
                 cnt[bi]++;
-                sah::grow(bins[bi], bounds[id].lo, bounds[id].hi);
+                spm::fold(bins[bi], bounds[id].lo, bounds[id].hi);
             }
             sah::sweep(d, cnt, bins, best);
         }
-        const sah::Decision what = sah::decide(nb, static_cast<uint32_t>(n), static_cast<uint32_t>(max_leaf), best);
+        const sah::Decision what = sah::decide(bb, static_cast<uint32_t>(n), static_cast<uint32_t>(max_leaf), best);
         const int           best_dim = best.dim, best_bin = best.bin;
         if (what == sah::MEDIAN) {
             // all centroids coincide: median split by index
@@ -234,7 +223,7 @@ Bvh build_bvh_sah_levels(const std::vector<PrimBounds>& bounds, int max_leaf)
     std::vector<int32_t>  ids(n), next(n);
     for (size_t i = 0; i < n; ++i) ids[i] = (int32_t)i;
     std::vector<uint32_t> open{ 0u }, opened;
-    auto cen = [&](int32_t id, int d) { return sah::centre(bounds[(size_t)id].lo[d], bounds[(size_t)id].hi[d]); };
+    auto cen = [&](int32_t id, int d) { return spm::centre(bounds[(size_t)id].lo[d], bounds[(size_t)id].hi[d]); };
     int  levels = 0;
     while (!open.empty()) {
         ++levels;
@@ -406,14 +395,14 @@ Bvh build_bvh_lbvh(const std::vector<PrimBounds>& bounds, int max_leaf)
     float cb_lo[3] = { INFINITY, INFINITY, INFINITY }, cb_hi[3] = { -INFINITY, -INFINITY, -INFINITY };
     for (const PrimBounds& b : bounds)
         for (int d = 0; d < 3; ++d) {
-            const float c = lbvh::centre(b.lo[d], b.hi[d]);
+            const float c = spm::centre(b.lo[d], b.hi[d]);
             cb_lo[d]      = lbvh::lower(cb_lo[d], c);
             cb_hi[d]      = lbvh::upper(cb_hi[d], c);
         }
     std::vector<uint64_t> key(n);
     for (size_t i = 0; i < n; ++i) {
         uint32_t q[3];
-        for (int d = 0; d < 3; ++d) q[d] = lbvh::cell(lbvh::centre(bounds[i].lo[d], bounds[i].hi[d]), cb_lo[d], cb_hi[d]);
+        for (int d = 0; d < 3; ++d) q[d] = lbvh::cell(spm::centre(bounds[i].lo[d], bounds[i].hi[d]), cb_lo[d], cb_hi[d]);
         key[i] = lbvh::code(q[0], q[1], q[2]);
     }
     // stable sort of (code, id) by code
