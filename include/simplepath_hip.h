@@ -24,6 +24,8 @@
  *   sp_scene_upload_with                  the same upload with the binary BVH built on the device
  *   sp_scene_bvh_check / _bvh_build_check (no counterpart: structural check of a built BVH)
  *   sp_scene_update_mesh                  (no counterpart: a moved mesh shown by refitting the resident BVHs)
+ *   sp_scene_trace_rays / _host           base/Scene.h:74 `Scene::intersect` and base/Scene.h:79
+ *                                         `Scene::intersect_p` for the caller's own rays
  *   sp_render_tiles                       main.cpp:77-107 `render_thread`: for each scheduled
  *                                         tile, for each pixel, num_pixel_samples x
  *                                         `integrator.integrate(camera.generate_ray(...))`,
@@ -660,6 +662,92 @@ int  sp_scene_update_mesh(sp_scene* scene, const sp_mesh_update* update, sp_refi
  * bvh_mode 1 is SP_ERR_ARG. */
 int  sp_scene_refit_build_check(const sp_scene* scene, const sp_upload_params* params, const sp_build_params* build,
                                 const sp_mesh_update* update, sp_bvh_check* bvh, sp_wide_check* wide);
+
+/* ---- ray queries ---------------------------------------------------------------------------
+ * sp_scene_trace_rays traces a caller's ray buffer against the resident scene: the reference's
+ * Scene::intersect(ray, limits, isect) (base/Scene.h:74, SP_QUERY_CLOSEST) and
+ * Scene::intersect_p(ray, limits) (base/Scene.h:79, SP_QUERY_ANY), which its integrators are only
+ * clients of.  The walks are the render kernels' own, so a ray finds the hit an integrator's ray
+ * would have found, bit for bit, whichever accelerator the upload chose.
+ *
+ * Geometry only: the query covers the geometry accelerator -- the unbounded shapes (planes) first,
+ * then the BVH -- as Scene::intersect does.  Lights are not intersected (a sphere light is not in
+ * the way of a query ray).  `d` need not be of unit length and `t` is in units of `d`.  The limits
+ * are the reference's RayLimits: a hit needs tmin <= t <= tmax, so tmin > tmax misses.
+ *
+ * Closest hit: t is the smallest accepted distance; kind is SP_PRIM_*; index is the triangle's
+ * index into sp_scene_desc.indices / 3 or the shape's index into sp_scene_desc.shapes; material is
+ * the index into sp_scene_desc.materials; beta and gamma are the triangle's barycentrics (the hit
+ * point is (1 - beta - gamma) v0 + beta v1 + gamma v2), 0 for the other kinds.  A miss is
+ * kind = index = material = -1 with t = the bits of the ray's own tmax, zero barycentrics and an
+ * all-zero normal.  Between primitives hit at exactly equal t the one reported is the one the walk
+ * of this residency keeps -- the rule of the images: bvh_mode 1 keeps the reference's, the 8-wide
+ * walk the lower wide slot, a device-built tree its own.  t itself does not depend on the walk.
+ *
+ * Normals: d_normals receives four floats per ray, the shading normal the integrators use (what the
+ * reference's intersect_impl leaves in Intersection::m_normal: interpolated vertex normals for a
+ * triangle, the transformed object-space normal for a sphere or plane; not flipped towards the
+ * ray) and a 0.  Leaving it NULL skips that work and the RSQRTSS table a block would copy into LDS.
+ *
+ * Any hit: d_occluded[i] is 1 exactly when some primitive accepts the ray, else 0.
+ *
+ * Rays no integrator makes: a NaN limit, an origin or direction component that is NaN or infinite,
+ * and a zero direction (which every primitive test rejects anyway) are answered as a miss without
+ * a walk.  Every other ray is walked with its own limits: tmax = +inf is allowed (a hit at
+ * t = +inf, which a denormal direction can produce, then counts), and so are rays parallel to an
+ * axis -- a direction component of +0, -0 or a denormal, an origin exactly in a box plane of the
+ * tree -- for which a box's entry distance comes out as NaN: such a box is entered, never skipped.
+ *
+ * Validation comes first and changes nothing, in this order: null scene or query; struct_size (the
+ * query's, and that of stats when given) and reserved words; unknown mode; num_rays < 0; the
+ * pointer rules of the mode -- a required pointer missing, a forbidden one given, d_rays / d_hits /
+ * d_normals not 16-byte aligned or d_occluded not 4-byte aligned -- all SP_ERR_ARG; then a scene
+ * that is not resident, SP_ERR_STATE.  num_rays == 0 succeeds and launches
+ * nothing.  More than 2^39 - 256 rays in one call are SP_ERR_UNSUPPORTED (one block of 256 per
+ * launch grid entry); a BVH whose stacks do not fit the LDS is SP_ERR_UNSUPPORTED as for a render.
+ *
+ * Ordering: the call is stream-ordered like sp_render_tiles.  It takes the scene's lock, makes
+ * `stream` wait for the previous call on the scene and records the event the next call waits for.
+ * With stats == NULL it only enqueues work: queries and renders can be queued back to back on one
+ * stream and read after one synchronize.  With stats it waits and fills them (hits: closest-hit
+ * records that are not a miss, or occluded rays; counted on the device only when asked for).
+ * The buffers must stay valid until the work has run.
+ *
+ * Scene state: a query sees what is resident -- after sp_scene_update_mesh, the moved mesh.  It
+ * does not invalidate progress objects and keeps nothing on the scene.
+ *
+ * sp_scene_trace_rays_host takes host arrays: it allocates device buffers, copies, traces, waits
+ * and copies back, as sp_render_tiles_host does.  Which outputs it needs follows the mode as above
+ * (h_hits for CLOSEST with h_normals optional, h_occluded for ANY); no alignment is asked of host
+ * arrays. */
+#define SP_HAS_RAY_QUERY 1
+
+typedef struct sp_ray     { float o[3]; float tmin; float d[3]; float tmax; } sp_ray;      /* 32 bytes */
+typedef struct sp_ray_hit { float t; int32_t kind; int32_t index; int32_t material;
+                            float beta, gamma; uint32_t reserved[2]; } sp_ray_hit;          /* 32 bytes */
+enum { SP_QUERY_CLOSEST = 0, SP_QUERY_ANY = 1 };
+typedef struct sp_ray_query {          /* zero-initialise; struct_size = sizeof */
+    uint32_t      struct_size;         /* a size the library does not know => SP_ERR_ARG */
+    int32_t       mode;                /* SP_QUERY_* */
+    const sp_ray* d_rays;              /* DEVICE, num_rays records, 16-byte aligned; required when num_rays > 0 */
+    int64_t       num_rays;
+    void*         stream;              /* hipStream_t, NULL = default stream */
+    sp_ray_hit*   d_hits;              /* DEVICE, 16-byte aligned.  CLOSEST: required.  ANY: must be NULL */
+    float*        d_normals;           /* DEVICE, 16-byte aligned.  CLOSEST, optional: 4 floats per ray
+                                          (shading normal, 0).  ANY: must be NULL */
+    uint32_t*     d_occluded;          /* DEVICE.  ANY: required, one word per ray, 1 or 0.  CLOSEST: must be NULL */
+    int32_t       reserved[4];         /* must be 0 */
+} sp_ray_query;
+typedef struct sp_ray_query_stats {    /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  launches;                 /* kernel launches issued (0 for num_rays == 0) */
+    uint64_t rays, hits;
+    float    kernel_ms;                /* HIP-event time of the query kernel */
+    int32_t  stack_depth;              /* LDS traversal-stack words per lane the walk of this mode used */
+} sp_ray_query_stats;
+int  sp_scene_trace_rays(sp_scene* scene, const sp_ray_query* query, sp_ray_query_stats* stats /* may be NULL */);
+int  sp_scene_trace_rays_host(sp_scene* scene, int32_t mode, const sp_ray* h_rays, int64_t num_rays,
+                              sp_ray_hit* h_hits, float* h_normals, uint32_t* h_occluded, sp_ray_query_stats* stats);
 
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the

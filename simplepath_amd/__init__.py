@@ -25,6 +25,7 @@ __all__ = [
     "Scene", "TileScheduler", "ColumnMajorTileScheduler", "RenderStats", "render", "render_tiles",
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
     "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
+    "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -35,6 +36,27 @@ def string_to_integrator_type(s: str) -> int:
     out = C.c_int32()
     check(lib().sp_string_to_integrator(s.encode(), C.byref(out)))
     return out.value
+
+
+# sp_ray / sp_ray_hit (include/simplepath_hip.h): the records of a ray query, 32 bytes each
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("tmin", "<f4"), ("d", "<f4", (3,)), ("tmax", "<f4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<i4"), ("index", "<i4"), ("material", "<i4"),
+                          ("beta", "<f4"), ("gamma", "<f4"), ("reserved", "<u4", (2,))])
+K_RAY_EPSILON = float(np.float32(0.001))      # RayLimits::m_t_min (math/Ray.h:17)
+K_INFINITE = float(np.finfo(np.float32).max)  # RayLimits::m_t_max: k_infinite_distance
+
+
+def make_rays(origins, directions, tmin=K_RAY_EPSILON, tmax=K_INFINITE) -> np.ndarray:
+    """RAY_DTYPE records [n] from origins, directions [n, 3] and limits (scalars or [n])."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions must both be [n, 3]")
+    rays = np.zeros(o.shape[0], dtype=RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (o.shape[0],))
+    rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (o.shape[0],))
+    return rays
 
 
 @dataclass
@@ -253,6 +275,57 @@ class Scene:
         check(lib().sp_scene_refit_build_check(self._h, C.byref(p), b, C.byref(u), C.byref(c), C.byref(w)))
         del keep
         return self._check_dict(c), self._wide_dict(w)
+
+    def trace(self, origins, directions, tmin=K_RAY_EPSILON, tmax=K_INFINITE, mode="closest", normals: bool = False):
+        """Ray queries on the resident scene from host arrays (sp_scene_trace_rays_host): the
+        reference's Scene::intersect ("closest") and Scene::intersect_p ("any") for the caller's
+        rays.  origins, directions: [n, 3]; tmin, tmax: scalars or [n] (the reference's RayLimits
+        defaults).  Geometry only -- lights are not intersected; directions need not be unit
+        vectors and t is in their units.
+        "closest" returns a RAY_HIT_DTYPE array [n] (a miss: kind = index = material = -1, t = the
+        ray's tmax), with normals=True also the shading normals [n, 3] float32 (zeros for a miss).
+        "any" returns a bool array [n]: some primitive accepts the ray."""
+        rays = make_rays(origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        m = _abi.QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+        if m == _abi.SP_QUERY_ANY:
+            if normals:
+                raise ValueError("an any-hit query has no normals")
+            occ = np.zeros(max(n, 1), dtype=np.uint32)
+            check(lib().sp_scene_trace_rays_host(self._h, m, C.c_void_p(rays.ctypes.data), n, None, None,
+                                                 C.c_void_p(occ.ctypes.data), None))
+            return occ[:n] != 0
+        hits = np.zeros(max(n, 1), dtype=RAY_HIT_DTYPE)
+        nrm = np.zeros((max(n, 1), 4), dtype=np.float32) if normals else None
+        check(lib().sp_scene_trace_rays_host(self._h, m, C.c_void_p(rays.ctypes.data), n, C.c_void_p(hits.ctypes.data),
+                                             C.c_void_p(nrm.ctypes.data) if normals else None, None, None))
+        return (hits[:n], nrm[:n, :3].copy()) if normals else hits[:n]
+
+    def trace_device(self, rays_ptr: int, n: int, hits_ptr: int = 0, normals_ptr: int = 0, occluded_ptr: int = 0,
+                     mode="closest", stream=None, stats: bool = False):
+        """Ray queries on device buffers (sp_scene_trace_rays), e.g. torch tensors' data_ptr():
+        rays_ptr n RAY_DTYPE records (a [n, 8] float32 tensor: origin, tmin, direction, tmax);
+        "closest" writes n RAY_HIT_DTYPE records to hits_ptr (a [n, 8] int32 tensor) and, when given,
+        [n, 4] float32 normals to normals_ptr; "any" writes n uint32 words to occluded_ptr.  The three
+        record buffers are 16-byte aligned (any torch allocation is).  With stats=False the query is
+        only enqueued on `stream` (returns None); with stats=True the call waits and returns a dict of
+        sp_ray_query_stats."""
+        q = _abi.sp_ray_query()
+        q.struct_size = C.sizeof(_abi.sp_ray_query)
+        q.mode = _abi.QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+        q.d_rays = rays_ptr or None
+        q.num_rays = int(n)
+        q.stream = stream
+        q.d_hits = hits_ptr or None
+        q.d_normals = normals_ptr or None
+        q.d_occluded = occluded_ptr or None
+        if not stats:
+            check(lib().sp_scene_trace_rays(self._h, C.byref(q), None))
+            return None
+        st = _abi.sp_ray_query_stats()
+        st.struct_size = C.sizeof(_abi.sp_ray_query_stats)
+        check(lib().sp_scene_trace_rays(self._h, C.byref(q), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _abi.sp_ray_query_stats._fields_ if k != "struct_size"}
 
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()

@@ -171,6 +171,31 @@ class sp_refit_stats(C.Structure):
                 ("ms_total", C.c_float), ("scratch_bytes", C.c_int64)]
 
 
+SP_QUERY_CLOSEST, SP_QUERY_ANY = 0, 1
+QUERY_MODES = {"closest": SP_QUERY_CLOSEST, "any": SP_QUERY_ANY}
+
+
+class sp_ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("tmin", C.c_float), ("d", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class sp_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("kind", C.c_int32), ("index", C.c_int32), ("material", C.c_int32),
+                ("beta", C.c_float), ("gamma", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class sp_ray_query(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32),
+                ("d_rays", C.c_void_p), ("num_rays", C.c_int64), ("stream", C.c_void_p),
+                ("d_hits", C.c_void_p), ("d_normals", C.c_void_p), ("d_occluded", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class sp_ray_query_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_int32), ("rays", C.c_uint64), ("hits", C.c_uint64),
+                ("kernel_ms", C.c_float), ("stack_depth", C.c_int32)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -240,6 +265,9 @@ SIGNATURES = {
     "sp_scene_update_mesh": (C.c_int, [C.c_void_p, C.POINTER(sp_mesh_update), C.POINTER(sp_refit_stats)]),
     "sp_scene_refit_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.POINTER(sp_build_params),
                                              C.POINTER(sp_mesh_update), C.POINTER(sp_bvh_check), C.POINTER(sp_wide_check)]),
+    "sp_scene_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_ray_query), C.POINTER(sp_ray_query_stats)]),
+    "sp_scene_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(sp_ray_query_stats)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

@@ -9,6 +9,7 @@
 #include "sp_sah_build.hpp"
 #include "sp_finish.hpp"
 #include "sp_refit.hpp"
+#include "sp_query.hpp"
 #include "../common/sp_refit.h"
 #include "../common/sp_sah.h"
 #include "../host/sp_host.hpp"
@@ -3045,6 +3046,142 @@ int sp_scene_refit_build_check(const sp_scene* s, const sp_upload_params* params
         return fail(e.code, e.what());
     } catch (const std::exception& e) {
         return fail(SP_ERR_UNSUPPORTED, std::string("refit check failed: ") + e.what());
+    }
+}
+
+// ---- ray queries (sp_query.hip) -----------------------------------------------------------------
+
+// Everything sp_scene_trace_rays refuses, in the header's order; changes nothing.  The scene's
+// lock is held (s->device is read last).  device_pointers: the alignment rules of device buffers
+// (the host form asks none of its host arrays).
+static int validate_query(const sp_scene* s, const sp_ray_query* q, const sp_ray_query_stats* stats, bool device_pointers)
+{
+    if (q->struct_size != sizeof(sp_ray_query)) return fail(SP_ERR_ARG, "sp_ray_query.struct_size is not this library's");
+    if (stats && stats->struct_size != sizeof(sp_ray_query_stats))
+        return fail(SP_ERR_ARG, "sp_ray_query_stats.struct_size is not this library's");
+    for (int32_t r : q->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_ray_query.reserved must be 0");
+    if (q->mode != SP_QUERY_CLOSEST && q->mode != SP_QUERY_ANY) return fail(SP_ERR_ARG, "unknown query mode");
+    if (q->num_rays < 0) return fail(SP_ERR_ARG, "num_rays < 0");
+    const bool any = q->mode == SP_QUERY_ANY;
+    if (any && (q->d_hits || q->d_normals)) return fail(SP_ERR_ARG, "SP_QUERY_ANY: d_hits and d_normals must be NULL");
+    if (!any && q->d_occluded) return fail(SP_ERR_ARG, "SP_QUERY_CLOSEST: d_occluded must be NULL");
+    if (q->num_rays > 0) {
+        if (!q->d_rays) return fail(SP_ERR_ARG, "d_rays is NULL");
+        if (any && !q->d_occluded) return fail(SP_ERR_ARG, "SP_QUERY_ANY needs d_occluded");
+        if (!any && !q->d_hits) return fail(SP_ERR_ARG, "SP_QUERY_CLOSEST needs d_hits");
+    }
+    if (device_pointers) {
+        const auto off = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+        if (off(q->d_rays, 16) || off(q->d_hits, 16) || off(q->d_normals, 16))
+            return fail(SP_ERR_ARG, "d_rays, d_hits and d_normals must be 16-byte aligned");
+        if (off(q->d_occluded, 4)) return fail(SP_ERR_ARG, "d_occluded must be 4-byte aligned");
+    }
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_scene_trace_rays");
+    return SP_OK;
+}
+
+static int trace_rays_impl(sp_scene* s, const sp_ray_query* q, sp_ray_query_stats* stats)
+{
+    if (int rc = validate_query(s, q, stats, true)) return rc;
+    const bool any = q->mode == SP_QUERY_ANY;
+    if (stats) {
+        *stats             = sp_ray_query_stats{};
+        stats->struct_size = sizeof(sp_ray_query_stats);
+        stats->stack_depth = any ? s->dev.any_stack_words : s->dev.stack_words;
+    }
+    if (q->num_rays == 0) return SP_OK;
+    if (q->num_rays > ((int64_t)1 << 39) - spd::QUERY_BLOCK) return fail(SP_ERR_UNSUPPORTED, "more rays than one launch takes");
+    const size_t lds_bytes = spd::query_lds_bytes(s->dev, any, q->d_normals != nullptr);
+    if (lds_bytes > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch& r      = s->scratch;
+    hipStream_t    stream = static_cast<hipStream_t>(q->stream);
+    // the previous call on this scene (a render, a refit's successor, another query) comes first
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    spd::QueryArgs a{};
+    a.rays     = q->d_rays;
+    a.num_rays = q->num_rays;
+    a.hits     = q->d_hits;
+    a.normals  = reinterpret_cast<float4*>(q->d_normals);
+    a.occluded = q->d_occluded;
+    if (stats) { // counted only when asked for: word 5 of the render counters, which every call clears for itself
+        a.hit_count = r.counters.as<unsigned long long>() + 5;
+        SP_HIP(hipMemsetAsync(a.hit_count, 0, sizeof(unsigned long long), stream));
+    }
+    SP_HIP(hipEventRecord(r.ev0, stream));
+    SP_HIP(any ? spd::launch_query_any(s->dev, a, lds_bytes, stream) : spd::launch_query_closest(s->dev, a, lds_bytes, stream));
+    if (int rc = end_call(s, stream)) return rc;
+    if (!stats) return SP_OK; // stream order: the query is only enqueued
+    SP_HIP(hipEventSynchronize(r.ev1));
+    unsigned long long hits = 0;
+    SP_HIP(hipMemcpy(&hits, a.hit_count, sizeof(hits), hipMemcpyDeviceToHost));
+    SP_HIP(hipEventElapsedTime(&stats->kernel_ms, r.ev0, r.ev1));
+    stats->launches = 1;
+    stats->rays     = (uint64_t)q->num_rays;
+    stats->hits     = hits;
+    return SP_OK;
+}
+
+int sp_scene_trace_rays(sp_scene* s, const sp_ray_query* q, sp_ray_query_stats* stats)
+{
+    if (!s || !q) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // calls on one scene run one at a time (sp_scene::mu)
+    try {
+        return trace_rays_impl(s, q, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("ray query failed: ") + e.what());
+    }
+}
+
+// the host form with the scene's lock held: the same refusals in the same order on the host
+// arrays as given, then device buffers of its own around the device form
+static int trace_rays_host_impl(sp_scene* s, int32_t mode, const sp_ray* h_rays, int64_t num_rays, sp_ray_hit* h_hits,
+                                float* h_normals, uint32_t* h_occluded, sp_ray_query_stats* stats)
+{
+    sp_ray_query q{};
+    q.struct_size = sizeof(q);
+    q.mode        = mode;
+    q.d_rays      = h_rays;
+    q.num_rays    = num_rays;
+    q.d_hits      = h_hits;
+    q.d_normals   = h_normals;
+    q.d_occluded  = h_occluded;
+    if (int rc = validate_query(s, &q, stats, false)) return rc;
+    SP_HIP(hipSetDevice(s->device));
+    const size_t  n = (size_t)num_rays;
+    DeviceScratch d_rays, d_hits, d_normals, d_occ;
+    const auto    device_copy = [](DeviceScratch& d, const void* host, size_t bytes) -> int {
+        if (host) SP_HIP(d.reserve(std::max<size_t>(bytes, 16)));
+        return SP_OK;
+    };
+    if (int rc = device_copy(d_rays, h_rays, n * sizeof(sp_ray))) return rc;
+    if (int rc = device_copy(d_hits, h_hits, n * sizeof(sp_ray_hit))) return rc;
+    if (int rc = device_copy(d_normals, h_normals, n * 4 * sizeof(float))) return rc;
+    if (int rc = device_copy(d_occ, h_occluded, n * sizeof(uint32_t))) return rc;
+    if (n) SP_HIP(hipMemcpy(d_rays.ptr, h_rays, n * sizeof(sp_ray), hipMemcpyHostToDevice));
+    q.d_rays     = d_rays.as<sp_ray>();
+    q.d_hits     = d_hits.as<sp_ray_hit>();
+    q.d_normals  = d_normals.as<float>();
+    q.d_occluded = d_occ.as<uint32_t>();
+    q.stream     = nullptr; // with the blocking copies below, as render_to_host
+    if (int rc = trace_rays_impl(s, &q, stats)) return rc;
+    if (n == 0) return SP_OK;
+    if (h_hits) SP_HIP(hipMemcpy(h_hits, d_hits.ptr, n * sizeof(sp_ray_hit), hipMemcpyDeviceToHost));
+    if (h_normals) SP_HIP(hipMemcpy(h_normals, d_normals.ptr, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_occluded) SP_HIP(hipMemcpy(h_occluded, d_occ.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_scene_trace_rays_host(sp_scene* s, int32_t mode, const sp_ray* h_rays, int64_t num_rays, sp_ray_hit* h_hits,
+                             float* h_normals, uint32_t* h_occluded, sp_ray_query_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // residency is decided, and kept, under the scene's lock
+    try {
+        return trace_rays_host_impl(s, mode, h_rays, num_rays, h_hits, h_normals, h_occluded, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("ray query failed: ") + e.what());
     }
 }
 

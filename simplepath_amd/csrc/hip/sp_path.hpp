@@ -987,6 +987,14 @@ struct WideHits {
     float    t_rest;      // smallest entry distance of the other hit inner slots
     uint32_t child_base, leaf_base, meta_lo, meta_hi;
 };
+// NAN_SAFE (the ray queries, sp_query.hip: rays no integrator makes): a child whose entry distance is
+// NaN -- slab_box keeps one from its last axis when 1 / d.z is infinite (d.z zero or a small
+// denormal) and the origin lies exactly in the child's lower z plane: 0 * inf -- is entered first and
+// never culled, as the binary walks' box test treats it (a NaN compares false: accepted), and a node
+// with hit inner children always names one of them the nearest (tmax = +inf lets a child pass with an
+// entry distance of +inf, which is not below FLT_MAX either).  The default is the render kernels'
+// code unchanged: their rays do not meet the condition.
+template <bool NAN_SAFE = false>
 __device__ __forceinline__ WideHits wide_visit(const Scene& sc, uint32_t node, const Ray& ray, const f3& inv, float tmin,
                                                float tmax, uint32_t filter = 0xffu)
 {
@@ -1022,6 +1030,7 @@ __device__ __forceinline__ WideHits wide_visit(const Scene& sc, uint32_t node, c
         const float hz = fma_f(ubyte(h ? w4.w : w4.z, k), sz, pz);
         float       t0;
         if (!wbox(lx, ly, lz, hx, hy, hz, ray, inv, tmin, tmax, t0)) continue;
+        if constexpr (NAN_SAFE) t0 = (t0 == t0) ? t0 : -k_infinite;
         if (inner) {
             r.inner |= 1u << k;
             if (t0 < best) { r.t_rest = best; best = t0; r.nearest = k; }
@@ -1030,6 +1039,8 @@ __device__ __forceinline__ WideHits wide_visit(const Scene& sc, uint32_t node, c
             r.leaf |= 1u << k;
         }
     }
+    if constexpr (NAN_SAFE)
+        if (r.inner && r.nearest < 0) r.nearest = __ffs(r.inner) - 1;
     return r;
 }
 
@@ -1044,6 +1055,7 @@ __device__ __forceinline__ uint32_t key_mask(uint32_t m, uint32_t o);
 // primitive lying in a box face, hit at t within an ulp or so of tmax, the walk can miss what the
 // cache finds.  The cache relies on that edge case not arising; it is off by default since round 6
 // (level on every DirectLighting config, profiles/r05/walk_cache/), so the default walk is exact.
+template <bool NAN_SAFE = false>
 __device__ __forceinline__ bool wide_any(const Scene& sc, const Ray& ray, float tmin, float tmax, Stack st,
                                          uint32_t* occ = nullptr)
 {
@@ -1059,7 +1071,7 @@ __device__ __forceinline__ bool wide_any(const Scene& sc, const Ray& ray, float 
 #else
 #define SP_WPROF_ANY
 #endif
-        const WideHits wh = wide_visit(sc, node, ray, inv, tmin, tmax);
+        const WideHits wh = wide_visit<NAN_SAFE>(sc, node, ray, inv, tmin, tmax);
         for (uint32_t m = wh.leaf; m; m &= m - 1) {
             const int      k    = __ffs(m) - 1;
             const uint32_t meta = ((k < 4 ? wh.meta_lo : wh.meta_hi) >> (8 * (k & 3))) & 0xffu;
@@ -1110,6 +1122,7 @@ __device__ __forceinline__ uint32_t key_mask(uint32_t m, uint32_t o)
 // dropped whole.  Every primitive whose (outward-rounded) box meets [tmin, t_closest] is tested,
 // so the result is the binary walk's except which of two primitives at exactly equal t wins
 // (here: the lower wide slot, prim_closest_w).
+template <bool NAN_SAFE = false>
 __device__ __forceinline__ Hit wide_closest(const Scene& sc, const Ray& ray, float tmin, Hit h, Stack st)
 {
     const f3       inv = mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
@@ -1121,7 +1134,7 @@ __device__ __forceinline__ Hit wide_closest(const Scene& sc, const Ray& ray, flo
 #ifdef SP_WAVE_PROF
         const uint64_t t_it = __builtin_amdgcn_s_memtime(); // region 6: closest-hit walk steps
 #endif
-        const WideHits wh = wide_visit(sc, node, ray, inv, tmin, h.t);
+        const WideHits wh = wide_visit<NAN_SAFE>(sc, node, ray, inv, tmin, h.t);
         for (uint32_t m = wh.leaf; m; m &= m - 1) {
             const int      k    = __ffs(m) - 1;
             const uint32_t meta = ((k < 4 ? wh.meta_lo : wh.meta_hi) >> (8 * (k & 3))) & 0xffu;
@@ -1464,11 +1477,12 @@ __device__ __forceinline__ Hit scene_intersect_unbounded(const Scene& sc, const 
     }
     return h;
 }
+template <bool NAN_SAFE = false> // (wide_visit)
 __device__ __forceinline__ Hit scene_intersect(const Scene& sc, const Ray& ray, float tmin, float tmax, Stack st)
 {
     Hit h = scene_intersect_unbounded(sc, ray, tmin, tmax);
     if (sc.n_nodes == 0) return h;
-    if (sc.wide_closest) return wide_closest(sc, ray, tmin, h, st);
+    if (sc.wide_closest) return wide_closest<NAN_SAFE>(sc, ray, tmin, h, st);
     return sc.stackless ? bvh_closest<true>(sc, ray, tmin, h, st) : bvh_closest<false>(sc, ray, tmin, h, st);
 }
 
@@ -1512,12 +1526,13 @@ __device__ __forceinline__ bool unbounded_any(const Scene& sc, const Ray& ray, f
     }
     return false;
 }
+template <bool NAN_SAFE = false> // (wide_visit)
 __device__ __forceinline__ bool geometry_any(const Scene& sc, const Ray& ray, float tmin, float tmax, Stack st,
                                              uint32_t* occ = nullptr)
 {
     if (unbounded_any(sc, ray, tmin, tmax)) return true;
     if (sc.n_nodes == 0) return false;
-    if (sc.wnodes) return wide_any(sc, ray, tmin, tmax, st, occ);
+    if (sc.wnodes) return wide_any<NAN_SAFE>(sc, ray, tmin, tmax, st, occ);
     return sc.stackless ? bvh_any<true>(sc, ray, tmin, tmax, st) : bvh_any<false>(sc, ray, tmin, tmax, st);
 }
 
