@@ -14,6 +14,7 @@
 // issues them (sp_math.h).  Build flags: -ffp-contract=off, IEEE division/sqrt, denormals kept.
 #pragma once
 #include "sp_device.hpp"
+#include "../common/sp_wide_visit.h"
 
 namespace spd {
 inline namespace SPD_LAYOUT_NS { // sp_device.hpp: one namespace per RNG state layout
@@ -739,6 +740,9 @@ __device__ __forceinline__ Isect finish_hit(const Scene& sc, const Hit& h, const
 //     compiler cannot prove equal, its words OR-ed in under a zero mask): twice the vector-L1
 //     lookups of node fetches, same walk and same image -- the sensitivity of the frame to them;
 //     2: the wide-leaf triangle records too.
+//   SP_XP_VISIT 1: every 8-wide node visit's box arithmetic (spw::visit: decode, slabs, ordering) is
+//     issued twice, the second on an origin the compiler cannot prove equal, its results OR-ed in
+//     under a zero mask: same walk and same image -- the share of the frame that arithmetic is (§25a).
 //   SP_XP_FASTLIBM: expf / logf / powf / sinf / cosf as the native f32 instructions (wrong image):
 //     the upper bound of replacing the exact glibc emulation's f64 arithmetic.
 //   SP_XP_SERVED_FREE: served estimates (IterativeRRNEE) draw hashed words instead of reading the
@@ -746,7 +750,10 @@ __device__ __forceinline__ Isect finish_hit(const Scene& sc, const Hit& h, const
 #ifndef SP_XP_DUP
 #define SP_XP_DUP 0
 #endif
-#if SP_XP_DUP
+#ifndef SP_XP_VISIT
+#define SP_XP_VISIT 0
+#endif
+#if SP_XP_DUP || SP_XP_VISIT
 __device__ __forceinline__ uint32_t xp_zero()
 {
     uint32_t z;
@@ -937,36 +944,6 @@ __device__ __forceinline__ bool walk_next(BinWalk<SL>& w, const f3& d, uint32_t&
 }
 
 
-// Slab test of one box with its entry distance (math/BBox.h:254 operation order).
-__device__ __forceinline__ bool slab_box(float lx, float ly, float lz, float hx, float hy, float hz, const Ray& r,
-                                         const f3& inv, float tmin, float tmax, float& t0_out)
-{
-    float t0 = tmin, t1 = tmax; // same operation order as box_hit (math/BBox.h:254)
-    {
-        float tn = (lx - r.o.x) * inv.x, tf = (hx - r.o.x) * inv.x;
-        if (tn > tf) { const float s = tn; tn = tf; tf = s; }
-        t0 = std_max(tn, t0);
-        t1 = std_min(tf, t1);
-        if (t0 > t1) return false;
-    }
-    {
-        float tn = (ly - r.o.y) * inv.y, tf = (hy - r.o.y) * inv.y;
-        if (tn > tf) { const float s = tn; tn = tf; tf = s; }
-        t0 = std_max(tn, t0);
-        t1 = std_min(tf, t1);
-        if (t0 > t1) return false;
-    }
-    {
-        float tn = (lz - r.o.z) * inv.z, tf = (hz - r.o.z) * inv.z;
-        if (tn > tf) { const float s = tn; tn = tf; tf = s; }
-        t0 = std_max(tn, t0);
-        t1 = std_min(tf, t1);
-        if (t0 > t1) return false;
-    }
-    t0_out = t0;
-    return true;
-}
-
 // ------------------------------------------------------------------------------ 8-wide BVH
 // One 80-byte fetch (5 x dwordx4) tests the boxes of up to 8 children, so a ray's chain of
 // dependent node fetches is about a third of the binary walk's.  Child boxes decode to
@@ -974,13 +951,6 @@ __device__ __forceinline__ bool slab_box(float lx, float ly, float lz, float hx,
 // accepts is accepted here too, so no primitive is missed; only the visiting order differs from
 // the binary SAH walk (closest hit: equal-distance ties; any hit: no change).  Stack entries are
 // child groups {first child << 8 | mask of pending children}: one entry per level.
-__device__ __forceinline__ bool wbox(float lx, float ly, float lz, float hx, float hy, float hz, const Ray& r, const f3& inv,
-                                     float tmin, float tmax, float& t0_out)
-{
-    return slab_box(lx, ly, lz, hx, hy, hz, r, inv, tmin, tmax, t0_out);
-}
-__device__ __forceinline__ float ubyte(uint32_t w, int k) { return (float)((w >> (8 * (k & 3))) & 0xffu); }
-
 struct WideHits {
     uint32_t inner, leaf; // slot masks
     int      nearest;     // inner slot with the smallest entry distance
@@ -988,7 +958,7 @@ struct WideHits {
     uint32_t child_base, leaf_base, meta_lo, meta_hi;
 };
 // NAN_SAFE (the ray queries, sp_query.hip: rays no integrator makes): a child whose entry distance is
-// NaN -- slab_box keeps one from its last axis when 1 / d.z is infinite (d.z zero or a small
+// NaN -- the slab test keeps one from its last axis when 1 / d.z is infinite (d.z zero or a small
 // denormal) and the origin lies exactly in the child's lower z plane: 0 * inf -- is entered first and
 // never culled, as the binary walks' box test treats it (a NaN compares false: accepted), and a node
 // with hit inner children always names one of them the nearest (tmax = +inf lets a child pass with an
@@ -1006,41 +976,21 @@ __device__ __forceinline__ WideHits wide_visit(const Scene& sc, uint32_t node, c
 #else
     const uint4    w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3], w4 = np[4];
 #endif
-    const float    px = __uint_as_float(w0.x), py = __uint_as_float(w0.y), pz = __uint_as_float(w0.z);
-    const float    sx = __uint_as_float((w0.w & 0xffu) << 23);
-    const float    sy = __uint_as_float(((w0.w >> 8) & 0xffu) << 23);
-    const float    sz = __uint_as_float(((w0.w >> 16) & 0xffu) << 23);
-    const uint32_t imask = w0.w >> 24;
-    WideHits       r;
-    r.inner = 0; r.leaf = 0; r.nearest = -1; r.t_rest = k_infinite;
-    r.child_base = w1.x; r.leaf_base = w1.y; r.meta_lo = w1.z; r.meta_hi = w1.w;
-    float best = k_infinite;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t meta  = ((k < 4 ? w1.z : w1.w) >> (8 * (k & 3))) & 0xffu;
-        const bool     inner = (imask >> k) & 1u;
-        if (!inner && meta == 0u) continue;
-        if (!((filter >> k) & 1u)) continue;
-        const int   h  = k >> 2;
-        const float lx = fma_f(ubyte(h ? w2.y : w2.x, k), sx, px);
-        const float ly = fma_f(ubyte(h ? w2.w : w2.z, k), sy, py);
-        const float lz = fma_f(ubyte(h ? w3.y : w3.x, k), sz, pz);
-        const float hx = fma_f(ubyte(h ? w3.w : w3.z, k), sx, px);
-        const float hy = fma_f(ubyte(h ? w4.y : w4.x, k), sy, py);
-        const float hz = fma_f(ubyte(h ? w4.w : w4.z, k), sz, pz);
-        float       t0;
-        if (!wbox(lx, ly, lz, hx, hy, hz, ray, inv, tmin, tmax, t0)) continue;
-        if constexpr (NAN_SAFE) t0 = (t0 == t0) ? t0 : -k_infinite;
-        if (inner) {
-            r.inner |= 1u << k;
-            if (t0 < best) { r.t_rest = best; best = t0; r.nearest = k; }
-            else r.t_rest = std_min(r.t_rest, t0);
-        } else {
-            r.leaf |= 1u << k;
-        }
+    const uint32_t w[20] = { w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w,
+                             w4.x, w4.y, w4.z, w4.w };
+    spw::Visit     v = spw::visit<NAN_SAFE>(w, ray.o.x, ray.o.y, ray.o.z, inv.x, inv.y, inv.z, tmin, tmax, filter);
+#if SP_XP_VISIT >= 1
+    {
+        const uint32_t   z = xp_zero();
+        const spw::Visit d = spw::visit<NAN_SAFE>(w, __uint_as_float(__float_as_uint(ray.o.x) | z), ray.o.y, ray.o.z, inv.x, inv.y,
+                                                  inv.z, tmin, tmax, filter);
+        v.inner |= d.inner & z; v.leaf |= d.leaf & z; v.nearest |= d.nearest & (int)z;
+        v.t_rest = __uint_as_float(__float_as_uint(v.t_rest) | (__float_as_uint(d.t_rest) & z));
     }
-    if constexpr (NAN_SAFE)
-        if (r.inner && r.nearest < 0) r.nearest = __ffs(r.inner) - 1;
+#endif
+    WideHits r;
+    r.inner = v.inner; r.leaf = v.leaf; r.nearest = v.nearest; r.t_rest = v.t_rest;
+    r.child_base = w1.x; r.leaf_base = w1.y; r.meta_lo = w1.z; r.meta_hi = w1.w;
     return r;
 }
 
@@ -1050,7 +1000,7 @@ __device__ __forceinline__ uint32_t key_mask(uint32_t m, uint32_t o);
 // primitive the ray meets in [tmin, tmax]) is true without a walk.  A hit found by the walk
 // becomes the new cached occluder.  Same answer either way: only which primitives are tested changes
 // -- PROVIDED the walk would have reached the cached primitive, i.e. no box on the way to its leaf
-// is rejected by wbox for a ray that tri_hit accepts in [tmin, tmax].  The quantised boxes are
+// is rejected by the slab test for a ray that tri_hit accepts in [tmin, tmax].  The quantised boxes are
 // rounded outward (supersets), but the slab t and the Moller-Trumbore t round differently, so for a
 // primitive lying in a box face, hit at t within an ulp or so of tmax, the walk can miss what the
 // cache finds.  The cache relies on that edge case not arising; it is off by default since round 6

@@ -67,8 +67,10 @@ __device__ __forceinline__ void count_hits(unsigned long long* counter, bool hit
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(counter, n);
 }
 
+// Waves per SIMD requested: the 7 (closest hit) and 8 (any hit) these kernels had before the one-exit
+// node visit, whose eight slots in flight would cost each a step; nothing spills.
 template <bool NORMALS>
-__global__ void __launch_bounds__(QUERY_BLOCK) sp_query_closest_kernel(Scene sc, QueryArgs a)
+__global__ void __launch_bounds__(QUERY_BLOCK, 7) sp_query_closest_kernel(Scene sc, QueryArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int tid  = threadIdx.x;
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(QUERY_BLOCK) sp_query_closest_kernel(Scene sc,
     count_hits(a.hit_count, hit);
 }
 
-__global__ void __launch_bounds__(QUERY_BLOCK) sp_query_any_kernel(Scene sc, QueryArgs a)
+__global__ void __launch_bounds__(QUERY_BLOCK, 8) sp_query_any_kernel(Scene sc, QueryArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const int      lane = threadIdx.x & 63;

@@ -45,7 +45,8 @@ namespace spd {
 
 constexpr int WF_BLOCK = 256;
 #ifndef WF_PRIM_WAVES
-#define WF_PRIM_WAVES 1 // camera-ray kernel: no occupancy request (the binary walk needs few registers)
+#define WF_PRIM_WAVES 7 // camera-ray kernel: the 7 waves per SIMD it had (71 VGPRs) before the one-exit node
+                        // visit, whose eight slots in flight would take 81; 7 spills, none in a loop (§25c)
 #endif
 #ifndef WF_TRAV_WAVES
 #define WF_TRAV_WAVES 8 // waves per SIMD requested for wf_shadow (64 VGPRs, 20 B spill; 6 / 7 / 8 measured

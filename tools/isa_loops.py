@@ -3,10 +3,16 @@
 instruction to the loop LLVM's comments place its basic block in ("This Loop Header: Depth=d",
 "in Loop: Header=BBx_y").
 
-Usage: python3 tools/isa_loops.py <kernel.s> [loop-header]   (with a header: its opcode histogram)
+Usage: python3 tools/isa_loops.py <kernel.s> [loop-header | all]   (with a header: its opcode histogram; all: every loop, not the 30 largest)
 The DirectLighting kernel's ISA: hipcc --offload-arch=gfx950 <the Makefile's flags> -S
 --offload-device-only -c simplepath_amd/csrc/hip/sp_mega_direct.hip, then the lines of
-sp_render_kernel<6, 4>."""
+sp_render_kernel<6, 4>.
+
+Since DESIGN.md §25 a loop's header block is counted with its loop also where the header names its
+parent loops first (a nested loop: the "This [Inner] Loop Header" comment is on a later line of the
+label).  Tables made before that (profiles/r08/straightline/isa_loops.txt and the other rounds')
+counted such a header block outside the loop: their rows of nested loops are lower, by some 30
+instructions for a walk loop, and are not to be set beside rows made since."""
 import collections
 import re
 import sys
@@ -14,22 +20,29 @@ import sys
 
 def blocks(lines):
     cur = "top"
+    lab = None  # the label whose comment lines are being read
     for l in lines:
         s = l.strip()
         if re.match(r"^\.LBB\d+_\d+:|^; %bb\.\d+:", s):
             m = re.search(r"Header=(BB\d+_\d+) Depth=(\d+)", s)
-            m2 = re.search(r"This Loop Header: Depth=(\d+)", s)
             lab = s.split(":")[0].lstrip(".").replace("LBB", "BB")
-            cur = lab if m2 else (m.group(1) if m else "top")
+            cur = lab if re.search(r"This (Inner )?Loop Header: Depth=", s) else (m.group(1) if m else "top")
+            continue
+        if lab and s.startswith(";"):
+            # a header inside other loops names its parents first: "=> This [Inner] Loop Header" comes
+            # on a later comment line of the same label, and the header block belongs to its own loop
+            if re.search(r"This (Inner )?Loop Header: Depth=", s):
+                cur = lab
             continue
         if not s or s.startswith((";", ".")) or s.endswith(":"):
             continue
+        lab = None
         yield cur, s.split()[0]
 
 
 def main(path, header=None):
     lines = open(path).read().split("\n")
-    if header:
+    if header and header != "all":
         c = collections.Counter(op for loop, op in blocks(lines) if loop == header)
         for op, n in c.most_common(50):
             print(op, n)
@@ -50,7 +63,14 @@ def main(path, header=None):
             c["valu"] += 1
         if "f64" in op:
             c["f64"] += 1
-    for k, c in sorted(stats.items(), key=lambda x: -x[1]["n"])[:30]:
+        # exec-mask traffic and select plumbing
+        for key, pre in (("saveexec", None), ("cbr_exec", "s_cbranch_exec"), ("s_nop", "s_nop"), ("v_cmp", "v_cmp"),
+                         ("v_cndmask", "v_cndmask"), ("v_mov", "v_mov"), ("ubyte", "v_cvt_f32_ubyte")):
+            if (pre is None and "saveexec" in op) or (pre is not None and op.startswith(pre)):
+                c[key] += 1
+        if op.startswith(("v_min_f32", "v_max_f32", "v_med3_f32")):
+            c["minmax"] += 1
+    for k, c in sorted(stats.items(), key=lambda x: -x[1]["n"])[:None if header == "all" else 30]:
         print(k, dict(c))
 
 
