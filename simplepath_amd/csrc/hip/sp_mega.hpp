@@ -399,6 +399,9 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
 #ifdef SP_TRAFFIC_DIAG
     if (lane < 32) tdg_lds[wave * 32 + lane] = 0;
 #endif
+#if SP_XP_NEE_CHECK
+    if (lane < 16) nee_chk_lds[wave * 16 + lane] = 0;
+#endif
     __syncthreads();
     Rsq   q{ lds };
     Stack st{ lds + rs_words + wave * sc.stack_words * 64, lane, sc.stack_depth };
@@ -558,7 +561,7 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
         o[0]     = acc.r;
         o[1]     = acc.g;
         o[2]     = acc.b;
-#if !defined(SP_WAVE_PROF) && !defined(SP_TRAFFIC_DIAG) // those builds use the buffer for their totals
+#if !defined(SP_WAVE_PROF) && !defined(SP_TRAFFIC_DIAG) && !SP_XP_NEE_CHECK // those builds use the buffer for their totals
         if (args.tile_diag) {
             // {t0, t1, wave, item, then per stage the largest shader-clock total of any lane}
             for (int k = 0; k < 4; ++k)
@@ -574,6 +577,12 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
     }
 #ifdef SP_WAVE_PROF
     if (args.tile_diag && lane < 16) atomicAdd(args.tile_diag + lane, wprof_lds[wave * 16 + lane]);
+#endif
+#if SP_XP_NEE_CHECK
+    if (args.tile_diag && lane < 16) {
+        if (lane == 10) atomicMax(args.tile_diag + lane, nee_chk_lds[wave * 16 + lane]);
+        else atomicAdd(args.tile_diag + lane, nee_chk_lds[wave * 16 + lane]);
+    }
 #endif
 #ifdef SP_TRAFFIC_DIAG
     if (args.tile_diag && lane < 32) atomicAdd(args.tile_diag + 16 + lane, tdg_lds[wave * 32 + lane]);

@@ -15,6 +15,7 @@
 #pragma once
 #include "sp_device.hpp"
 #include "../common/sp_wide_visit.h"
+#include "../common/sp_nee_black.h"
 
 namespace spd {
 inline namespace SPD_LAYOUT_NS { // sp_device.hpp: one namespace per RNG state layout
@@ -2428,16 +2429,19 @@ __device__ __forceinline__ rgb onesample_eval_w(const Material& m, f3 wo, f3 wi,
     if (p1 > 0.0f) r = cadd(r, cscale(m.lambert_albedo, balance(p1, inner)));
     return r;
 }
+// OneSampleMaterial::eval of a Lambertian material: no estimate, no draws
+__device__ __forceinline__ rgb lambert_eval(const Material& m)
+{
+    const float w     = lambert_only_weight(m);
+    const float p     = k_uniform_hemisphere_pdf * w;
+    const float inner = 0.0f + p;
+    rgb         r     = mkc(0, 0, 0);
+    if (p > 0.0f) r = cadd(r, cscale(m.lambert_albedo, balance(p, inner)));
+    return r;
+}
 __device__ __forceinline__ rgb onesample_eval(const Material& m, f3 wo, f3 wi, Rng& rng, const Rsq& q)
 {
-    if (m.kind == SP_MAT_LAMBERTIAN) {
-        const float w     = lambert_only_weight(m);
-        const float p     = k_uniform_hemisphere_pdf * w;
-        const float inner = 0.0f + p;
-        rgb         r     = mkc(0, 0, 0);
-        if (p > 0.0f) r = cadd(r, cscale(m.lambert_albedo, balance(p, inner)));
-        return r;
-    }
+    if (m.kind == SP_MAT_LAMBERTIAN) return lambert_eval(m);
     float w[2];
     glossy_weights(m, wo, rng, q, w);
     return onesample_eval_w(m, wo, wi, w, q);
@@ -2657,6 +2661,14 @@ __device__ __forceinline__ bool occluded(Ctx& c, const Ray& r, float tmin, float
     return hit;
 }
 
+// occluded() without the counting: direct_nee counts once it knows whether f is black
+__device__ __forceinline__ bool shadow_walk(Ctx& c, const Ray& r, float tmin, float tmax)
+{
+    bool hit;
+    SP_WPROF(3, hit = scene_any(c.sc, r, tmin, tmax, c.st, SP_OCC_CACHE ? &c.occ_slot : nullptr));
+    return hit;
+}
+
 // Shared "primary" query of every integrator: intersect_lights then intersect.
 struct Query {
     LightHit lh;
@@ -2680,20 +2692,120 @@ __device__ __forceinline__ Query trace(Ctx& c, const Ray& ray, float tmin, float
 
 // DirectLightingIntegrator::do_integrate (Integrators/Integrator.cpp:277) -- also the NEE part
 // of WhittedIntegrator.
+//
+// The reference evaluates the material, then traces the shadow ray where f is not black.  For a
+// glossy material the evaluation runs the 16-sample rho estimate, and for an occluded sample all
+// that is left of it is the stream 32 words further on and one bit -- is f black? -- that decides
+// whether the shadow ray is counted.  A shadow walk draws nothing, so the walk comes first here
+// (one call site for every lane), and an occluded lane skips the estimate: it moves its stream on by
+// the 32 words and takes the bit from spn::nee_black_known (sp_nee_black.h).  A lane
+// whose bit is unknown runs the estimate.  Same words drawn, same values, same counters.
+#ifndef SP_XP_NEE_CHECK // checking build, never the product: see nee_check
+#define SP_XP_NEE_CHECK 0
+#endif
+#if SP_XP_NEE_CHECK
+// The checking build runs the estimate on the lanes that skip it as well (on a copy of the stream)
+// and counts, per wave in LDS, flushed into words 0..15 of the render's tile_diag buffer at kernel
+// end (sp_mega.hpp): 0 votes that skipped, 1 votes that ran, 2 of those with no visible lane (run
+// for an unknown alone), 3 lanes that rode along (occluded, known, in a vote that ran), 4 occluded
+// lanes with "unknown", 5 lanes with an estimate, 6 DISAGREEMENTS between the decider and the true
+// cblack(f), 7 estimates whose weights are not in [0, 1] (not finite), 8 lanes that skipped,
+// 9 of those black, 10 the largest estimate weight w0 seen, as float bits (a maximum, not a sum).
+// Words 0..2 count the first lane of each ballot: votes under SP_NEE_SKIP 1, and under 2, where
+// nothing is voted on, no more than groups of lanes that reached this point together.  Only the
+// megakernel body (sp_mega.hpp) zeroes and flushes the row; ck_shade counts into LDS nobody reads.
+// tools/nee_check_counts.py prints the words.
+static __shared__ unsigned long long nee_chk_lds[16 * 16];
+__device__ __forceinline__ void nee_count(int k, unsigned long long n = 1ull) { atomicAdd(&nee_chk_lds[(threadIdx.x >> 6) * 16 + k], n); }
+__device__ __forceinline__ void nee_check(Ctx& c, const Material& mb, f3 wol, float P, rgb E, float A, bool coat, float cf, int known,
+                                          bool occ, bool run)
+{
+    const uint64_t vote  = __builtin_amdgcn_ballot_w64(true);
+    const bool     first = (threadIdx.x & 63) == __builtin_ctzll(vote);
+    const bool     vis   = __builtin_amdgcn_ballot_w64(!occ) != 0ull;
+    if (first) nee_count(run ? 1 : 0);
+    if (first && run && !vis) nee_count(2);
+    if (run && occ && known != spn::NEE_UNKNOWN) nee_count(3);
+    if (occ && known == spn::NEE_UNKNOWN) nee_count(4);
+    nee_count(5);
+    Rng   rc = c.rng; // the estimate's twist, if any, writes the generation the stream would write itself
+    float w[2];
+    glossy_weights(mb, wol, rc, c.q, w);
+    const bool black = cblack(spn::nee_finish(P, E, mb.lambert_albedo, w, coat, cf));
+    if (known != spn::NEE_UNKNOWN && black != (known == spn::NEE_BLACK)) nee_count(6);
+    if (!(w[0] >= 0.0f && w[0] <= 1.0f && w[1] >= 0.0f && w[1] <= 1.0f)) nee_count(7);
+    if (!run) nee_count(8);
+    if (!run && known == spn::NEE_BLACK) nee_count(9);
+    if (w[0] >= 0.0f) atomicMax(&nee_chk_lds[(threadIdx.x >> 6) * 16 + 10], (unsigned long long)f2u(w[0]));
+}
+#endif
+// SP_NEE_SKIP 0: every lane with an estimate runs it (the walk still comes first).  1: lanes skip
+// only where no lane of their wave has to run it, and otherwise ride along.  2: every lane on its
+// own -- the estimate's loops end with their slowest lane and fetch per lane, so a wave that runs
+// it with fewer lanes is done sooner (bunny 1080p @ 256 spp: 1 gains 10.7 ms of 229.7, 2 gains 11.3;
+// profiles/r19/nee_order/).
+#ifndef SP_NEE_SKIP
+#define SP_NEE_SKIP 2
+#endif
 __device__ __forceinline__ rgb direct_nee(Ctx& c, const Isect& is, f3 wo)
 {
-    rgb L = mkc(0, 0, 0);
+    rgb             L    = mkc(0, 0, 0);
+    const Material& m    = c.sc.materials[is.material];
+    const bool      coat = m.kind == SP_MAT_CLEARCOAT;
+    const Material& mb   = c.sc.materials[coat ? m.base : is.material];
+    const bool      rho  = mb.kind != SP_MAT_LAMBERTIAN; // the glossy pair: Material::eval runs the estimate
     for (int li = 0; li < c.sc.n_lights; ++li) {
         const Light l = uload_light(c.sc.lights + li);
         LSample     ls;
         SP_PROF(1, ls = light_sample(c.sc, l, is.p, is.n, next2D(c.rng), c.q));
         if (ls.pdf == 0.0f || cblack(ls.L)) continue;
-        const f3 wi = ls.ray.d;
-        rgb      f;
-        SP_PROF(2, f = material_eval(c.sc, is.material, wo, wi, is.n, c.rng, c.q));
-        bool vis = false;
-        if (!cblack(f)) SP_PROF(3, vis = !occluded(c, ls.ray, ls.tmin, ls.tmax));
-        if (vis) L = cadd(L, cdivs(cscale(cmul(f, ls.L), abs_f(dot(wi, is.n))), ls.pdf));
+        const f3    wi  = ls.ray.d;
+        const Onb   o   = onb_from_v(is.n, c.q);
+        const f3    wol = to_onb(o, wo), wil = to_onb(o, wi);
+        const float cf  = coat ? 1.0f - fresnel_dielectric(wol.y, 1.0f, m.coat_ior) : 1.0f;
+        rgb         f   = mkc(0, 0, 0);
+        if (!rho) {
+            f = lambert_eval(mb); // not onesample_eval: it would inline a second copy of the estimate
+            if (coat) f = cscale(f, cf);
+        }
+        const bool walk = rho || !cblack(f);
+        bool       occ  = false;
+        if (walk) SP_PROF(3, occ = shadow_walk(c, ls.ray, ls.tmin, ls.tmax));
+        bool black = !walk;
+        if (rho) {
+            const float P     = mf_pdf(mb, wol, wil, c.q);
+            const rgb   E     = mf_eval(mb, wol, wil, c.q); // pure: evaluated where p0 > 0 is false too
+            const float A     = spn::lambert_lum(mb.lambert_albedo);
+            const int   known = spn::nee_black_known(
+                spn::estimate_bounded(wol, mb.alpha_x, mb.alpha_y, mb.microfacet_ior, mb.microfacet_r, mb.sample_visible_area != 0),
+                P, E, mb.lambert_albedo, A, coat, cf);
+            // a lane skips on its own two conditions; a vote (SP_NEE_SKIP 1) only widens `run`
+            const bool mine = !occ || known == spn::NEE_UNKNOWN;
+            bool       run  = mine || SP_NEE_SKIP == 0;
+#if SP_NEE_SKIP == 1 // taken by every lane here: inside `mine || ...` only the lanes without `mine` would vote
+            const bool some = __builtin_amdgcn_ballot_w64(mine) != 0ull;
+            run             = run || some;
+#endif
+#if SP_XP_NEE_CHECK
+            nee_check(c, mb, wol, P, E, A, coat, cf, known, occ, run);
+#endif
+            if (run) {
+                float w[2];
+                SP_PROF(2, glossy_weights(mb, wol, c.rng, c.q, w));
+                f     = spn::nee_finish(P, E, mb.lambert_albedo, w, coat, cf);
+                black = cblack(f);
+            } else {
+                // mf_rho16's effect on the stream: the reservation (the twist of a generation
+                // crossing) and 32 words on; wo.y == 0, which draws none, never gets here (the guard)
+                rng_reserve(c.rng, 32);
+                rng_skip_reserved(c.rng, 32);
+                black = known == spn::NEE_BLACK;
+            }
+        }
+        if (black) continue; // the reference traces no shadow ray: the walk is discarded, nothing counted
+        ++c.shadow;
+        ++c.rays;
+        if (!occ) L = cadd(L, cdivs(cscale(cmul(f, ls.L), abs_f(dot(wi, is.n))), ls.pdf));
     }
     return L;
 }
