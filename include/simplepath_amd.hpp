@@ -120,6 +120,10 @@ public:
         check(sp_scene_update_mesh(m_s, &u, stage_times ? &st : nullptr));
         return st;
     }
+    // Another camera (sp_scene_set_camera): a transform for this image size, from look_at() or the
+    // host's own.  On a resident scene nothing is uploaded or rebuilt; the transform then fixes the
+    // image size, and progress objects made on the scene become invalid.
+    void set_camera(const sp_camera_desc& camera) const { check(sp_scene_set_camera(m_s, &camera)); }
     sp_scene* handle() const noexcept { return m_s; }
 
     // The reference's public Scene members (base/Scene.h:90-96), as read after loading.  They are
@@ -277,6 +281,47 @@ inline Image render_image(const Integrator& integrator, unsigned num_pixel_sampl
     img.rgb.assign(static_cast<size_t>(img.width) * img.height * 3, 0.0f);
     check(sp_tiles_to_image(img.width, img.height, ids.data(), p.num_tiles, tiles.data(), img.rgb.data()));
     return img;
+}
+
+// PerspectiveCamera of the parser's perspective_camera block (origin, look_at, up, fov) for a
+// width x height film (sp_camera_look_at): the parser's bits for equal attributes.
+inline sp_camera_desc look_at(const float (&eye)[3], const float (&target)[3], const float (&up)[3], float fov_degrees,
+                              int width, int height)
+{
+    sp_camera_desc c{};
+    check(sp_camera_look_at(eye, target, up, fov_degrees, width, height, &c));
+    return c;
+}
+
+// Many views of one scene in one launch (sp_render_views): image v is render_image's after
+// scene.set_camera(cameras[v]), bit for bit; the scene's own camera is neither used nor changed.
+// Meant for many small frames (turntables, stereo pairs, cube-map faces), which one by one cannot
+// fill the device.  All views draw the same random numbers at the same pixel.  stats: totals.
+inline std::vector<Image> render_views(const Integrator& integrator, unsigned num_pixel_samples, const Scene& scene,
+                                       const std::vector<sp_camera_desc>& cameras, sp_render_stats* stats = nullptr)
+{
+    if (sp_scene_bvh_info(scene.handle(), nullptr, nullptr, nullptr) != SP_OK) scene.upload(0, 0); // not resident yet
+    int64_t n_tiles = 0;
+    check(sp_tile_count(scene.image_width, scene.image_height, &n_tiles));
+    sp_view_params p{};
+    p.struct_size       = sizeof(p);
+    p.integrator        = static_cast<int32_t>(integrator.type());
+    p.samples_per_pixel = num_pixel_samples;
+    p.num_views         = static_cast<int32_t>(cameras.size());
+    p.cameras           = cameras.data();
+    const size_t       per_view = static_cast<size_t>(n_tiles) * 64 * 3;
+    std::vector<float> tiles(cameras.size() * per_view);
+    sp_render_stats    st{};
+    check(sp_render_views_host(scene.handle(), &p, tiles.data(), &st));
+    if (stats) *stats = st;
+    std::vector<Image> out(cameras.size());
+    for (size_t v = 0; v < cameras.size(); ++v) {
+        out[v].width  = scene.image_width;
+        out[v].height = scene.image_height;
+        out[v].rgb.assign(static_cast<size_t>(out[v].width) * out[v].height * 3, 0.0f);
+        check(sp_tiles_to_image(out[v].width, out[v].height, nullptr, 0, tiles.data() + v * per_view, out[v].rgb.data()));
+    }
+    return out;
 }
 
 // Resumable render (sp_progress): render_more(n) adds n samples per pixel; after calls with n1, n2,

@@ -749,6 +749,92 @@ int  sp_scene_trace_rays(sp_scene* scene, const sp_ray_query* query, sp_ray_quer
 int  sp_scene_trace_rays_host(sp_scene* scene, int32_t mode, const sp_ray* h_rays, int64_t num_rays,
                               sp_ray_hit* h_hits, float* h_normals, uint32_t* h_occluded, sp_ray_query_stats* stats);
 
+/* ---- camera edits ---------------------------------------------------------------------------
+ * sp_camera_look_at builds the transform of a perspective camera on the host: what the parser's
+ * perspective_camera block (origin, look_at, up, fov) gives for a film of width x height, with the
+ * RSQRTSS table in effect (below) -- for equal attributes, the parser's bits.  It needs no scene and
+ * no device.  SP_ERR_ARG: a null pointer, a non-finite input, a width or height outside 1..65535,
+ * fov_degrees outside (0, 180).
+ *
+ * sp_scene_set_camera replaces the scene's camera.  Validation comes first and changes nothing, in
+ * this order: null arguments; film_width or film_height other than the scene's image size; any
+ * non-finite float -- all SP_ERR_ARG.  Then, under the scene's lock: the host camera is overwritten
+ * and fixes the image size from now on, as after sp_scene_from_desc (sp_scene_set_resolution to
+ * another size is SP_ERR_STATE; to the same size it succeeds and keeps the camera);
+ * sp_scene_get_desc shows the new camera; and every progress object made on the scene becomes
+ * invalid (SP_ERR_STATE), as after sp_scene_set_resolution.  On a resident scene only the twelve
+ * floats every launch carries by value change: nothing is uploaded, rebuilt, refitted or waited
+ * for, work already queued keeps the camera it was launched with, a moved mesh
+ * (sp_scene_update_mesh) stays moved, and a later upload with the resident options still finds the
+ * scene resident. */
+#define SP_HAS_CAMERA_EDIT 1
+
+int  sp_camera_look_at(const float eye[3], const float look_at[3], const float up[3],
+                       float fov_degrees, int32_t width, int32_t height, sp_camera_desc* out);
+int  sp_scene_set_camera(sp_scene* scene, const sp_camera_desc* camera);
+
+/* ---- many views in one launch ---------------------------------------------------------------
+ * sp_render_views renders num_views views of the resident scene -- one tile list, integrator and
+ * sample count, one camera per view -- in ONE launch of the persistent megakernel, whose queue
+ * holds num_views x num_tiles items.  For frames too small to fill the device (a 256 x 256 frame is
+ * 1024 tiles; a 256-CU device keeps up to 4096 waves of one tile each) this replaces num_views
+ * launches that each underfill it and each end in their own tail.
+ *
+ * View v is, bit for bit, the image sp_render_tiles gives for the same tiles, integrator and
+ * samples after sp_scene_set_camera(cameras[v]) (SP_PIPELINE_MEGAKERNEL, tail chunks off).  The
+ * pixel sampler and the integrator's sampler are seeded from the pixel position alone
+ * (main.cpp:67-76): nothing of the view enters.  It follows that all views draw the SAME random
+ * numbers at the same pixel -- their noise is correlated, as it is between the reference's own
+ * renders of two cameras.  Averaging views does not average that noise away as independent
+ * renders would; differences between nearby views are smoother for it.
+ *
+ * The scene's own camera is neither read nor changed, and progress objects stay valid.
+ * Output: out[((v * num_tiles + slot) * 64 + morton) * 3 + c]; pixels of clipped border tiles
+ * outside the image are 0, as for sp_render_tiles.  Stats are totals over all views: rays,
+ * shadow_rays, samples and rng_draws are the sums of the single-view calls' counts, pipeline is
+ * SP_PIPELINE_MEGAKERNEL and launches is 1.
+ *
+ * The views render in queue order: there is no tile-order probe and there are no tail chunks.
+ * Prefer sp_render_views when a view has fewer tiles than the device keeps persistent waves: on one
+ * MI355X (bunny, DirectLighting, 64 spp) 64 views of 256 x 256 took 146 ms against 397 ms for 64
+ * sp_render_tiles calls queued back to back (1483 ms with SP_PIPELINE_MEGAKERNEL).  Prefer num_views
+ * single sp_render_tiles calls for LARGE frames at sample counts where they order their queue and
+ * cut tail chunks (from 128 spp): four 1920 x 1080 views at 256 spp took 896 ms in one launch and
+ * 872 ms as four calls; at 64 spp both took 228 ms.  DESIGN.md section 27 has the figures.
+ *
+ * Ordering and locking as sp_render_tiles: the scene's lock; `stream` waits for the previous call
+ * on the scene; with stats == NULL the call only enqueues.  Host cameras and a host tile list are
+ * copied before the call returns; d_cameras and d_tile_ids must stay valid and unchanged until the
+ * work has run.
+ *
+ * Validation comes first, in this order: null scene, params or output; struct_size and reserved
+ * words; flags; num_views < 1; exactly one of cameras / d_cameras, d_cameras 16-byte aligned; a host
+ * camera with another film size or a non-finite value; the tile-list rules of sp_render_tiles;
+ * samples_per_pixel == 0 -- all SP_ERR_ARG; then a scene that is not resident, SP_ERR_STATE.  Then
+ * the integrator as for sp_render_tiles; SP_INTEGRATOR_MANDELBROT is SP_ERR_UNSUPPORTED (it has no
+ * camera), and so are more than INT32_MAX queue items (num_views x num_tiles). */
+#define SP_HAS_VIEWS 1
+
+typedef struct sp_view_params {        /* zero-initialise; struct_size = sizeof */
+    uint32_t              struct_size;       /* a size the library does not know => SP_ERR_ARG */
+    int32_t               integrator;        /* as sp_render_params */
+    uint32_t              samples_per_pixel;
+    int32_t               num_views;         /* >= 1 */
+    const sp_camera_desc* cameras;           /* HOST, num_views; film size must be the scene's; or NULL */
+    const float*          d_cameras;         /* DEVICE, num_views x 12 floats {vx, vy, vz, p}, 16-byte aligned;
+                                                exactly one of cameras / d_cameras */
+    const int32_t*        tile_ids;          /* as sp_render_params: host list, or */
+    const int32_t*        d_tile_ids;        /* device list, or both NULL = every tile; shared by all views */
+    int64_t               num_tiles;
+    void*                 stream;
+    int32_t               waves_per_simd;    /* as sp_render_params */
+    int32_t               flags;             /* SP_RENDER_PER_LANE_QUERIES or 0; anything else SP_ERR_ARG */
+    int32_t               reserved[4];       /* must be 0 */
+} sp_view_params;
+int  sp_render_views(sp_scene* scene, const sp_view_params* params, float* d_out, sp_render_stats* stats /* may be NULL */);
+/* h_out: num_views * num_tiles * 64 * 3 floats in host memory; waits for the render */
+int  sp_render_views_host(sp_scene* scene, const sp_view_params* params, float* h_out, sp_render_stats* stats);
+
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the
  * reference's images are those of the CPU it ran on.  By default scenes are built (host) and

@@ -25,7 +25,7 @@ __all__ = [
     "Scene", "TileScheduler", "ColumnMajorTileScheduler", "RenderStats", "render", "render_tiles",
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
     "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
-    "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays",
+    "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays", "camera_look_at", "render_views", "render_views_device",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -136,6 +136,13 @@ class Scene:
 
     def set_resolution(self, width: int, height: int) -> None:
         check(lib().sp_scene_set_resolution(self._h, width, height))
+
+    def set_camera(self, camera: _abi.sp_camera_desc) -> None:
+        """Replace the camera (sp_scene_set_camera): a sp_camera_desc for the scene's image size, from
+        camera_look_at() or made by hand.  On a resident scene nothing is uploaded or rebuilt -- the
+        next render sees the new camera.  The transform then fixes the image size (set_resolution to
+        another size raises SP_ERR_STATE), and progress objects made on the scene become invalid."""
+        check(lib().sp_scene_set_camera(self._h, C.byref(camera)))
 
     @staticmethod
     def _upload_params(bvh_mode=0, stackless=False, stack_max_levels=0, wide_bvh=True, env_replay=False, sah_leaf=0,
@@ -454,6 +461,80 @@ def render_tiles_device(scene: Scene, integrator, num_pixel_samples: int, tile_i
     return _stats(st)
 
 
+def camera_look_at(eye, look_at, up, fov_degrees: float, width: int, height: int) -> _abi.sp_camera_desc:
+    """The parser's perspective_camera (origin, look_at, up, fov) for a width x height film, as a
+    sp_camera_desc (sp_camera_look_at): host only, the parser's bits for equal attributes."""
+    v = [(C.c_float * 3)(*[float(x) for x in a]) for a in (eye, look_at, up)]
+    out = _abi.sp_camera_desc()
+    check(lib().sp_camera_look_at(v[0], v[1], v[2], float(fov_degrees), int(width), int(height), C.byref(out)))
+    return out
+
+
+def _view_params(integrator, spp, cameras, tile_ids, d_cameras=0, d_tile_ids=0, num_tiles=0, num_views=0, stream=None,
+                 waves_per_simd=0, per_lane_queries=False) -> tuple:
+    if isinstance(integrator, str):
+        integrator = string_to_integrator_type(integrator)
+    p = _abi.sp_view_params()
+    p.struct_size = C.sizeof(_abi.sp_view_params)
+    p.integrator = int(integrator or 0)
+    p.samples_per_pixel = int(spp)
+    keep = [None, None]
+    if cameras is not None:
+        cams = list(cameras)
+        keep[0] = (_abi.sp_camera_desc * max(len(cams), 1))(*cams)
+        p.cameras = C.cast(keep[0], C.POINTER(_abi.sp_camera_desc))
+        p.num_views = len(cams)
+    else:
+        p.d_cameras = d_cameras or None
+        p.num_views = int(num_views)
+    if tile_ids is not None:
+        keep[1] = np.ascontiguousarray(np.asarray(tile_ids), dtype=np.int32)
+        p.tile_ids = keep[1].ctypes.data_as(C.POINTER(C.c_int32))
+        p.num_tiles = keep[1].size
+    elif d_tile_ids:
+        p.d_tile_ids = C.c_void_p(d_tile_ids)
+        p.num_tiles = int(num_tiles)
+    p.stream = stream
+    p.waves_per_simd = int(waves_per_simd)
+    p.flags = PER_LANE_QUERIES if per_lane_queries else 0
+    return p, keep
+
+
+def render_views(scene: Scene, integrator, num_pixel_samples: int, cameras, tile_ids: Optional[Sequence[int]] = None,
+                 **options):
+    """Many views of the resident scene in one launch (sp_render_views_host): cameras is a sequence of
+    sp_camera_desc (camera_look_at(), scene.desc().camera, ...) for the scene's image size.  Returns
+    (radiance [V, n, 64, 3] float32 -- view v is render_tiles' image after scene.set_camera(cameras[v]),
+    bit for bit --, RenderStats with the totals over all views).  The scene's own camera is not used
+    and not changed.  All views draw the same random numbers at the same pixel.
+    options: waves_per_simd, per_lane_queries (as render_tiles)."""
+    p, keep = _view_params(integrator, num_pixel_samples, cameras, tile_ids, **options)
+    n = keep[1].size if keep[1] is not None else TileScheduler(scene.width, scene.height).get_num_tiles()
+    v = max(int(p.num_views), 0)
+    out = np.zeros((max(v * n, 1), 64, 3), dtype=np.float32)
+    st = _abi.sp_render_stats()
+    check(lib().sp_render_views_host(scene.handle, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+    return out[:v * n].reshape(v, n, 64, 3), _stats(st)
+
+
+def render_views_device(scene: Scene, integrator, num_pixel_samples: int, cameras, tile_ids, out_ptr: int,
+                        d_cameras: int = 0, num_views: int = 0, stream=None, stats=True, d_tile_ids: int = 0,
+                        num_tiles: int = 0, **options):
+    """render_views into a caller-owned device buffer of V * n * 64 * 3 floats (e.g. a torch tensor's
+    data_ptr()).  cameras: host sequence of sp_camera_desc, or None with d_cameras, a device pointer
+    to num_views x 12 floats {vx, vy, vz, p} (a [V, 12] float32 tensor; 16-byte aligned).  tile_ids as
+    render_tiles_device.  With stats=False the work is only enqueued on `stream` (returns None);
+    host cameras and a host tile list are copied before the call returns."""
+    p, keep = _view_params(integrator, num_pixel_samples, cameras, tile_ids, d_cameras, d_tile_ids, num_tiles, num_views,
+                           stream, **options)
+    if not stats:
+        check(lib().sp_render_views(scene.handle, C.byref(p), C.c_void_p(out_ptr), None))
+        return None
+    st = _abi.sp_render_stats()
+    check(lib().sp_render_views(scene.handle, C.byref(p), C.c_void_p(out_ptr), C.byref(st)))
+    return _stats(st)
+
+
 # sp_pixel_state (include/simplepath_hip.h): one pixel's carried state in a checkpoint
 PIXEL_STATE_DTYPE = np.dtype([("mt", "<u8", (312,)), ("mt_pos", "<u8"), ("draws", "<u8"), ("sum", "<f4", (3,)),
                               ("reserved", "<u4")])
@@ -477,7 +558,7 @@ class Progressive:
     """Resumable render of one tile list (sp_progress): render(n) adds n samples per pixel, and the
     image after calls with n1, n2, ... samples is render_tiles' image at n1 + n2 + ... samples, bit
     for bit.  Holds 2520 bytes of device memory per pixel slot until close().  The scene must stay
-    uploaded as it is: upload() with other options or set_resolution() invalidates the object.
+    uploaded as it is: upload() with other options, set_resolution() or set_camera() invalidates the object.
 
         prog = Progressive(scene, "direct_lighting")
         while not good_enough(img):

@@ -196,6 +196,14 @@ class sp_ray_query_stats(C.Structure):
                 ("kernel_ms", C.c_float), ("stack_depth", C.c_int32)]
 
 
+class sp_view_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32), ("samples_per_pixel", C.c_uint32),
+                ("num_views", C.c_int32), ("cameras", C.POINTER(sp_camera_desc)), ("d_cameras", C.c_void_p),
+                ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
+                ("stream", C.c_void_p), ("waves_per_simd", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -251,6 +259,12 @@ SIGNATURES = {
     "sp_scene_get_info": (C.c_int, [C.c_void_p, C.POINTER(sp_scene_info)]),
     "sp_scene_get_desc": (C.c_int, [C.c_void_p, C.POINTER(sp_scene_desc)]),
     "sp_scene_set_resolution": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "sp_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
+                                    C.c_int32, C.c_int32, C.POINTER(sp_camera_desc)]),
+    "sp_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(sp_camera_desc)]),
+    "sp_render_views": (C.c_int, [C.c_void_p, C.POINTER(sp_view_params), C.c_void_p, C.POINTER(sp_render_stats)]),
+    "sp_render_views_host": (C.c_int, [C.c_void_p, C.POINTER(sp_view_params), C.POINTER(C.c_float),
+                                       C.POINTER(sp_render_stats)]),
     "sp_tile_count": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "sp_tile_origin": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sp_device_count": (C.c_int, [C.POINTER(C.c_int32)]),

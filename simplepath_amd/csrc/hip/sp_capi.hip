@@ -533,7 +533,13 @@ struct RenderScratch {
     Events<STAGE_RING> ev_tiles;          // after each buffer's staged copy
     bool          tiles_rec[STAGE_RING] = {};
     int           stage_next = 0;
-    int           n_cu = 0;     // the device's compute units (0: not asked yet)
+    // sp_render_views: a call's host cameras, staged as the tile lists are (a ring of its own)
+    DeviceScratch d_cams;
+    PinnedScratch h_cams[STAGE_RING];
+    Events<STAGE_RING> ev_cams;
+    bool          cams_rec[STAGE_RING] = {};
+    int           cams_next = 0;
+    int           n_cu = 0;    // the device's compute units (0: not asked yet)
 };
 
 // Sizes of the resident accelerators: what the check and info calls need to read them back
@@ -567,7 +573,8 @@ struct sp_scene {
     std::mutex           mu;
     RenderScratch        scratch;
     // counts every change that invalidates a progress object made on this scene (sp_progress):
-    // a new upload (the device scene is rebuilt) and sp_scene_set_resolution
+    // a new upload (the device scene is rebuilt), sp_scene_set_resolution, sp_scene_update_mesh and
+    // sp_scene_set_camera (an object's kept tile order is the old camera's)
     uint64_t             generation = 0;
     // the resident trees were refitted (sp_scene_update_mesh): their topology is an earlier pose's, so
     // an upload with the resident options builds again instead of finding the scene resident
@@ -887,7 +894,7 @@ int sp_scene_set_resolution(sp_scene* scene, int32_t width, int32_t height)
         return fail(SP_ERR_STATE, "scene built from a descriptor: its camera transform fixes the image size");
     scene->host->image_width  = width;
     scene->host->image_height = height;
-    scene->host->rebuild_camera();
+    if (!scene->host->camera_fixed) scene->host->rebuild_camera(); // (a given transform has no attributes to rebuild from)
     ++scene->generation;
     fill_desc(scene);
     if (scene->device >= 0) {
@@ -895,6 +902,59 @@ int sp_scene_set_resolution(sp_scene* scene, int32_t width, int32_t height)
         scene->dev.height = height;
         scene->dev.camera = scene->host->camera;
     }
+    return SP_OK;
+}
+
+// ---- camera edits (SP_HAS_CAMERA_EDIT) ------------------------------------------------------------
+
+static bool camera_finite(const sp_camera_desc& c)
+{
+    const sp_affine& t = c.transform;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(t.vx[k]) || !std::isfinite(t.vy[k]) || !std::isfinite(t.vz[k]) || !std::isfinite(t.p[k])) return false;
+    return true;
+}
+
+int sp_camera_look_at(const float eye[3], const float look_at[3], const float up[3], float fov_degrees, int32_t width,
+                      int32_t height, sp_camera_desc* out)
+{
+    if (!eye || !look_at || !up || !out) return fail(SP_ERR_ARG, "null argument");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(eye[k]) || !std::isfinite(look_at[k]) || !std::isfinite(up[k]))
+            return fail(SP_ERR_ARG, "sp_camera_look_at: non-finite input");
+    if (!std::isfinite(fov_degrees)) return fail(SP_ERR_ARG, "sp_camera_look_at: non-finite input");
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return fail(SP_ERR_ARG, "sp_camera_look_at: bad film size");
+    if (!(fov_degrees > 0.0f && fov_degrees < 180.0f)) return fail(SP_ERR_ARG, "sp_camera_look_at: fov_degrees outside (0, 180)");
+    const spm::aff a = sph::perspective_camera_transform(spm::mk(eye[0], eye[1], eye[2]), spm::mk(look_at[0], look_at[1], look_at[2]),
+                                                         spm::mk(up[0], up[1], up[2]), fov_degrees, width, height);
+    auto put = [](float* o, spm::f3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+    *out = sp_camera_desc{};
+    put(out->transform.vx, a.vx);
+    put(out->transform.vy, a.vy);
+    put(out->transform.vz, a.vz);
+    put(out->transform.p, a.p);
+    out->film_width  = width;
+    out->film_height = height;
+    return SP_OK;
+}
+
+// The device side of the camera is the twelve floats of spd::Scene::camera, which every launch
+// carries by value (MegaSetup::sc_run and its like): replacing them touches no device memory, and
+// launches already queued keep their copy.  Nothing in RenderScratch depends on the camera; a
+// progress object's kept tile order does, and the generation bump retires those objects.
+int sp_scene_set_camera(sp_scene* scene, const sp_camera_desc* camera)
+{
+    if (!scene || !camera) return fail(SP_ERR_ARG, "null argument");
+    if (camera->film_width != scene->host->image_width || camera->film_height != scene->host->image_height)
+        return fail(SP_ERR_ARG, "sp_scene_set_camera: the film size is not the scene's image size");
+    if (!camera_finite(*camera)) return fail(SP_ERR_ARG, "sp_scene_set_camera: non-finite transform");
+    std::lock_guard<std::mutex> lock(scene->mu);
+    scene->host->camera       = from_desc(camera->transform);
+    scene->host->has_camera   = true;
+    scene->host->camera_fixed = true;
+    fill_desc(scene);
+    ++scene->generation;
+    if (scene->device >= 0) scene->dev.camera = scene->host->camera;
     return SP_OK;
 }
 
@@ -1228,6 +1288,7 @@ static int create_render_handles(sp_scene* s)
     SP_HIP(hipEventCreate(&r.ev1[0]));
     SP_HIP(hipEventCreateWithFlags(&r.ev_done[0], hipEventDisableTiming));
     for (hipEvent_t& e : r.ev_tiles.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t& e : r.ev_cams.h) SP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SP_OK;
 }
 
@@ -1563,22 +1624,23 @@ static int validate_render(const sp_scene* s, const sp_render_params* p, const f
 // A host tile list goes to the device through the next pinned buffer of the ring, so the caller's
 // array is free once the call returns; the host waits only if that buffer's copy (STAGE_RING calls
 // back) has not run
-static int stage_tile_list(RenderCall& c)
+static int stage_ids(sp_scene* s, const int32_t* ids, int64_t n, hipStream_t stream, const int32_t*& d_ids)
 {
-    RenderScratch& r     = c.s->scratch;
-    const size_t   bytes = (size_t)c.tiles.n * sizeof(int32_t);
+    RenderScratch& r     = s->scratch;
+    const size_t   bytes = (size_t)n * sizeof(int32_t);
     SP_HIP(r.d_tiles.reserve(bytes));
     const int k  = r.stage_next;
     r.stage_next = (k + 1) % RenderScratch::STAGE_RING;
     if (r.tiles_rec[k]) SP_HIP(hipEventSynchronize(r.ev_tiles[k]));
     SP_HIP(r.h_tiles[k].reserve(bytes));
-    std::memcpy(r.h_tiles[k].ptr, c.p->tile_ids, bytes);
-    SP_HIP(hipMemcpyAsync(r.d_tiles.ptr, r.h_tiles[k].ptr, bytes, hipMemcpyHostToDevice, c.stream));
-    SP_HIP(hipEventRecord(r.ev_tiles[k], c.stream));
+    std::memcpy(r.h_tiles[k].ptr, ids, bytes);
+    SP_HIP(hipMemcpyAsync(r.d_tiles.ptr, r.h_tiles[k].ptr, bytes, hipMemcpyHostToDevice, stream));
+    SP_HIP(hipEventRecord(r.ev_tiles[k], stream));
     r.tiles_rec[k] = true;
-    c.d_ids        = r.d_tiles.as<int32_t>();
+    d_ids          = r.d_tiles.as<int32_t>();
     return SP_OK;
 }
+static int stage_tile_list(RenderCall& c) { return stage_ids(c.s, c.p->tile_ids, c.tiles.n, c.stream, c.d_ids); }
 
 // Which pipeline (sp_plan.hpp plan_render), and the sample chunks' buffers when it is theirs
 static int plan_call(RenderCall& c)
@@ -2074,6 +2136,116 @@ int sp_render_tiles_host(sp_scene* s, const sp_render_params* p, float* h_out, s
     SP_HIP(hipSetDevice(s->device));
     const int64_t n = tile_list(s, p->tile_ids, p->d_tile_ids, p->num_tiles).n; // what the render writes
     return render_to_host(n, h_out, [&](float* d) { return sp_render_tiles(s, p, d, stats); });
+}
+
+// ---- many views in one launch (SP_HAS_VIEWS) -------------------------------------------------------
+
+// Arguments, in the order their errors are promised; changes no state.  The tile count is the host
+// scene's (the resident one's is equal), so the list rules hold before any upload.
+static int validate_views(const sp_scene* s, const sp_view_params* p, const float* out, TileList& tiles)
+{
+    if (!s || !p || !out) return fail(SP_ERR_ARG, "null argument");
+    if (p->struct_size != sizeof(sp_view_params)) return fail(SP_ERR_ARG, "sp_view_params.struct_size is not this library's");
+    for (int32_t r : p->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_view_params.reserved must be 0");
+    if ((p->flags & ~SP_RENDER_PER_LANE_QUERIES) != 0) return fail(SP_ERR_ARG, "unknown flags");
+    if (p->num_views < 1) return fail(SP_ERR_ARG, "num_views < 1");
+    if ((p->cameras != nullptr) == (p->d_cameras != nullptr)) return fail(SP_ERR_ARG, "give cameras (host) or d_cameras (device), one of them");
+    if (reinterpret_cast<uintptr_t>(p->d_cameras) % 16 != 0) return fail(SP_ERR_ARG, "d_cameras must be 16-byte aligned");
+    if (p->cameras)
+        for (int32_t v = 0; v < p->num_views; ++v) {
+            if (p->cameras[v].film_width != s->host->image_width || p->cameras[v].film_height != s->host->image_height)
+                return fail(SP_ERR_ARG, "a view's film size is not the scene's image size");
+            if (!camera_finite(p->cameras[v])) return fail(SP_ERR_ARG, "a view's transform is not finite");
+        }
+    if (p->tile_ids && p->d_tile_ids) return fail(SP_ERR_ARG, "give tile_ids (host) or d_tile_ids (device), not both");
+    sp_tile_count(s->host->image_width, s->host->image_height, &tiles.total);
+    tiles.listed = p->tile_ids || p->d_tile_ids;
+    tiles.n      = tiles.listed ? p->num_tiles : tiles.total;
+    if (int rc = check_tile_list(tiles, p->tile_ids)) return rc;
+    if (p->samples_per_pixel == 0) return fail(SP_ERR_ARG, "samples_per_pixel must be > 0");
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_render_views");
+    return SP_OK;
+}
+
+// Host cameras to the device through a ring of pinned buffers of their own (stage_ids is the pattern)
+static int stage_cameras(sp_scene* s, const sp_camera_desc* cams, int32_t n, hipStream_t stream, const spd::aff*& d_cams)
+{
+    RenderScratch& r     = s->scratch;
+    const size_t   bytes = (size_t)n * sizeof(spd::aff);
+    static_assert(sizeof(spd::aff) == 48 && sizeof(sp_affine) == 48, "twelve floats per camera");
+    SP_HIP(r.d_cams.reserve(bytes));
+    const int k = r.cams_next;
+    r.cams_next = (k + 1) % RenderScratch::STAGE_RING;
+    if (r.cams_rec[k]) SP_HIP(hipEventSynchronize(r.ev_cams[k]));
+    SP_HIP(r.h_cams[k].reserve(bytes));
+    for (int32_t v = 0; v < n; ++v) std::memcpy(r.h_cams[k].as<char>() + (size_t)v * 48, &cams[v].transform, 48);
+    SP_HIP(hipMemcpyAsync(r.d_cams.ptr, r.h_cams[k].ptr, bytes, hipMemcpyHostToDevice, stream));
+    SP_HIP(hipEventRecord(r.ev_cams[k], stream));
+    r.cams_rec[k] = true;
+    d_cams        = r.d_cams.as<spd::aff>();
+    return SP_OK;
+}
+
+static int render_views_impl(sp_scene* s, const sp_view_params* p, float* d_out, sp_render_stats* stats)
+{
+    TileList tiles;
+    if (int rc = validate_views(s, p, d_out, tiles)) return rc;
+    int32_t integ = 0;
+    if (int rc = resolve_integrator(s, p->integrator, p->waves_per_simd, integ)) return rc;
+    if (integ == SP_INTEGRATOR_MANDELBROT) return fail(SP_ERR_UNSUPPORTED, "sp_render_views: Mandelbrot has no camera");
+    if (tiles.n > 0 && (int64_t)p->num_views > (int64_t)INT32_MAX / tiles.n)
+        return fail(SP_ERR_UNSUPPORTED, "sp_render_views: more than INT32_MAX queue items (num_views x num_tiles)");
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch&    r      = s->scratch;
+    const hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    if (stats) *stats = sp_render_stats{};
+    if (tiles.n == 0) return SP_OK;
+    // the previous call on this scene may have used another stream (render_tiles_impl)
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    const int32_t* d_ids = p->d_tile_ids;
+    if (p->tile_ids)
+        if (int rc = stage_ids(s, p->tile_ids, tiles.n, stream, d_ids)) return rc;
+    spd::ViewArgs vw{};
+    vw.cameras        = reinterpret_cast<const spd::aff*>(p->d_cameras);
+    vw.tiles_per_view = tiles.n;
+    if (p->cameras)
+        if (int rc = stage_cameras(s, p->cameras, p->num_views, stream, vw.cameras)) return rc;
+    if (int rc = device_cus(s)) return rc;
+    MegaSetup m;
+    if (int rc = mega_setup(s, spd::MegaFamily::Views, integ, p->waves_per_simd, d_ids, (int64_t)p->num_views * tiles.n, m)) return rc;
+    SP_HIP(hipMemsetAsync(r.counters.ptr, 0, 8 * sizeof(unsigned long long), stream));
+    SP_HIP(hipMemsetAsync(r.tile_counter.ptr, 0, sizeof(int32_t), stream));
+    m.sc_run.merge_queries = (p->flags & SP_RENDER_PER_LANE_QUERIES) ? 0 : 1;
+    m.a.out = d_out;
+    m.a.spp = p->samples_per_pixel;
+    SP_HIP(hipEventRecord(r.ev0, stream));
+    SP_HIP(spd::launch_mega(m.family, m.sc_run, m.a, nullptr, nullptr, m.integ, m.variant, m.blocks, m.lds_bytes, stream, &vw));
+    if (int rc = end_call(s, stream)) return rc;
+    if (!stats) return SP_OK; // stream order: only enqueued
+    unsigned long long ctr[8];
+    return read_stats(s, SP_PIPELINE_MEGAKERNEL, 1, stats, ctr);
+}
+
+int sp_render_views(sp_scene* s, const sp_view_params* p, float* d_out, sp_render_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    try {
+        return render_views_impl(s, p, d_out, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_render_views failed: ") + e.what());
+    }
+}
+
+int sp_render_views_host(sp_scene* s, const sp_view_params* p, float* h_out, sp_render_stats* stats)
+{
+    TileList tiles;
+    if (int rc = validate_views(s, p, h_out, tiles)) return rc; // (before any device buffer is made)
+    if (tiles.n > 0 && (int64_t)p->num_views > (int64_t)INT32_MAX / tiles.n)
+        return fail(SP_ERR_UNSUPPORTED, "sp_render_views: more than INT32_MAX queue items (num_views x num_tiles)");
+    SP_HIP(hipSetDevice(s->device));
+    return render_to_host((int64_t)p->num_views * tiles.n, h_out, [&](float* d) { return sp_render_views(s, p, d, stats); });
 }
 
 // ---- progressive renders (sp_progress) ---------------------------------------------------------

@@ -259,6 +259,16 @@ struct AdaptArgs {
     uint32_t       cap;      // max_samples
 };
 
+// Many views in one launch (sp_views_kernel, sp_mega.hpp; sp_render_views): the queue holds
+// num_views * tiles_per_view items (RenderArgs::num_tiles is that product, so the grid is sized from
+// all views' work); item s is tile slot s % tiles_per_view seen through cameras[s / tiles_per_view]
+// and writes output slot s.  A third kernel argument of the views kernels only, so RenderArgs and
+// the existing kernels stay as they are; Scene::camera is not read by them.
+struct ViewArgs {
+    const aff* cameras;        // [num_views] {vx, vy, vz, p}
+    int64_t    tiles_per_view; // > 0; num_views * tiles_per_view <= INT32_MAX (the queue head)
+};
+
 // The selection of a round (sp_adaptive.hip adapt_error_kernel): which lanes of a slot are pixels,
 // and the rule's parameters.  flag == nullptr: tile errors only.
 struct SelectArgs {

@@ -9,8 +9,9 @@
 namespace spd {
 
 // The persistent megakernel's families: a one-shot render (sp_render_kernel), a call on a progress
-// object (sp_resume_kernel: needs ResumeArgs) and on an adaptive one (sp_adapt_kernel: AdaptArgs too).
-enum class MegaFamily { Render, Resume, Adapt };
+// object (sp_resume_kernel: needs ResumeArgs) and on an adaptive one (sp_adapt_kernel: AdaptArgs too),
+// many views of the scene in one launch (sp_views_kernel: needs ViewArgs; no Mandelbrot).
+enum class MegaFamily { Render, Resume, Adapt, Views };
 
 // A family's kernel for an integrator.  variant = requested waves per SIMD of its
 // __launch_bounds__ (DirectLighting 1..4, IterativeRRNEE 2..4; the others have one each).
@@ -24,9 +25,9 @@ const void* tail_kernel(int variant);
 int    kernel_blocks_per_cu(const void* kernel, size_t lds_bytes);
 size_t kernel_static_lds(const void* kernel);
 
-// res / ad: what the family needs (nullptr for the others)
+// res / ad / vw: what the family needs (nullptr for the others)
 hipError_t launch_mega(MegaFamily family, const Scene& sc, const RenderArgs& args, const ResumeArgs* res, const AdaptArgs* ad,
-                       int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream);
+                       int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream, const ViewArgs* vw = nullptr);
 hipError_t launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream);
 
 // tile order: the one-sample probe of an integrator's megakernel, then the queue order

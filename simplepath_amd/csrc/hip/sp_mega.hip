@@ -22,14 +22,22 @@ const void* mega_kernel(MegaFamily family, int integ, int variant)
     switch (family) {
     case MegaFamily::Resume: return reinterpret_cast<const void*>(select_resume(integ, variant));
     case MegaFamily::Adapt: return reinterpret_cast<const void*>(select_adapt(integ, variant));
+    case MegaFamily::Views: return reinterpret_cast<const void*>(select_views(integ, variant));
     default: return reinterpret_cast<const void*>(select_kernel(integ, variant));
     }
 }
 
 hipError_t launch_mega(MegaFamily family, const Scene& sc, const RenderArgs& args, const ResumeArgs* res, const AdaptArgs* ad,
-                       int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream)
+                       int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream, const ViewArgs* vw)
 {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
+    if (family == MegaFamily::Views) {
+        const ViewsFn k = select_views(integ, variant);
+        if (!vw || !vw->cameras || vw->tiles_per_view <= 0) return hipErrorInvalidValue;
+        if (!k) return hipErrorInvalidDeviceFunction; // (an integrator without a views kernel: no fall-back)
+        hipLaunchKernelGGL(k, grid, block, lds_bytes, stream, sc, args, *vw);
+        return hipGetLastError();
+    }
     if ((family != MegaFamily::Render && !res) || (family == MegaFamily::Adapt && !ad)) return hipErrorInvalidValue;
     switch (family) {
     case MegaFamily::Resume: hipLaunchKernelGGL(select_resume(integ, variant), grid, block, lds_bytes, stream, sc, args, *res); break;

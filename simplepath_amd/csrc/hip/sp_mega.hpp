@@ -380,10 +380,16 @@ __device__ __forceinline__ void noise_push(float& mean, float& m2, rgb L, uint32
 // (its length read from the device count, so a round needs no host wait), a tile's first sample is
 // its own count done[slot], it gets min(step, cap - done) samples, and every sample is pushed into
 // the pixel's running statistics, which live in two registers across the sample loop.
-template <int INTEG, bool PROBE, int TAIL = 0, bool RESUME = false, bool ADAPT = false>
+// VIEWS: many views of the scene in one launch (sp_views_kernel; ViewArgs, sp_device.hpp): queue
+// item s is tile slot s % tiles_per_view through camera s / tiles_per_view, written to output slot s,
+// in queue order.  The item's camera is fetched once, by scalar loads through a wave-uniform index,
+// and is dead at the item's end; sc.camera is not read.
+template <int INTEG, bool PROBE, int TAIL = 0, bool RESUME = false, bool ADAPT = false, bool VIEWS = false>
 __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderArgs& args, const ResumeArgs* res = nullptr,
-                                                  const AdaptArgs* ad = nullptr)
+                                                  const AdaptArgs* ad = nullptr, const ViewArgs* vw = nullptr)
 {
+    static_assert(!VIEWS || (!PROBE && TAIL == 0 && !RESUME && INTEG != SP_INTEGRATOR_MANDELBROT),
+                  "views run the plain megakernel form of an integrator that has a camera");
     static_assert(!RESUME || (!PROBE && TAIL == 0), "progressive calls run the plain megakernel form");
     static_assert(!ADAPT || RESUME, "adaptive calls are progressive calls");
     extern __shared__ uint32_t lds[];
@@ -467,9 +473,19 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
         }
         int64_t slot;
         if constexpr (ADAPT) slot = __builtin_amdgcn_readfirstlane(ad->active[item]);
+        else if constexpr (VIEWS) slot = item;
         else slot = PROBE ? item * args.probe_step : (args.order ? args.order[item] : item);
         const uint64_t t_start = (PROBE || args.tile_diag) ? __builtin_amdgcn_s_memrealtime() : 0;
-        const int32_t  tile   = args.tile_ids ? args.tile_ids[slot] : (int32_t)slot;
+        int64_t list_slot = slot; // the tile's position in the list
+        aff     view_cam{};       // VIEWS: this item's camera, in SGPRs until the item ends
+        if constexpr (VIEWS) {    // (the queue head is an int32, so the whole queue is: sp_render_views refuses more)
+            const uint32_t it  = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
+            const uint32_t tpv = (uint32_t)vw->tiles_per_view;
+            list_slot          = (int64_t)(it % tpv);
+            view_cam           = uload_aff(vw->cameras + it / tpv);
+        }
+        const aff&     cam    = VIEWS ? view_cam : sc.camera;
+        const int32_t  tile   = args.tile_ids ? args.tile_ids[list_slot] : (int32_t)list_slot;
         const uint32_t px     = (uint32_t)((tile % args.tiles_x) * 8) + dx;
         const uint32_t py     = (uint32_t)((tile / args.tiles_x) * 8) + dy;
         // unsigned compares: a negative tile id (device lists are not checked) lands outside
@@ -522,8 +538,8 @@ __device__ __forceinline__ void render_tiles_body(const Scene& sc, const RenderA
                 const float fy = (float)(int)py + sy;
                 // PerspectiveCamera::generate_ray_impl (Cameras/Camera.h:119)
                 Ray ray;
-                ray.o = sc.camera.p;
-                ray.d = normalize(add(add(scale(fx, sc.camera.vx), scale(fy, sc.camera.vy)), sc.camera.vz), q);
+                ray.o = cam.p;
+                ray.d = normalize(add(add(scale(fx, cam.vx), scale(fy, cam.vy)), cam.vz), q);
                 if constexpr (ADAPT) {
                     rgb L;
                     if constexpr (INTEG == SP_INTEGRATOR_MANDELBROT) L = integrate_mandelbrot(fx, fy, sc.width, sc.height);
@@ -614,6 +630,11 @@ __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_adapt_kernel(Sc
 {
     render_tiles_body<INTEG, false, 0, true, true>(sc, args, &res, &ad);
 }
+template <int INTEG, int MINW>
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_views_kernel(Scene sc, RenderArgs args, ViewArgs vw)
+{
+    render_tiles_body<INTEG, false, 0, false, false, true>(sc, args, nullptr, nullptr, &vw);
+}
 template <int MINW, bool REPLAY>
 __global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, MINW) sp_tail_kernel(Scene sc, RenderArgs args)
 {
@@ -651,5 +672,11 @@ AdaptFn    adapt_mandelbrot();
 AdaptFn    adapt_rrnee(int waves);
 AdaptFn    adapt_path(int integ);
 AdaptFn    select_adapt(int integ, int variant);
+// many views in one launch (sp_mega_views*.hip, the same split; no Mandelbrot: it has no camera)
+using ViewsFn = void (*)(Scene, RenderArgs, ViewArgs);
+ViewsFn    views_direct(int variant);
+ViewsFn    views_rrnee(int waves);
+ViewsFn    views_path(int integ);
+ViewsFn    select_views(int integ, int variant); // nullptr: Mandelbrot
 
 } // namespace spd

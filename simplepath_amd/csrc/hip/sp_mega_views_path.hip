@@ -1,0 +1,16 @@
+// sp_mega_views_path.hip -- many views in one launch, BruteForce / BruteForceIterative(RR) / Whitted:
+// sp_views_kernel with the default sampler options, as their one-shot kernels
+// (sp_mega_recursive.hip, sp_mega_iterative.hip).
+#include "sp_mega.hpp"
+
+namespace spd {
+ViewsFn views_path(int integ)
+{
+    switch (integ) {
+    case SP_INTEGRATOR_WHITTED: return sp_views_kernel<SP_INTEGRATOR_WHITTED, 2>;
+    case SP_INTEGRATOR_BRUTE_FORCE_ITERATIVE: return sp_views_kernel<SP_INTEGRATOR_BRUTE_FORCE_ITERATIVE, 2>;
+    case SP_INTEGRATOR_BRUTE_FORCE_ITERATIVE_RR: return sp_views_kernel<SP_INTEGRATOR_BRUTE_FORCE_ITERATIVE_RR, 2>;
+    default: return sp_views_kernel<SP_INTEGRATOR_BRUTE_FORCE, 2>;
+    }
+}
+} // namespace spd
