@@ -835,6 +835,85 @@ int  sp_render_views(sp_scene* scene, const sp_view_params* params, float* d_out
 /* h_out: num_views * num_tiles * 64 * 3 floats in host memory; waits for the render */
 int  sp_render_views_host(sp_scene* scene, const sp_view_params* params, float* h_out, sp_render_stats* stats);
 
+/* ---- radiance queries -----------------------------------------------------------------------
+ * sp_scene_radiance_rays runs an integrator along the caller's own rays on the resident scene: the
+ * reference's Integrator::integrate(ray, scene, arena, sampler, pixel_coords)
+ * (Integrators/Integrator.h:37), of which its pinhole camera is only one client (main.cpp:94-101).
+ * A fisheye or equirectangular probe, an orthographic or thin-lens camera, bake points on a surface
+ * or rays from a learned camera model get light here, where sp_scene_trace_rays gives hits.
+ *
+ * What record i means.  The library makes IncoherentSampler::create_new_sequence(Seed{seed}) -- the
+ * mt19937_64 a render seeds per pixel, with `seed` taken as given --, calls the integrator
+ * samples_per_ray times on the ray (o, d) with that one sampler running on, as main.cpp:94-101 does
+ * for one pixel, sums the results in call order, divides by (float)samples_per_ray and writes
+ * d_out[i * 3 + c].
+ *
+ * Direction: d is used as given.  The reference's cameras hand integrate a direction normalised by
+ * sp::rsqrt and the materials take -d as wo: the caller normalises.
+ * Position independence: a record's result does not depend on its position in the buffer or on its
+ * neighbours.
+ * Seeds: equal seeds on different rays give correlated noise.  main.cpp's seed for pixel (x, y) is
+ * ((x << 16) | y) ^ 0xb0ae9d99.
+ * Rays no integrator makes: a NaN or infinite component of o or d, or a zero d, gives radiance +0
+ * without a walk or a draw; such a record counts no rays, samples or draws.  `reserved` of a
+ * record is not checked (it lives in device memory).
+ * Geometry and lights are a render's: unlike a ray query, lights are hit and sampled, because
+ * integrate does that.  Equal-distance ties resolve as in a render of this residency.
+ * Scene state: a query sees what is resident -- after sp_scene_update_mesh, the moved mesh.  It does
+ * not read the camera: sp_scene_set_camera changes no bit of it.  It leaves progress objects valid
+ * and keeps nothing on the scene beyond the scratch a render uses.
+ *
+ * One launch of a persistent kernel serves all rays: its waves take 64 consecutive records at a
+ * time from a queue, because rays cost very differently.  That is the right call for many rays
+ * (from a few thousand: one item per wave the device keeps resident) whatever their order or mix.
+ * It is not the right call for a pinhole frame -- sp_render_tiles orders its tiles by cost, cuts
+ * tail chunks and makes the camera rays itself -- nor for a handful of rays at many samples, which
+ * keep one wave busy while the device idles: split such rays into records of fewer samples with
+ * different seeds and average.  Records that are neighbours in the buffer share a wave: rays that
+ * start and head alike (tile or Morton order of a probe) walk the tree together and run faster than
+ * the same rays in random order.  On one MI355X (bunny at 1920 x 1080, DirectLighting, one ray per
+ * pixel) two million rays in the render's tile order took about 2.4 ms at 1 sample and 65 ms at 64,
+ * level with sp_render_tiles' megakernel for the same integrate calls; in row order 9-10 % more from
+ * 16 samples (IterativeRRNEE: 2 %).  At one sample per ray about half of that is the fixed cost per record, mostly the
+ * 312-word seeding of its generator.  DESIGN.md section 28 has the figures.
+ *
+ * Validation comes first and changes nothing, in this order: null scene, query or output;
+ * struct_size and reserved words; flags other than SP_RENDER_PER_LANE_QUERIES; num_rays < 0; d_rays
+ * missing when num_rays > 0, or not 16-byte aligned; samples_per_ray == 0; waves_per_simd out of the
+ * integrator's range -- all SP_ERR_ARG; then a scene that is not resident, SP_ERR_STATE.  Then the
+ * integrator resolves as for sp_render_tiles; SP_INTEGRATOR_MANDELBROT is SP_ERR_UNSUPPORTED (it
+ * has no ray), and so are more than INT32_MAX queue items of 64 rays and a BVH too deep for the LDS
+ * stacks, as for a render.  num_rays == 0 succeeds and launches nothing.
+ *
+ * Ordering and locking as sp_render_tiles: the scene's lock; `stream` waits for the previous call
+ * on the scene; with stats == NULL the call only enqueues.  d_rays and d_out must stay valid until
+ * the work has run.  Stats: rays, shadow_rays, samples and rng_draws are totals over the records,
+ * pipeline is SP_PIPELINE_MEGAKERNEL and launches is 1.
+ *
+ * sp_scene_radiance_rays_host takes host arrays (query->d_rays is ignored; no alignment is asked of
+ * h_rays): it allocates device buffers, copies, runs, waits and copies back. */
+#define SP_HAS_RADIANCE_QUERY 1
+
+typedef struct sp_radiance_ray { float o[3]; uint32_t seed; float d[3]; uint32_t reserved; } sp_radiance_ray; /* 32 bytes */
+
+typedef struct sp_radiance_query {      /* zero-initialise; struct_size = sizeof */
+    uint32_t               struct_size;       /* a size the library does not know => SP_ERR_ARG */
+    int32_t                integrator;        /* as sp_render_params.integrator */
+    const sp_radiance_ray* d_rays;            /* DEVICE, num_rays records, 16-byte aligned */
+    int64_t                num_rays;
+    uint32_t               samples_per_ray;   /* >= 1 */
+    int32_t                waves_per_simd;    /* as sp_render_params */
+    int32_t                flags;             /* SP_RENDER_PER_LANE_QUERIES or 0; anything else SP_ERR_ARG */
+    int32_t                reserved0;         /* must be 0 */
+    void*                  stream;            /* hipStream_t, NULL = default stream */
+    int32_t                reserved[4];       /* must be 0 */
+} sp_radiance_query;
+/* d_out: DEVICE, num_rays * 3 floats */
+int  sp_scene_radiance_rays(sp_scene* scene, const sp_radiance_query* query, float* d_out, sp_render_stats* stats /* may be NULL */);
+/* h_rays, h_out: host arrays of num_rays records and num_rays * 3 floats; waits for the work */
+int  sp_scene_radiance_rays_host(sp_scene* scene, const sp_radiance_query* query /* d_rays ignored */,
+                                 const sp_radiance_ray* h_rays, float* h_out, sp_render_stats* stats /* may be NULL */);
+
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the
  * reference's images are those of the CPU it ran on.  By default scenes are built (host) and

@@ -26,6 +26,7 @@ __all__ = [
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
     "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
     "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays", "camera_look_at", "render_views", "render_views_device",
+    "RADIANCE_RAY_DTYPE", "make_radiance_rays", "pixel_seed",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -56,6 +57,30 @@ def make_rays(origins, directions, tmin=K_RAY_EPSILON, tmax=K_INFINITE) -> np.nd
     rays["o"], rays["d"] = o, d
     rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (o.shape[0],))
     rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (o.shape[0],))
+    return rays
+
+
+# sp_radiance_ray (include/simplepath_hip.h): the record of a radiance query, 32 bytes
+RADIANCE_RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("seed", "<u4"), ("d", "<f4", (3,)), ("reserved", "<u4")])
+
+
+def pixel_seed(x, y):
+    """main.cpp's integrator-sampler seed of pixel (x, y): ((x << 16) | y) ^ 0xb0ae9d99 as uint32
+    (scalars give an int, arrays a uint32 array)."""
+    s = ((np.asarray(x).astype(np.uint32) << np.uint32(16)) | np.asarray(y).astype(np.uint32)) ^ np.uint32(0xb0ae9d99)
+    return int(s) if s.ndim == 0 else s
+
+
+def make_radiance_rays(origins, directions, seeds) -> np.ndarray:
+    """RADIANCE_RAY_DTYPE records [n] from origins, directions [n, 3] and sampler seeds (a scalar or
+    [n], taken modulo 2^32).  Directions are used as given: normalise them."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions must both be [n, 3]")
+    rays = np.zeros(o.shape[0], dtype=RADIANCE_RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["seed"] = np.broadcast_to((np.asarray(seeds).astype(np.int64) & 0xffffffff).astype(np.uint32), (o.shape[0],))
     return rays
 
 
@@ -333,6 +358,54 @@ class Scene:
         st.struct_size = C.sizeof(_abi.sp_ray_query_stats)
         check(lib().sp_scene_trace_rays(self._h, C.byref(q), C.byref(st)))
         return {k: getattr(st, k) for k, _ in _abi.sp_ray_query_stats._fields_ if k != "struct_size"}
+
+    @staticmethod
+    def _radiance_query(integrator, samples, n, rays_ptr=0, stream=None, waves_per_simd=0, per_lane_queries=False):
+        if isinstance(integrator, str):
+            integrator = string_to_integrator_type(integrator)
+        q = _abi.sp_radiance_query()
+        q.struct_size = C.sizeof(_abi.sp_radiance_query)
+        q.integrator = int(integrator or 0)
+        q.d_rays = rays_ptr or None
+        q.num_rays = int(n)
+        q.samples_per_ray = int(samples)
+        q.waves_per_simd = int(waves_per_simd)
+        q.flags = PER_LANE_QUERIES if per_lane_queries else 0
+        q.stream = stream
+        return q
+
+    def radiance(self, origins, directions, seeds, integrator=None, samples: int = 1, **options):
+        """Radiance along the caller's own rays on the resident scene, from host arrays
+        (sp_scene_radiance_rays_host): the reference's Integrator::integrate for ray i = (origins[i],
+        directions[i]) with a sampler seeded seeds[i], called `samples` times with the sampler running
+        on, summed in call order and divided -- what main.cpp does for one pixel, whose seed is
+        pixel_seed(x, y).  Directions are used as given (normalise them); lights are hit and sampled
+        as in a render; a non-finite ray or a zero direction gives 0.  integrator None: the scene's.
+        Returns ([n, 3] float32, RenderStats with the totals).  options: waves_per_simd,
+        per_lane_queries (as render_tiles)."""
+        rays = make_radiance_rays(origins, directions, seeds)
+        n = rays.shape[0]
+        q = self._radiance_query(integrator, samples, n, **options)
+        out = np.zeros((max(n, 1), 3), dtype=np.float32)
+        st = _abi.sp_render_stats()
+        check(lib().sp_scene_radiance_rays_host(self._h, C.byref(q), C.c_void_p(rays.ctypes.data) if n else None,
+                                                C.c_void_p(out.ctypes.data), C.byref(st)))
+        return out[:n], _stats(st)
+
+    def radiance_device(self, rays_ptr: int, n: int, out_ptr: int, integrator=None, samples: int = 1, stream=None,
+                        stats: bool = True, **options):
+        """radiance on device buffers (sp_scene_radiance_rays), e.g. torch tensors' data_ptr():
+        rays_ptr n RADIANCE_RAY_DTYPE records (an [n, 8] float32 tensor: origin, seed, direction, 0,
+        with columns 3 and 7 written through an int32 view; 16-byte aligned, as any torch allocation
+        is), out_ptr n * 3 floats.  With stats=False the query is only enqueued on `stream` (returns
+        None); with stats=True the call waits and returns RenderStats."""
+        q = self._radiance_query(integrator, samples, n, rays_ptr, stream, **options)
+        if not stats:
+            check(lib().sp_scene_radiance_rays(self._h, C.byref(q), C.c_void_p(out_ptr), None))
+            return None
+        st = _abi.sp_render_stats()
+        check(lib().sp_scene_radiance_rays(self._h, C.byref(q), C.c_void_p(out_ptr), C.byref(st)))
+        return _stats(st)
 
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()

@@ -204,6 +204,16 @@ class sp_view_params(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class sp_radiance_ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("seed", C.c_uint32), ("d", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class sp_radiance_query(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32), ("d_rays", C.c_void_p), ("num_rays", C.c_int64),
+                ("samples_per_ray", C.c_uint32), ("waves_per_simd", C.c_int32), ("flags", C.c_int32),
+                ("reserved0", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -282,6 +292,9 @@ SIGNATURES = {
     "sp_scene_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_ray_query), C.POINTER(sp_ray_query_stats)]),
     "sp_scene_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(sp_ray_query_stats)]),
+    "sp_scene_radiance_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_radiance_query), C.c_void_p, C.POINTER(sp_render_stats)]),
+    "sp_scene_radiance_rays_host": (C.c_int, [C.c_void_p, C.POINTER(sp_radiance_query), C.c_void_p, C.c_void_p,
+                                              C.POINTER(sp_render_stats)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

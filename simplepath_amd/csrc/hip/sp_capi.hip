@@ -2248,6 +2248,117 @@ int sp_render_views_host(sp_scene* s, const sp_view_params* p, float* h_out, sp_
     return render_to_host((int64_t)p->num_views * tiles.n, h_out, [&](float* d) { return sp_render_views(s, p, d, stats); });
 }
 
+// ---- radiance queries (SP_HAS_RADIANCE_QUERY; sp_radiance.hpp) --------------------------------------
+
+// Arguments, in the order their errors are promised; changes no state.  rays: the device buffer, or
+// the host form's array (device_pointers false: no alignment is asked of it).  The waves_per_simd
+// range is the integrator's, which the host scene names without an upload; an integrator that does
+// not resolve is refused where sp_render_tiles refuses it, after the residency.
+static int validate_radiance(const sp_scene* s, const sp_radiance_query* q, const sp_radiance_ray* rays, const float* out,
+                             bool device_pointers)
+{
+    if (!s || !q || !out) return fail(SP_ERR_ARG, "null argument");
+    if (q->struct_size != sizeof(sp_radiance_query)) return fail(SP_ERR_ARG, "sp_radiance_query.struct_size is not this library's");
+    if (q->reserved0 != 0) return fail(SP_ERR_ARG, "sp_radiance_query.reserved must be 0");
+    for (int32_t r : q->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_radiance_query.reserved must be 0");
+    if ((q->flags & ~SP_RENDER_PER_LANE_QUERIES) != 0) return fail(SP_ERR_ARG, "unknown flags");
+    if (q->num_rays < 0) return fail(SP_ERR_ARG, "num_rays < 0");
+    if (q->num_rays > 0 && !rays) return fail(SP_ERR_ARG, device_pointers ? "d_rays is NULL" : "h_rays is NULL");
+    if (device_pointers && reinterpret_cast<uintptr_t>(rays) % 16 != 0) return fail(SP_ERR_ARG, "d_rays must be 16-byte aligned");
+    if (q->samples_per_ray == 0) return fail(SP_ERR_ARG, "samples_per_ray must be > 0");
+    int32_t integ = q->integrator != SP_INTEGRATOR_NOT_SPECIFIED ? q->integrator : s->host->integrator;
+    if (integ == SP_INTEGRATOR_NOT_SPECIFIED) integ = SP_INTEGRATOR_DIRECT_LIGHTING;
+    if (q->waves_per_simd != 0 && integ >= SP_INTEGRATOR_MANDELBROT && integ <= SP_INTEGRATOR_WHITTED) {
+        int32_t same = 0;
+        if (int rc = resolve_integrator(s, integ, q->waves_per_simd, same)) return rc;
+    }
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_scene_radiance_rays");
+    return SP_OK;
+}
+
+// after validate_radiance, with the scene's lock held
+static int radiance_rays_impl(sp_scene* s, const sp_radiance_query* q, float* d_out, sp_render_stats* stats)
+{
+    int32_t integ = 0;
+    if (int rc = resolve_integrator(s, q->integrator, q->waves_per_simd, integ)) return rc;
+    if (integ == SP_INTEGRATOR_MANDELBROT) return fail(SP_ERR_UNSUPPORTED, "sp_scene_radiance_rays: Mandelbrot has no ray");
+    const int64_t items = q->num_rays / 64 + (q->num_rays % 64 != 0);
+    if (items > (int64_t)INT32_MAX)
+        return fail(SP_ERR_UNSUPPORTED, "sp_scene_radiance_rays: more than INT32_MAX queue items of 64 rays");
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch&    r      = s->scratch;
+    const hipStream_t stream = static_cast<hipStream_t>(q->stream);
+    if (stats) *stats = sp_render_stats{};
+    if (q->num_rays == 0) return SP_OK;
+    // the previous call on this scene may have used another stream (render_tiles_impl)
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    if (int rc = device_cus(s)) return rc;
+    MegaSetup m;
+    if (int rc = mega_setup(s, spd::MegaFamily::Radiance, integ, q->waves_per_simd, nullptr, items, m)) return rc;
+    SP_HIP(hipMemsetAsync(r.counters.ptr, 0, 8 * sizeof(unsigned long long), stream));
+    SP_HIP(hipMemsetAsync(r.tile_counter.ptr, 0, sizeof(int32_t), stream));
+    m.sc_run.merge_queries = (q->flags & SP_RENDER_PER_LANE_QUERIES) ? 0 : 1;
+    m.a.out = d_out;
+    m.a.spp = q->samples_per_ray;
+    spd::RadianceArgs ra{};
+    ra.rays     = q->d_rays;
+    ra.num_rays = q->num_rays;
+    SP_HIP(hipEventRecord(r.ev0, stream));
+    SP_HIP(spd::launch_radiance(m.sc_run, m.a, ra, m.integ, m.variant, m.blocks, m.lds_bytes, stream));
+    if (int rc = end_call(s, stream)) return rc;
+    if (!stats) return SP_OK; // stream order: only enqueued
+    unsigned long long ctr[8];
+    return read_stats(s, SP_PIPELINE_MEGAKERNEL, 1, stats, ctr);
+}
+
+int sp_scene_radiance_rays(sp_scene* s, const sp_radiance_query* q, float* d_out, sp_render_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    try {
+        if (int rc = validate_radiance(s, q, q ? q->d_rays : nullptr, d_out, true)) return rc;
+        return radiance_rays_impl(s, q, d_out, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_radiance_rays failed: ") + e.what());
+    }
+}
+
+// the host form with the scene's lock held: the same refusals in the same order on the host arrays
+// as given, then device buffers of its own around the device form (trace_rays_host_impl's pattern)
+static int radiance_rays_host_impl(sp_scene* s, const sp_radiance_query* q, const sp_radiance_ray* h_rays, float* h_out,
+                                   sp_render_stats* stats)
+{
+    if (int rc = validate_radiance(s, q, h_rays, h_out, false)) return rc;
+    sp_radiance_query dq = *q;
+    dq.d_rays = nullptr;
+    dq.stream = nullptr; // with the blocking copies below, as render_to_host
+    const size_t  n = (size_t)q->num_rays;
+    DeviceScratch d_rays, d_out;
+    if (n) {
+        SP_HIP(hipSetDevice(s->device));
+        SP_HIP(d_rays.reserve(n * sizeof(sp_radiance_ray)));
+        SP_HIP(d_out.reserve(n * 3 * sizeof(float)));
+        SP_HIP(hipMemcpy(d_rays.ptr, h_rays, n * sizeof(sp_radiance_ray), hipMemcpyHostToDevice));
+        dq.d_rays = d_rays.as<sp_radiance_ray>();
+    }
+    if (int rc = radiance_rays_impl(s, &dq, d_out.as<float>(), stats)) return rc;
+    if (n) SP_HIP(hipMemcpy(h_out, d_out.ptr, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_scene_radiance_rays_host(sp_scene* s, const sp_radiance_query* q, const sp_radiance_ray* h_rays, float* h_out,
+                                sp_render_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // residency is decided, and kept, under the scene's lock
+    try {
+        return radiance_rays_host_impl(s, q, h_rays, h_out, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_radiance_rays_host failed: ") + e.what());
+    }
+}
+
 // ---- progressive renders (sp_progress) ---------------------------------------------------------
 
 // pixel (x, y) of record slot * 64 + m; false: outside the image (a clipped border tile, or a

@@ -269,6 +269,16 @@ struct ViewArgs {
     int64_t    tiles_per_view; // > 0; num_views * tiles_per_view <= INT32_MAX (the queue head)
 };
 
+// Radiance queries (sp_radiance_kernel, sp_radiance.hpp; sp_scene_radiance_rays): the queue holds
+// ceil(num_rays / 64) items of 64 consecutive records (RenderArgs::num_tiles is that count, so the
+// grid is sized from the rays); RenderArgs::spp is samples_per_ray and RenderArgs::out takes three
+// floats per record.  A third kernel argument of the radiance kernels only; they read no tile list,
+// no order and no camera.
+struct RadianceArgs {
+    const sp_radiance_ray* rays;     // [num_rays] 32-byte records, 16-byte aligned
+    int64_t                num_rays; // > 0; ceil(num_rays / 64) <= INT32_MAX (the queue head)
+};
+
 // The selection of a round (sp_adaptive.hip adapt_error_kernel): which lanes of a slot are pixels,
 // and the rule's parameters.  flag == nullptr: tile errors only.
 struct SelectArgs {

@@ -10,8 +10,10 @@ namespace spd {
 
 // The persistent megakernel's families: a one-shot render (sp_render_kernel), a call on a progress
 // object (sp_resume_kernel: needs ResumeArgs) and on an adaptive one (sp_adapt_kernel: AdaptArgs too),
-// many views of the scene in one launch (sp_views_kernel: needs ViewArgs; no Mandelbrot).
-enum class MegaFamily { Render, Resume, Adapt, Views };
+// many views of the scene in one launch (sp_views_kernel: needs ViewArgs; no Mandelbrot), radiance
+// along a caller's rays (sp_radiance_kernel, sp_radiance.hpp: needs RadianceArgs; no Mandelbrot;
+// launched by launch_radiance below).
+enum class MegaFamily { Render, Resume, Adapt, Views, Radiance };
 
 // A family's kernel for an integrator.  variant = requested waves per SIMD of its
 // __launch_bounds__ (DirectLighting 1..4, IterativeRRNEE 2..4; the others have one each).
@@ -29,6 +31,12 @@ size_t kernel_static_lds(const void* kernel);
 hipError_t launch_mega(MegaFamily family, const Scene& sc, const RenderArgs& args, const ResumeArgs* res, const AdaptArgs* ad,
                        int integ, int variant, int blocks, size_t lds_bytes, hipStream_t stream, const ViewArgs* vw = nullptr);
 hipError_t launch_tail(const Scene& sc, const RenderArgs& args, int variant, int blocks, size_t lds_bytes, hipStream_t stream);
+// The radiance family (sp_radiance.hip): its kernel for an integrator (nullptr: Mandelbrot) and its
+// launch; args.num_tiles = ceil(ra.num_rays / 64) queue items, args.spp = samples per ray.  A missing
+// kernel is hipErrorInvalidDeviceFunction, never another kernel.
+const void* radiance_kernel(int integ, int variant);
+hipError_t  launch_radiance(const Scene& sc, const RenderArgs& args, const RadianceArgs& ra, int integ, int variant, int blocks,
+                            size_t lds_bytes, hipStream_t stream);
 
 // tile order: the one-sample probe of an integrator's megakernel, then the queue order
 bool       has_probe(int integ);

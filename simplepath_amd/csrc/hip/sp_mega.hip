@@ -23,6 +23,7 @@ const void* mega_kernel(MegaFamily family, int integ, int variant)
     case MegaFamily::Resume: return reinterpret_cast<const void*>(select_resume(integ, variant));
     case MegaFamily::Adapt: return reinterpret_cast<const void*>(select_adapt(integ, variant));
     case MegaFamily::Views: return reinterpret_cast<const void*>(select_views(integ, variant));
+    case MegaFamily::Radiance: return radiance_kernel(integ, variant);
     default: return reinterpret_cast<const void*>(select_kernel(integ, variant));
     }
 }
