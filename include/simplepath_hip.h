@@ -914,6 +914,114 @@ int  sp_scene_radiance_rays(sp_scene* scene, const sp_radiance_query* query, flo
 int  sp_scene_radiance_rays_host(sp_scene* scene, const sp_radiance_query* query /* d_rays ignored */,
                                  const sp_radiance_ray* h_rays, float* h_out, sp_render_stats* stats /* may be NULL */);
 
+/* ---- relighting: light, material and sky edits -------------------------------------------------
+ * Three calls change what a look-dev session changes most, without a new upload: the materials,
+ * the light list, and an image environment light (its pixels, its max_radiance, its rotation).  The
+ * contract is refit's: an edited resident scene is, in every bit, what a fresh upload of the edited
+ * descriptor would be.  The image light's tables (the constructor's clamped image, its
+ * Distribution2D and the guide tables) are built on the device, byte for byte what the upload's
+ * host builder makes (sp_scene_env_check).
+ *
+ * Common to all three, as for sp_scene_update_mesh: validation comes first and changes nothing;
+ * the scene's host copy is then overwritten, so sp_scene_get_desc and a later upload see the edit;
+ * a scene that is not resident is done at that point.  A resident scene takes the scene's lock,
+ * waits for queued work, rewrites the device arrays, and invalidates every progress object made on
+ * the scene (SP_ERR_STATE).  A device failure is SP_ERR_HIP and leaves no resident scene (the host
+ * scene is already the edited one: upload again).  The geometry trees, the primitive records, the
+ * RSQRTSS table and the camera are not touched.
+ *
+ * sp_scene_set_materials -- validation order: null scene; null `materials` with a nonzero count;
+ * num_materials other than the scene's (triangles and shapes index the materials); each material
+ * in turn: unknown kind, a clearcoat's base out of range; then a clearcoat whose base is a clearcoat
+ * (SP_ERR_UNSUPPORTED, as at upload).  Pointers from an earlier sp_scene_get_desc are stale
+ * afterwards (desc.materials is rebuilt).  The device side is one copy into the resident array.
+ *
+ * sp_scene_set_lights -- replaces the whole list; count and kinds may change.  Validation order:
+ * null scene; num_lights < 0; null `lights` with a nonzero count; each light in turn: unknown kind,
+ * an image light whose `image` names no env image of the scene.  Pointers from an earlier
+ * sp_scene_get_desc are stale afterwards.  On a resident scene the light accelerator is built
+ * again by the upload's own code (sphere lights partitioned from unbounded ones, the reference-order
+ * light BVH, the slot table, parent links when stackless) into the scene's light blocks, and the walk
+ * plan is recomputed from the new light depth: stack sizes and sp_bvh_info follow.  A light list so
+ * deep that the walk would have to change between stack and parent links is SP_ERR_UNSUPPORTED
+ * before anything changes (upload again).
+ *
+ * sp_scene_set_env_image -- replaces or appends one env image.  `image` is an existing index, or
+ * num_env_images to append (so a scene loaded without a sky can get one; sp_scene_set_lights then
+ * names it; removal is not offered).  At most one of `pixels` (host) and `d_pixels` (device) may be
+ * given, in sp_env_image layout, already multiplied by the light's radiance; with either, width
+ * and height are the new map's size.  With neither the current pixels are kept (width and height
+ * must be 0 or the current size): when max_radiance is bit-equal to the current one only the two
+ * matrices of the resident record change (rebuilt = 0: rotating the sky costs one small copy), else
+ * the tables are rebuilt from the host's unclamped pixels.  Device pixels are copied back to the
+ * host scene, which stays the truth.  Same dimensions: every table is rewritten in place and
+ * sp_scene_device_bytes does not change (unless the map gains or loses its guide tables); other
+ * dimensions: the map's blocks are released and allocated again.  Validation order: null scene or
+ * update; struct sizes (the update's, and that of stats when given); reserved fields; `image`
+ * outside [0, num_env_images]; both pixel pointers given; with pixels, width or height < 1 or above
+ * 32767; without pixels, an append, or a size that is neither 0 nor the current one; all SP_ERR_ARG;
+ * last, d_pixels on a scene that is not resident, SP_ERR_STATE.  Pointers from an earlier
+ * sp_scene_get_desc are stale when the image count or an image's size changed.
+ * sp_upload_params.env_replay of the resident upload still suppresses the guide tables. */
+#define SP_HAS_RELIGHT 1
+
+int  sp_scene_set_materials(sp_scene* scene, const sp_material_desc* materials, int32_t num_materials);
+int  sp_scene_set_lights(sp_scene* scene, const sp_light_desc* lights, int32_t num_lights);
+
+typedef struct sp_env_update {        /* zero-initialise; struct_size = sizeof */
+    uint32_t     struct_size;         /* a size the library does not know => SP_ERR_ARG */
+    int32_t      image;               /* an existing index, or num_env_images to append */
+    int32_t      width, height;       /* the new map's size (with pixels); else 0 or the current size */
+    const float* pixels;              /* HOST, width * height * 3, sp_env_image layout, or NULL */
+    const void*  d_pixels;            /* DEVICE, the same layout, or NULL */
+    float        max_radiance;        /* as sp_env_image */
+    int32_t      reserved0;           /* must be 0 */
+    sp_linear    light_to_world;      /* the light's rotation */
+    sp_linear    world_to_light;      /* its inverse */
+    int32_t      reserved[4];         /* must be 0 */
+} sp_env_update;                      /* 128 bytes */
+
+typedef struct sp_env_stats {         /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  rebuilt;                 /* 0: host scene only, or the matrices alone; 1: the resident tables were rebuilt */
+    int32_t  guided;                  /* the rebuilt map's rows and marginal are ordered (no NaN): it can have guide tables */
+    int32_t  reserved;
+    float    ms_upload, ms_clamp, ms_func, ms_rows, ms_marginal, ms_guides, ms_total; /* device stages */
+    int32_t  reserved2;
+    int64_t  scratch_bytes;           /* peak device scratch, all released before the call returns */
+} sp_env_stats;                       /* 56 bytes */
+
+/* stats may be NULL.  Passing stats makes the call wait for the device after each stage so that
+ * ms_* hold stage times. */
+int  sp_scene_set_env_image(sp_scene* scene, const sp_env_update* update, sp_env_stats* stats);
+
+/* The tables of one env image, in the order of sp_env_check.hash. */
+enum { SP_ENV_RADIANCE = 0, SP_ENV_COND_FUNC = 1, SP_ENV_COND_CDF = 2, SP_ENV_COND_INT = 3, SP_ENV_MARG_FUNC = 4,
+       SP_ENV_MARG_CDF = 5, SP_ENV_COND_GUIDE = 6, SP_ENV_MARG_GUIDE = 7, SP_ENV_SCALARS = 8, SP_ENV_TABLES = 8 };
+enum { SP_ENV_BUILDER_HOST = 0, SP_ENV_BUILDER_DEVICE = 1 };
+
+typedef struct sp_env_check {         /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  builder;                 /* SP_ENV_BUILDER_*: who made the tables that were hashed */
+    int32_t  width, height, nu, nv;
+    int32_t  guided;                  /* rows and marginal ordered */
+    int32_t  cond_bits, marg_bits;
+    uint32_t marg_int_bits;           /* the marginal's integral, as bits */
+    int64_t  mismatches;              /* resident words that differ from the host builder's (0 for the build check) */
+    int32_t  first_table;             /* SP_ENV_* of the first mismatch (SP_ENV_SCALARS: guided, bits or marg_int), -1: none */
+    int32_t  reserved;
+    int64_t  first_index;             /* its word index in that table, -1: none */
+    uint64_t hash[10];                /* FNV-1a 64 per table (0: table absent); [8], [9] are 0 */
+} sp_env_check;                       /* 144 bytes */
+
+/* Reads the resident tables of env image `image` back, builds the host's from the scene's current
+ * host pixels, and compares word for word (radiance as float4 words).  Guide tables the resident
+ * scene does not hold (env_replay, or an unguided map) are not compared.  SP_ERR_STATE when the
+ * scene is not resident; SP_ERR_ARG for an image out of range. */
+int  sp_scene_env_check(sp_scene* scene, int32_t image, sp_env_check* out);
+/* The host half alone, no device: the hashes of what the upload's host builder makes. */
+int  sp_scene_env_build_check(const sp_scene* scene, int32_t image, sp_env_check* out);
+
 /* RSQRTSS emulation table.  The reference normalises with RSQRTSS + one Newton step
  * (math/Math.h:205); RSQRTSS is a hardware table whose outputs differ between CPU vendors, so the
  * reference's images are those of the CPU it ran on.  By default scenes are built (host) and

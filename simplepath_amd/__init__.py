@@ -308,6 +308,91 @@ class Scene:
         del keep
         return self._check_dict(c), self._wide_dict(w)
 
+    def set_materials(self, materials) -> None:
+        """Replace every material (sp_scene_set_materials): a sequence of sp_material_desc, as many as
+        the scene has (desc().materials).  On a resident scene the device array is rewritten -- no
+        upload, no rebuild -- and progress objects made on the scene become invalid."""
+        arr = (_abi.sp_material_desc * max(len(materials), 1))(*materials)
+        check(lib().sp_scene_set_materials(self._h, arr, len(materials)))
+
+    def set_lights(self, lights) -> None:
+        """Replace the whole light list (sp_scene_set_lights): a sequence of sp_light_desc; count and
+        kinds may change, an image light names an existing env image.  On a resident scene the light
+        accelerator is rebuilt and the walk's stack sizes follow; geometry is not touched."""
+        arr = (_abi.sp_light_desc * max(len(lights), 1))(*lights)
+        check(lib().sp_scene_set_lights(self._h, arr, len(lights)))
+
+    def set_env_image(self, image: int, pixels=None, device_ptr: int = 0, width: int = 0, height: int = 0,
+                      max_radiance=None, light_to_world=None, stats: bool = False):
+        """Replace env image `image`, or append one when image == desc().num_env_images
+        (sp_scene_set_env_image).  pixels: [height, width, 3] float32 host array (already multiplied
+        by the light's radiance), or device_ptr with width and height for the same layout on the
+        device (e.g. a torch tensor's data_ptr()); neither keeps the current pixels.  max_radiance
+        None keeps the current value; light_to_world None keeps the current rotation, else a 3x3
+        array of the columns vx, vy, vz (rows of the array), whose inverse is computed here.  On a
+        resident scene the tables are rebuilt on the device; a rotation alone rewrites only the
+        record's matrices.  With stats=True returns a dict of sp_env_stats, else None."""
+        d = self.desc()
+        u = _abi.sp_env_update()
+        u.struct_size = C.sizeof(_abi.sp_env_update)
+        u.image = int(image)
+        cur = d.env_images[image] if 0 <= image < d.num_env_images else None
+        keep = None
+        if pixels is not None:
+            keep = np.ascontiguousarray(pixels, dtype=np.float32)
+            if keep.ndim != 3 or keep.shape[2] != 3:
+                raise ValueError("pixels must be [height, width, 3]")
+            u.height, u.width = keep.shape[0], keep.shape[1]
+            u.pixels = keep.ctypes.data_as(C.POINTER(C.c_float))
+        else:
+            u.width, u.height = int(width), int(height)
+        if device_ptr:
+            u.d_pixels = device_ptr
+        if max_radiance is None:
+            max_radiance = cur.max_radiance if cur is not None else np.finfo(np.float32).max
+        u.max_radiance = float(np.float32(max_radiance))
+        if light_to_world is None:
+            if cur is not None:
+                u.light_to_world, u.world_to_light = cur.light_to_world, cur.world_to_light
+            else:
+                light_to_world = np.eye(3)
+        if light_to_world is not None:
+            m = np.asarray(light_to_world, dtype=np.float64).reshape(3, 3)
+            inv = np.linalg.inv(m.T).T  # rows are columns of the matrix: invert the matrix itself
+            for dst, src in ((u.light_to_world, m), (u.world_to_light, inv)):
+                for name, row in zip(("vx", "vy", "vz"), src):
+                    setattr(dst, name, (C.c_float * 3)(*[float(np.float32(x)) for x in row]))
+        st = _abi.sp_env_stats()
+        st.struct_size = C.sizeof(_abi.sp_env_stats)
+        check(lib().sp_scene_set_env_image(self._h, C.byref(u), C.byref(st) if stats else None))
+        del keep
+        if not stats:
+            return None
+        return {k: getattr(st, k) for k, _ in _abi.sp_env_stats._fields_ if k not in ("struct_size", "reserved", "reserved2")}
+
+    @staticmethod
+    def _env_dict(c: _abi.sp_env_check) -> dict:
+        d = {k: getattr(c, k) for k, _ in _abi.sp_env_check._fields_ if k not in ("struct_size", "reserved", "hash")}
+        d["builder"] = {v: k for k, v in _abi.ENV_BUILDERS.items()}.get(c.builder, c.builder)
+        d["hashes"] = {name: int(c.hash[i]) for i, name in enumerate(_abi.ENV_TABLES)}
+        return d
+
+    def env_check(self, image: int = 0) -> dict:
+        """The resident tables of env image `image` read back and compared, word for word, with what
+        the host builder makes from the scene's current pixels (sp_scene_env_check): mismatches == 0
+        when they are equal; hashes name each table; builder says who made the resident ones."""
+        c = _abi.sp_env_check()
+        c.struct_size = C.sizeof(_abi.sp_env_check)
+        check(lib().sp_scene_env_check(self._h, image, C.byref(c)))
+        return self._env_dict(c)
+
+    def env_build_check(self, image: int = 0) -> dict:
+        """The host half alone, no device (sp_scene_env_build_check): the hashes of the host builder's tables."""
+        c = _abi.sp_env_check()
+        c.struct_size = C.sizeof(_abi.sp_env_check)
+        check(lib().sp_scene_env_build_check(self._h, image, C.byref(c)))
+        return self._env_dict(c)
+
     def trace(self, origins, directions, tmin=K_RAY_EPSILON, tmax=K_INFINITE, mode="closest", normals: bool = False):
         """Ray queries on the resident scene from host arrays (sp_scene_trace_rays_host): the
         reference's Scene::intersect ("closest") and Scene::intersect_p ("any") for the caller's

@@ -171,6 +171,34 @@ class sp_refit_stats(C.Structure):
                 ("ms_total", C.c_float), ("scratch_bytes", C.c_int64)]
 
 
+class sp_env_update(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("image", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("pixels", C.POINTER(C.c_float)), ("d_pixels", C.c_void_p),
+                ("max_radiance", C.c_float), ("reserved0", C.c_int32),
+                ("light_to_world", sp_linear), ("world_to_light", sp_linear), ("reserved", C.c_int32 * 4)]
+
+
+class sp_env_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rebuilt", C.c_int32), ("guided", C.c_int32), ("reserved", C.c_int32),
+                ("ms_upload", C.c_float), ("ms_clamp", C.c_float), ("ms_func", C.c_float), ("ms_rows", C.c_float),
+                ("ms_marginal", C.c_float), ("ms_guides", C.c_float), ("ms_total", C.c_float), ("reserved2", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
+ENV_TABLES = ("radiance", "cond_func", "cond_cdf", "cond_int", "marg_func", "marg_cdf", "cond_guide", "marg_guide")
+SP_ENV_SCALARS = 8
+SP_ENV_BUILDER_HOST, SP_ENV_BUILDER_DEVICE = 0, 1
+ENV_BUILDERS = {"host": SP_ENV_BUILDER_HOST, "device": SP_ENV_BUILDER_DEVICE}
+
+
+class sp_env_check(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("builder", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32),
+                ("guided", C.c_int32), ("cond_bits", C.c_int32), ("marg_bits", C.c_int32), ("marg_int_bits", C.c_uint32),
+                ("mismatches", C.c_int64), ("first_table", C.c_int32), ("reserved", C.c_int32),
+                ("first_index", C.c_int64), ("hash", C.c_uint64 * 10)]
+
+
 SP_QUERY_CLOSEST, SP_QUERY_ANY = 0, 1
 QUERY_MODES = {"closest": SP_QUERY_CLOSEST, "any": SP_QUERY_ANY}
 
@@ -289,6 +317,11 @@ SIGNATURES = {
     "sp_scene_update_mesh": (C.c_int, [C.c_void_p, C.POINTER(sp_mesh_update), C.POINTER(sp_refit_stats)]),
     "sp_scene_refit_build_check": (C.c_int, [C.c_void_p, C.POINTER(sp_upload_params), C.POINTER(sp_build_params),
                                              C.POINTER(sp_mesh_update), C.POINTER(sp_bvh_check), C.POINTER(sp_wide_check)]),
+    "sp_scene_set_materials": (C.c_int, [C.c_void_p, C.POINTER(sp_material_desc), C.c_int32]),
+    "sp_scene_set_lights": (C.c_int, [C.c_void_p, C.POINTER(sp_light_desc), C.c_int32]),
+    "sp_scene_set_env_image": (C.c_int, [C.c_void_p, C.POINTER(sp_env_update), C.POINTER(sp_env_stats)]),
+    "sp_scene_env_check": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(sp_env_check)]),
+    "sp_scene_env_build_check": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(sp_env_check)]),
     "sp_scene_trace_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_ray_query), C.POINTER(sp_ray_query_stats)]),
     "sp_scene_trace_rays_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(sp_ray_query_stats)]),

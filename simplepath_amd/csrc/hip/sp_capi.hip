@@ -10,6 +10,7 @@
 #include "sp_finish.hpp"
 #include "sp_refit.hpp"
 #include "sp_query.hpp"
+#include "sp_envbuild.hpp"
 #include "../common/sp_refit.h"
 #include "../common/sp_sah.h"
 #include "../host/sp_host.hpp"
@@ -122,6 +123,7 @@ struct UploadOpts {
 struct UploadHooks {
     int  stackless = 0, stack_max = 96, wide = 1, env_guide = 1, wide_closest = 1, sah_leaf = 4;
     int  device_build = 0, device_finish = -1; // -1: the finish follows the builder
+    int  device_env   = 0;                     // SP_DEVICE_ENV=1: the image lights' tables from the device builder (sp_envbuild.hip)
     int  sah_small    = 0;                     // SP_SAH_SMALL: the device SAH builder's hand-over size (0: its default)
     bool timing     = false;                   // SP_UPLOAD_TIMING (set at all): the sp_upload_timing line
     bool rsqrt_pack = true;                    // SP_RSQRT_PACK=0: 32-bit RSQRTSS entries (comparison)
@@ -134,6 +136,7 @@ struct UploadHooks {
             { "SP_STACKLESS", &h.stackless }, { "SP_STACK_MAX", &h.stack_max }, { "SP_WIDE", &h.wide },
             { "SP_ENV_GUIDE", &h.env_guide }, { "SP_WIDE_CLOSEST", &h.wide_closest }, { "SP_SAH_LEAF", &h.sah_leaf },
             { "SP_DEVICE_BUILD", &h.device_build }, { "SP_DEVICE_FINISH", &h.device_finish }, { "SP_SAH_SMALL", &h.sah_small },
+            { "SP_DEVICE_ENV", &h.device_env },
             { "SP_RSQRT_PACK", &pack } };
         for (const auto& e : ints)
             if (const char* v = std::getenv(e.first)) *e.second = std::atoi(v);
@@ -326,6 +329,19 @@ struct HostAccel {
 
 enum class BuildOn { HOST, DEVICE }; // where a device builder runs: its host restatement, or the current device
 
+// Scene ctor's light accelerator (base/Scene.h:29): sphere lights first (libstdc++
+// std::partition order), the reference BVH over them; the rest are unbounded.  An upload's, and
+// sp_scene_set_lights' on a resident scene.
+void build_light_tree(const std::vector<sp_light_desc>& lights, HostAccel& a)
+{
+    a.lids.resize(lights.size());
+    for (size_t i = 0; i < a.lids.size(); ++i) a.lids[i] = (int32_t)i;
+    a.lpart = sph::stl_partition(a.lids, 0, a.lids.size(), [&](int32_t i) { return lights[i].kind == SP_LIGHT_SPHERE; });
+    std::vector<sph::PrimBounds> lb;
+    for (size_t i = 0; i < a.lpart; ++i) lb.push_back(sphere_bounds(from_desc(lights[a.lids[i]].object_to_world)));
+    a.lbvh = sph::build_bvh_reference(lb);
+}
+
 // Bounds; the BVH over the bounded part -- the reference's median split (bvh_mode 1,
 // shapes/BVHAccelerator.h:173), binned SAH, or the linear BVH of the device builder (one tree,
 // from the device or its host restatement); the light BVH; and from their depths whether the scene
@@ -364,14 +380,7 @@ void build_trees(const sph::Scene& h, HostAccel& a, const UploadOpts& o, BuildOn
     a.n_nodes       = kept ? keep->n_nodes : a.bvh.nodes.size();
     a.n_slots       = kept ? keep->n_slots : a.bvh.prim_order.size();
     if (tm) tm->lap(tm->ms_bvh);
-    // Scene ctor's light accelerator (base/Scene.h:29): sphere lights first (libstdc++
-    // std::partition order), the reference BVH over them; the rest are unbounded
-    a.lids.resize(h.lights.size());
-    for (size_t i = 0; i < a.lids.size(); ++i) a.lids[i] = (int32_t)i;
-    a.lpart = sph::stl_partition(a.lids, 0, a.lids.size(), [&](int32_t i) { return h.lights[i].kind == SP_LIGHT_SPHERE; });
-    std::vector<sph::PrimBounds> lb;
-    for (size_t i = 0; i < a.lpart; ++i) lb.push_back(sphere_bounds(from_desc(h.lights[a.lids[i]].object_to_world)));
-    a.lbvh      = sph::build_bvh_reference(lb);
+    build_light_tree(h.lights, a);
     a.walk      = walk_plan(o, a.bvh.max_depth, a.lbvh.max_depth, 0);
     a.want_wide = o.bvh_mode != 1 && o.wide && a.n_nodes != 0 && !a.walk.stackless;
     if (a.walk.stackless) a.light_parents = parent_links(a.lbvh.nodes);
@@ -542,6 +551,23 @@ struct RenderScratch {
     int           n_cu = 0;    // the device's compute units (0: not asked yet)
 };
 
+// The device blocks of the parts of a resident scene that an edit replaces (sp_scene_set_lights,
+// sp_scene_set_env_image): each block is as large as its array, so an edited scene holds the
+// bytes a fresh upload of the edited scene would.
+struct LightBlocks {
+    DeviceScratch lights, unbounded, nodes, slot, parents;
+    size_t bytes() const { return lights.cap + unbounded.cap + nodes.cap + slot.cap + parents.cap; }
+};
+struct EnvBlocks {
+    DeviceScratch radiance, cond_func, cond_cdf, cond_int, marg_func, marg_cdf, cond_guide, marg_guide;
+    int  builder = SP_ENV_BUILDER_HOST; // who made the tables
+    bool guided  = false;               // rows and marginal ordered (the guide blocks exist only if the upload wants them too)
+    size_t bytes() const
+    {
+        return radiance.cap + cond_func.cap + cond_cdf.cap + cond_int.cap + marg_func.cap + marg_cdf.cap + cond_guide.cap + marg_guide.cap;
+    }
+};
+
 // Sizes of the resident accelerators: what the check and info calls need to read them back
 struct ResidentSizes {
     int    geom_depth = 0, light_depth = 0, wide_depth = 0;
@@ -558,7 +584,11 @@ struct sp_scene {
     // device residency
     int                  device   = -1; // >= 0 only after an upload that built everything
     UploadOpts           opts{};    // effective accelerator options of the resident upload
-    std::vector<DeviceScratch> bufs; // every device array of the resident scene
+    std::vector<DeviceScratch> bufs; // every device array of the resident scene that no edit replaces
+    LightBlocks          light_blocks; // lights and their accelerator
+    std::vector<EnvBlocks>   env_blocks; // per env image, its tables
+    std::vector<spd::EnvMap> env_recs;   // the host's copy of dev.envs
+    DeviceScratch        env_recs_buf;
     spd::Scene           dev{};
     ResidentSizes        sizes;
     // One scene, many host threads (the reference's render() shares one Scene across N threads,
@@ -585,6 +615,10 @@ struct sp_scene {
         refitted = false;
         if (device >= 0) (void)hipSetDevice(device);
         bufs.clear();
+        light_blocks = LightBlocks{};
+        env_blocks.clear();
+        env_recs.clear();
+        env_recs_buf.reset();
         scratch = RenderScratch{};
         sizes   = ResidentSizes{};
         dev     = spd::Scene{};
@@ -614,6 +648,32 @@ struct sp_scene {
         SP_HIP(hipMemcpy(bufs.back().ptr, v.data(), bufs.back().cap, hipMemcpyHostToDevice));
         *out = bufs.back().as<T>();
         return SP_OK;
+    }
+
+    // `v` into a block of exactly its size: the block is kept when the size is, else made again
+    template <typename T>
+    int put(DeviceScratch& b, const std::vector<T>& v, const T** out)
+    {
+        *out = nullptr;
+        if (v.empty()) {
+            b.reset();
+            return SP_OK;
+        }
+        const size_t bytes = v.size() * sizeof(T);
+        if (b.cap != bytes) {
+            b.reset();
+            SP_HIP(b.reserve(bytes));
+        }
+        SP_HIP(hipMemcpy(b.ptr, v.data(), bytes, hipMemcpyHostToDevice));
+        *out = b.as<T>();
+        return SP_OK;
+    }
+    size_t device_bytes() const
+    {
+        size_t b = light_blocks.bytes() + env_recs_buf.cap;
+        for (const auto& d : bufs) b += d.cap;
+        for (const auto& e : env_blocks) b += e.bytes();
+        return b;
     }
 };
 
@@ -1106,6 +1166,28 @@ static std::vector<spd::Light> convert_lights(const sph::Scene& h) // Scene::m_l
     return lights;
 }
 
+// The lights and the light accelerator (partition by boundedness: unbounded lights, nodes, slot ->
+// light, parent links when stackless) of `a`, into the scene's light blocks
+static int upload_lights(sp_scene* s, const HostAccel& a)
+{
+    const sph::Scene& h = *s->host;
+    spd::Scene&       d = s->dev;
+    LightBlocks&      b = s->light_blocks;
+    d.n_lights = (int)h.lights.size();
+    SP_TRY(s->put(b.lights, convert_lights(h), &d.lights));
+    std::vector<int32_t>  unbounded_lights(a.lids.begin() + (long)a.lpart, a.lids.end());
+    std::vector<uint32_t> light_slot(a.lbvh.prim_order.size());
+    for (size_t sl = 0; sl < light_slot.size(); ++sl) light_slot[sl] = (uint32_t)a.lids[a.lbvh.prim_order[sl]];
+    std::vector<spd::Node> lnodes(a.lbvh.nodes.size());
+    std::memcpy(lnodes.data(), a.lbvh.nodes.data(), lnodes.size() * sizeof(spd::Node));
+    d.n_unbounded_lights = (int)unbounded_lights.size();
+    SP_TRY(s->put(b.unbounded, unbounded_lights, &d.unbounded_lights));
+    d.n_light_nodes = (int)lnodes.size();
+    SP_TRY(s->put(b.nodes, lnodes, &d.light_nodes));
+    SP_TRY(s->put(b.slot, light_slot, &d.light_slot));
+    return s->put(b.parents, a.light_parents, &d.light_parents); // (empty unless stackless)
+}
+
 // Camera, the unbounded list, the binary tree (adopted where the device built it), normals, indices
 // (the device finish reads them), triangle materials, shapes, lights and the light accelerator
 static int upload_scene_arrays(UploadCall& c)
@@ -1140,20 +1222,7 @@ static int upload_scene_arrays(UploadCall& c)
     SP_TRY(c.s->upload(h.indices, &d.indices));
     SP_TRY(c.s->upload(h.tri_material, &d.tri_material));
     SP_TRY(c.s->upload(convert_shapes(h), &d.shapes));
-    d.n_lights = (int)h.lights.size();
-    SP_TRY(c.s->upload(convert_lights(h), &d.lights));
-    // the light accelerator (partition by boundedness): unbounded lights, nodes, slot -> light
-    std::vector<int32_t>  unbounded_lights(a.lids.begin() + (long)a.lpart, a.lids.end());
-    std::vector<uint32_t> light_slot(a.lbvh.prim_order.size());
-    for (size_t sl = 0; sl < light_slot.size(); ++sl) light_slot[sl] = (uint32_t)a.lids[a.lbvh.prim_order[sl]];
-    std::vector<spd::Node> lnodes(a.lbvh.nodes.size());
-    std::memcpy(lnodes.data(), a.lbvh.nodes.data(), lnodes.size() * sizeof(spd::Node));
-    d.n_unbounded_lights = (int)unbounded_lights.size();
-    SP_TRY(c.s->upload(unbounded_lights, &d.unbounded_lights));
-    d.n_light_nodes = (int)lnodes.size();
-    SP_TRY(c.s->upload(lnodes, &d.light_nodes));
-    SP_TRY(c.s->upload(light_slot, &d.light_slot));
-    return c.s->upload(a.light_parents, &d.light_parents); // (empty unless stackless)
+    return upload_lights(c.s, a);
 }
 
 // The finish's arrays as finish_host made them.  Like run_device_finish it fills wnodes, wslot_tri,
@@ -1217,35 +1286,119 @@ static int run_device_finish(UploadCall& c)
     return SP_OK;
 }
 
-// Image environment lights: the constructor's tables (sp_envmap.cpp), then the EnvMap records
+// ---- image environment lights: the constructor's tables, then the EnvMap records -----------------
+
+// the blocks of a w x h map, each exactly as large as its table; the guide blocks only when asked
+static int env_alloc(EnvBlocks& b, const spe::EnvSizes& z, bool guides)
+{
+    auto need = [](DeviceScratch& d, size_t bytes) -> hipError_t {
+        if (d.cap == bytes) return hipSuccess;
+        d.reset();
+        return bytes ? d.reserve(bytes) : hipSuccess;
+    };
+    SP_HIP(need(b.radiance, z.texels * sizeof(float4)));
+    SP_HIP(need(b.cond_func, z.func * 4));
+    SP_HIP(need(b.cond_cdf, z.cdf * 4));
+    SP_HIP(need(b.cond_int, z.rows * 4));
+    SP_HIP(need(b.marg_func, z.rows * 4));
+    SP_HIP(need(b.marg_cdf, z.marg_cdf * 4));
+    SP_HIP(need(b.cond_guide, guides ? z.cond_guide * 4 : 0));
+    SP_HIP(need(b.marg_guide, guides ? z.marg_guide * 4 : 0));
+    return SP_OK;
+}
+
+// the record a kernel reads, from the blocks and the image's matrices
+static spd::EnvMap env_record(const EnvBlocks& b, const sph::EnvImage& e, const spe::EnvSizes& z, float marg_int)
+{
+    spd::EnvMap x{};
+    x.l2w = e.light_to_world;
+    x.w2l = e.world_to_light;
+    x.w = e.width; x.h = e.height; x.nu = z.nu; x.nv = z.nv;
+    x.radiance   = b.radiance.as<float4>();
+    x.cond_func  = b.cond_func.as<float>();
+    x.cond_cdf   = b.cond_cdf.as<float>();
+    x.cond_int   = b.cond_int.as<float>();
+    x.marg_func  = b.marg_func.as<float>();
+    x.marg_cdf   = b.marg_cdf.as<float>();
+    x.marg_int   = marg_int;
+    x.cond_guide = b.cond_guide.as<uint32_t>(); // null: the exact upper_bound replay (identical results)
+    x.marg_guide = b.marg_guide.as<uint32_t>();
+    x.cond_bits  = z.cond_bits;
+    x.marg_bits  = z.marg_bits;
+    return x;
+}
+
+// Tables of env image i by the host builder (sp_envmap.cpp), copied into its blocks
+static int env_build_host(sp_scene* s, size_t i, bool env_guide)
+{
+    const sph::EnvImage&  e = s->host->env_images[i];
+    EnvBlocks&            b = s->env_blocks[i];
+    const sph::EnvMap     m = sph::build_env_map(e);
+    const spe::EnvSizes   z = spe::env_sizes(e.width, e.height);
+    SP_TRY(env_alloc(b, z, m.guided && env_guide));
+    std::vector<float4> rad((size_t)m.w * m.h);
+    for (size_t k = 0; k < rad.size(); ++k) rad[k] = make_float4(m.radiance[3 * k], m.radiance[3 * k + 1], m.radiance[3 * k + 2], 0.0f);
+    auto up = [](DeviceScratch& d, const void* src) { return d.cap ? hipMemcpy(d.ptr, src, d.cap, hipMemcpyHostToDevice) : hipSuccess; };
+    SP_HIP(up(b.radiance, rad.data()));
+    SP_HIP(up(b.cond_func, m.cond_func.data()));
+    SP_HIP(up(b.cond_cdf, m.cond_cdf.data()));
+    SP_HIP(up(b.cond_int, m.cond_int.data()));
+    SP_HIP(up(b.marg_func, m.marg_func.data()));
+    SP_HIP(up(b.marg_cdf, m.marg_cdf.data()));
+    SP_HIP(up(b.cond_guide, m.cond_guide.data()));
+    SP_HIP(up(b.marg_guide, m.marg_guide.data()));
+    b.builder      = SP_ENV_BUILDER_HOST;
+    b.guided       = m.guided;
+    s->env_recs[i] = env_record(b, e, z, m.marg_int);
+    return SP_OK;
+}
+
+// The same tables by the device builder (sp_envbuild.hip) from the host's pixels, or from the
+// caller's device copy of them
+static int env_build_device(sp_scene* s, size_t i, const float* d_pixels, bool env_guide, spe::EnvBuildStats& st, bool timed)
+{
+    const sph::EnvImage& e = s->host->env_images[i];
+    EnvBlocks&           b = s->env_blocks[i];
+    const spe::EnvSizes  z = spe::env_sizes(e.width, e.height);
+    SP_TRY(env_alloc(b, z, env_guide));
+    spe::EnvBuildIn in;
+    in.w = e.width; in.h = e.height;
+    in.max_radiance = e.max_radiance;
+    in.h_pixels     = d_pixels ? nullptr : e.pixels.data();
+    in.d_pixels     = d_pixels;
+    in.radiance     = b.radiance.as<float4>();
+    in.cond_func    = b.cond_func.as<float>();
+    in.cond_cdf     = b.cond_cdf.as<float>();
+    in.cond_int     = b.cond_int.as<float>();
+    in.marg_func    = b.marg_func.as<float>();
+    in.marg_cdf     = b.marg_cdf.as<float>();
+    in.cond_guide   = b.cond_guide.as<uint32_t>();
+    in.marg_guide   = b.marg_guide.as<uint32_t>();
+    spe::EnvBuildOut out;
+    std::string      err;
+    if (const int rc = spe::build_env_device(in, out, st, err, timed)) return fail(rc, err);
+    if (!out.guided) { // as the host: one row out of order and the map has no guides
+        b.cond_guide.reset();
+        b.marg_guide.reset();
+    }
+    b.builder      = SP_ENV_BUILDER_DEVICE;
+    b.guided       = out.guided;
+    s->env_recs[i] = env_record(b, e, z, out.marg_int);
+    return SP_OK;
+}
+
+static int upload_env_records(sp_scene* s) { return s->put(s->env_recs_buf, s->env_recs, &s->dev.envs); }
+
 static int upload_envs(UploadCall& c)
 {
-    spd::Scene&              d = c.s->dev;
-    std::vector<spd::EnvMap> envs;
-    for (const auto& e : c.s->host->env_images) {
-        const sph::EnvMap m = sph::build_env_map(e);
-        spd::EnvMap       x{};
-        x.l2w = e.light_to_world;
-        x.w2l = e.world_to_light;
-        x.w = m.w; x.h = m.h; x.nu = m.nu; x.nv = m.nv;
-        std::vector<float4> rad((size_t)m.w * m.h);
-        for (size_t i = 0; i < rad.size(); ++i) rad[i] = make_float4(m.radiance[3 * i], m.radiance[3 * i + 1], m.radiance[3 * i + 2], 0.0f);
-        SP_TRY(c.s->upload(rad, &x.radiance));
-        SP_TRY(c.s->upload(m.cond_func, &x.cond_func));
-        SP_TRY(c.s->upload(m.cond_cdf, &x.cond_cdf));
-        SP_TRY(c.s->upload(m.cond_int, &x.cond_int));
-        SP_TRY(c.s->upload(m.marg_func, &x.marg_func));
-        SP_TRY(c.s->upload(m.marg_cdf, &x.marg_cdf));
-        x.marg_int   = m.marg_int;
-        x.cond_bits  = m.cond_bits;
-        x.marg_bits  = m.marg_bits;
-        if (m.guided && c.opts.env_guide) { // else the exact upper_bound replay (identical results)
-            SP_TRY(c.s->upload(m.cond_guide, &x.cond_guide));
-            SP_TRY(c.s->upload(m.marg_guide, &x.marg_guide));
-        }
-        envs.push_back(x);
+    sp_scene* s = c.s;
+    s->env_blocks.resize(s->host->env_images.size());
+    s->env_recs.resize(s->host->env_images.size());
+    for (size_t i = 0; i < s->env_blocks.size(); ++i) {
+        spe::EnvBuildStats st;
+        SP_TRY(c.hooks.device_env ? env_build_device(s, i, nullptr, c.opts.env_guide, st, false) : env_build_host(s, i, c.opts.env_guide));
     }
-    return c.s->upload(envs, &d.envs);
+    return upload_env_records(s);
 }
 
 // RSQRTSS table in its device form (sp_rsqrt_pack.hpp: 16-bit entries where the table allows it)
@@ -1265,11 +1418,10 @@ static int upload_rsqrt_table(UploadCall& c, const sph::RsqrtCapture& rc)
     return SP_OK;
 }
 
-static void apply_walk_plan(UploadCall& c)
+static void apply_walk_plan(sp_scene* s, const UploadOpts& opts, const WalkPlan& w)
 {
-    const WalkPlan& w = c.accel.walk;
-    spd::Scene&     d = c.s->dev;
-    d.ordered         = c.opts.bvh_mode == 1 ? 0 : 1; // reference order is part of the bit-exact contract
+    spd::Scene&     d = s->dev;
+    d.ordered         = opts.bvh_mode == 1 ? 0 : 1; // reference order is part of the bit-exact contract
     d.wide_closest    = w.wide_closest ? 1 : 0;
     d.stackless       = w.stackless ? 1 : 0;
     d.stack_depth     = w.stack_depth;
@@ -1342,7 +1494,7 @@ static int build_residency(UploadCall& c)
     s->sizes.light_depth = a.lbvh.max_depth;
     s->sizes.geom_nodes  = a.n_nodes;
     s->sizes.geom_slots  = a.n_slots;
-    apply_walk_plan(c);
+    apply_walk_plan(s, c.opts, a.walk);
     SP_TRY(create_render_handles(s));
     if (c.tm) {
         c.tm->lap(c.tm->ms_copies);
@@ -3332,6 +3484,337 @@ int sp_scene_refit_build_check(const sp_scene* s, const sp_upload_params* params
     }
 }
 
+// ---- relighting: material, light and sky edits ---------------------------------------
+
+namespace {
+#define SP_TRY(call) do { if (int rc__ = (call)) return rc__; } while (0)
+
+// the start of every edit of a resident scene (the caller holds the lock): nothing queued reads the
+// arrays any more, and every progress object made on the scene is retired
+int begin_edit(sp_scene* s)
+{
+    SP_HIP(hipSetDevice(s->device));
+    SP_TRY(wait_done(s));
+    ++s->generation;
+    return SP_OK;
+}
+
+// how an edit ends: a failure leaves no resident scene, as after a failed upload
+int end_edit(sp_scene* s, int rc)
+{
+    if (rc == SP_OK) return SP_OK;
+    (void)hipGetLastError();
+    s->release();
+    return rc;
+}
+
+spm::lin lin_of(const sp_linear& d) { return from_desc(d); }
+bool     same_bits(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
+
+// sp_env_update against the scene, in the order the header promises; changes nothing
+int validate_env_update(const sp_scene* s, const sp_env_update* u, const sp_env_stats* stats)
+{
+    if (!u) return fail(SP_ERR_ARG, "null sp_env_update");
+    if (u->struct_size != sizeof(sp_env_update)) return fail(SP_ERR_ARG, "sp_env_update.struct_size is not a known size");
+    if (stats && stats->struct_size != sizeof(sp_env_stats)) return fail(SP_ERR_ARG, "sp_env_stats.struct_size is not a known size");
+    if (u->reserved0 != 0 || u->reserved[0] != 0 || u->reserved[1] != 0 || u->reserved[2] != 0 || u->reserved[3] != 0)
+        return fail(SP_ERR_ARG, "sp_env_update.reserved must be 0");
+    const int32_t n = (int32_t)s->host->env_images.size();
+    if (u->image < 0 || u->image > n) return fail(SP_ERR_ARG, "sp_env_update.image is out of range");
+    if (u->pixels && u->d_pixels) return fail(SP_ERR_ARG, "sp_env_update: pixels and d_pixels are both given");
+    if (u->pixels || u->d_pixels) {
+        if (u->width < 1 || u->height < 1 || u->width > 32767 || u->height > 32767)
+            return fail(SP_ERR_ARG, "sp_env_update: bad image size");
+    } else {
+        if (u->image == n) return fail(SP_ERR_ARG, "sp_env_update: an appended image needs pixels");
+        const sph::EnvImage& e = s->host->env_images[(size_t)u->image];
+        if (!((u->width == 0 && u->height == 0) || (u->width == e.width && u->height == e.height)))
+            return fail(SP_ERR_ARG, "sp_env_update: without pixels the size is 0 or the current one");
+    }
+    if (u->d_pixels && s->device < 0) return fail(SP_ERR_STATE, "sp_env_update.d_pixels needs a resident scene");
+    return SP_OK;
+}
+
+void fill_env_stats(sp_env_stats* stats, int rebuilt, bool guided, const spe::EnvBuildStats& st)
+{
+    if (!stats) return;
+    *stats             = sp_env_stats{};
+    stats->struct_size = sizeof(sp_env_stats);
+    stats->rebuilt     = rebuilt;
+    stats->guided      = guided ? 1 : 0;
+    stats->ms_upload   = (float)st.ms_upload;
+    stats->ms_clamp    = (float)st.ms_clamp;
+    stats->ms_func     = (float)st.ms_func;
+    stats->ms_rows     = (float)st.ms_rows;
+    stats->ms_marginal = (float)st.ms_marginal;
+    stats->ms_guides   = (float)st.ms_guides;
+    stats->ms_total    = (float)st.ms_total;
+    stats->scratch_bytes = (int64_t)st.peak_bytes;
+}
+
+// the resident side of sp_scene_set_env_image; the host scene is the edited one already
+int relight_env(sp_scene* s, size_t i, const float* d_pixels, bool matrices_only, sp_env_stats* stats)
+{
+    spe::EnvBuildStats st;
+    if (matrices_only) {
+        const sph::EnvImage& e = s->host->env_images[i];
+        s->env_recs[i].l2w     = e.light_to_world;
+        s->env_recs[i].w2l     = e.world_to_light;
+        SP_HIP(hipMemcpy(s->env_recs_buf.as<spd::EnvMap>() + i, &s->env_recs[i], sizeof(spd::EnvMap), hipMemcpyHostToDevice));
+        fill_env_stats(stats, 0, s->env_blocks[i].guided, st);
+        return SP_OK;
+    }
+    if (i == s->env_blocks.size()) {
+        s->env_blocks.emplace_back();
+        s->env_recs.emplace_back();
+    }
+    SP_TRY(env_build_device(s, i, d_pixels, s->opts.env_guide, st, stats != nullptr));
+    SP_TRY(upload_env_records(s));
+    fill_env_stats(stats, 1, s->env_blocks[i].guided, st);
+    return SP_OK;
+}
+
+// FNV-1a 64 of a table (0: absent)
+uint64_t table_hash(const void* p, size_t bytes) { return bytes ? sph::fnv1a64(p, bytes) : 0; }
+
+struct EnvTables { // one map's tables as words, in SP_ENV_* order
+    std::vector<uint32_t> t[SP_ENV_TABLES];
+    bool                  guided = false;
+    uint32_t              marg_int_bits = 0;
+};
+
+EnvTables host_tables(const sph::EnvImage& e)
+{
+    const sph::EnvMap m = sph::build_env_map(e);
+    EnvTables         x;
+    auto              to_words = [](const auto& v, std::vector<uint32_t>& w) {
+        static_assert(sizeof(v[0]) == 4, "a table of words");
+        w.resize(v.size());
+        if (!v.empty()) std::memcpy(w.data(), v.data(), v.size() * 4);
+    };
+    x.t[SP_ENV_RADIANCE].assign((size_t)m.w * m.h * 4, 0u);
+    for (size_t k = 0; k < (size_t)m.w * m.h; ++k) std::memcpy(&x.t[SP_ENV_RADIANCE][4 * k], &m.radiance[3 * k], 12);
+    to_words(m.cond_func, x.t[SP_ENV_COND_FUNC]);
+    to_words(m.cond_cdf, x.t[SP_ENV_COND_CDF]);
+    to_words(m.cond_int, x.t[SP_ENV_COND_INT]);
+    to_words(m.marg_func, x.t[SP_ENV_MARG_FUNC]);
+    to_words(m.marg_cdf, x.t[SP_ENV_MARG_CDF]);
+    to_words(m.cond_guide, x.t[SP_ENV_COND_GUIDE]);
+    to_words(m.marg_guide, x.t[SP_ENV_MARG_GUIDE]);
+    x.guided = m.guided;
+    std::memcpy(&x.marg_int_bits, &m.marg_int, 4);
+    return x;
+}
+
+void fill_env_check(sp_env_check* out, const sph::EnvImage& e, const EnvTables& x, int builder)
+{
+    const spe::EnvSizes z = spe::env_sizes(e.width, e.height);
+    *out               = sp_env_check{};
+    out->struct_size   = sizeof(sp_env_check);
+    out->builder       = builder;
+    out->width         = e.width;
+    out->height        = e.height;
+    out->nu            = z.nu;
+    out->nv            = z.nv;
+    out->guided        = x.guided ? 1 : 0;
+    out->cond_bits     = z.cond_bits;
+    out->marg_bits     = z.marg_bits;
+    out->marg_int_bits = x.marg_int_bits;
+    out->first_table   = -1;
+    out->first_index   = -1;
+    for (int k = 0; k < SP_ENV_TABLES; ++k) out->hash[k] = table_hash(x.t[k].data(), x.t[k].size() * 4);
+}
+} // namespace
+
+int sp_scene_set_materials(sp_scene* s, const sp_material_desc* materials, int32_t num_materials)
+{
+    if (!s) return fail(SP_ERR_ARG, "null scene");
+    std::lock_guard<std::mutex> lock(s->mu);
+    sph::Scene&                 h = *s->host;
+    if (!materials && num_materials != 0) return fail(SP_ERR_ARG, "sp_scene_set_materials: null materials");
+    if (num_materials != (int32_t)h.materials.size()) return fail(SP_ERR_ARG, "sp_scene_set_materials: num_materials is not the scene's");
+    for (int32_t i = 0; i < num_materials; ++i) {
+        const sp_material_desc& m = materials[i];
+        if (m.kind < SP_MAT_LAMBERTIAN || m.kind > SP_MAT_CLEARCOAT ||
+            (m.kind == SP_MAT_CLEARCOAT && (m.base < 0 || m.base >= num_materials)))
+            return fail(SP_ERR_ARG, "sp_scene_set_materials: bad material");
+    }
+    for (int32_t i = 0; i < num_materials; ++i)
+        if (materials[i].kind == SP_MAT_CLEARCOAT && materials[materials[i].base].kind == SP_MAT_CLEARCOAT)
+            return fail(SP_ERR_UNSUPPORTED, "clearcoat over clearcoat");
+    try {
+        for (int32_t i = 0; i < num_materials; ++i) h.materials[(size_t)i].d = materials[i];
+        fill_desc(s);
+        if (s->device < 0 || num_materials == 0) return SP_OK;
+        std::vector<spd::Material> mats;
+        SP_TRY(convert_materials(h, mats));
+        int rc = begin_edit(s);
+        if (rc == SP_OK) {
+            const hipError_t e = hipMemcpy(const_cast<spd::Material*>(s->dev.materials), mats.data(), mats.size() * sizeof(spd::Material),
+                                           hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = fail(SP_ERR_HIP, std::string("sp_scene_set_materials: ") + hipGetErrorString(e));
+        }
+        return end_edit(s, rc);
+    } catch (const std::exception& e) {
+        return end_edit(s, fail(SP_ERR_UNSUPPORTED, std::string("sp_scene_set_materials: ") + e.what()));
+    }
+}
+
+int sp_scene_set_lights(sp_scene* s, const sp_light_desc* lights, int32_t num_lights)
+{
+    if (!s) return fail(SP_ERR_ARG, "null scene");
+    std::lock_guard<std::mutex> lock(s->mu);
+    sph::Scene&                 h = *s->host;
+    if (num_lights < 0) return fail(SP_ERR_ARG, "sp_scene_set_lights: num_lights < 0");
+    if (!lights && num_lights != 0) return fail(SP_ERR_ARG, "sp_scene_set_lights: null lights");
+    for (int32_t i = 0; i < num_lights; ++i) {
+        const sp_light_desc& l = lights[i];
+        if (l.kind < SP_LIGHT_SPHERE || l.kind > SP_LIGHT_IMAGE_ENVIRONMENT) return fail(SP_ERR_ARG, "sp_scene_set_lights: bad light kind");
+        if (l.kind == SP_LIGHT_IMAGE_ENVIRONMENT && (l.image < 0 || l.image >= (int32_t)h.env_images.size()))
+            return fail(SP_ERR_ARG, "sp_scene_set_lights: light image out of range");
+    }
+    try {
+        std::vector<sp_light_desc> list(lights, lights + num_lights);
+        HostAccel                  a;
+        WalkPlan                   walk;
+        if (s->device >= 0) { // the new accelerator first: a walk that cannot follow is refused before anything changes
+            build_light_tree(list, a);
+            walk = walk_plan(s->opts, s->sizes.geom_depth, a.lbvh.max_depth, s->sizes.wide_depth);
+            if (walk.stackless != (s->dev.stackless != 0))
+                return fail(SP_ERR_UNSUPPORTED, "sp_scene_set_lights: the light BVH's depth changes how the resident scene is walked: upload again");
+            if (walk.stackless) a.light_parents = parent_links(a.lbvh.nodes);
+        }
+        h.lights.swap(list);
+        fill_desc(s);
+        if (s->device < 0) return SP_OK;
+        int rc = begin_edit(s);
+        if (rc == SP_OK) rc = upload_lights(s, a);
+        if (rc == SP_OK) {
+            s->sizes.light_depth = a.lbvh.max_depth;
+            apply_walk_plan(s, s->opts, walk);
+        }
+        return end_edit(s, rc);
+    } catch (const std::exception& e) {
+        return end_edit(s, fail(SP_ERR_UNSUPPORTED, std::string("sp_scene_set_lights: ") + e.what()));
+    }
+}
+
+int sp_scene_set_env_image(sp_scene* s, const sp_env_update* u, sp_env_stats* stats)
+{
+    if (!s) return fail(SP_ERR_ARG, "null scene");
+    std::lock_guard<std::mutex> lock(s->mu);
+    SP_TRY(validate_env_update(s, u, stats));
+    sph::Scene& h = *s->host;
+    try {
+        const size_t i        = (size_t)u->image;
+        const bool   pixels   = u->pixels || u->d_pixels;
+        const bool   matrices = !pixels && same_bits(u->max_radiance, h.env_images[i].max_radiance);
+        if (i == h.env_images.size()) h.env_images.emplace_back();
+        sph::EnvImage& e = h.env_images[i];
+        if (pixels) {
+            const size_t n = (size_t)u->width * (size_t)u->height * 3;
+            if (u->pixels) {
+                std::vector<float> px(u->pixels, u->pixels + n); // (a copy first: `pixels` may be the scene's own)
+                e.pixels.swap(px);
+            } else {
+                // the device copy comes back so that the host scene stays the truth
+                std::vector<float> px(n);
+                hipError_t         err = hipSetDevice(s->device);
+                if (err == hipSuccess) err = hipMemcpy(px.data(), u->d_pixels, n * sizeof(float), hipMemcpyDeviceToHost);
+                if (err != hipSuccess) {
+                    (void)hipGetLastError();
+                    if (i + 1 == h.env_images.size() && e.pixels.empty()) h.env_images.pop_back(); // (an append that never was)
+                    return fail(SP_ERR_HIP, std::string("sp_scene_set_env_image: d_pixels: ") + hipGetErrorString(err));
+                }
+                e.pixels.swap(px);
+            }
+            e.width  = u->width;
+            e.height = u->height;
+        }
+        e.max_radiance   = u->max_radiance;
+        e.light_to_world = lin_of(u->light_to_world);
+        e.world_to_light = lin_of(u->world_to_light);
+        fill_desc(s);
+        if (s->device < 0) {
+            fill_env_stats(stats, 0, false, spe::EnvBuildStats{});
+            return SP_OK;
+        }
+        int rc = begin_edit(s);
+        if (rc == SP_OK) rc = relight_env(s, i, static_cast<const float*>(u->d_pixels), matrices, stats);
+        return end_edit(s, rc);
+    } catch (const std::exception& e) {
+        return end_edit(s, fail(SP_ERR_UNSUPPORTED, std::string("sp_scene_set_env_image: ") + e.what()));
+    }
+}
+
+int sp_scene_env_build_check(const sp_scene* s, int32_t image, sp_env_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_env_check)) return fail(SP_ERR_ARG, "sp_env_check.struct_size is not a known size");
+    if (image < 0 || image >= (int32_t)s->host->env_images.size()) return fail(SP_ERR_ARG, "env image out of range");
+    try {
+        const sph::EnvImage& e = s->host->env_images[(size_t)image];
+        fill_env_check(out, e, host_tables(e), SP_ENV_BUILDER_HOST);
+        return SP_OK;
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("env build check failed: ") + e.what());
+    }
+}
+
+int sp_scene_env_check(sp_scene* s, int32_t image, sp_env_check* out)
+{
+    if (!s || !out) return fail(SP_ERR_ARG, "null argument");
+    if (out->struct_size != sizeof(sp_env_check)) return fail(SP_ERR_ARG, "sp_env_check.struct_size is not a known size");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (image < 0 || image >= (int32_t)s->host->env_images.size()) return fail(SP_ERR_ARG, "env image out of range");
+    if (s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
+    try {
+        const sph::EnvImage& e    = s->host->env_images[(size_t)image];
+        const EnvTables      host = host_tables(e);
+        const EnvBlocks&     b    = s->env_blocks[(size_t)image];
+        const spd::EnvMap&   r    = s->env_recs[(size_t)image];
+        SP_HIP(hipSetDevice(s->device));
+        SP_HIP(hipDeviceSynchronize());
+        EnvTables            dev;
+        const DeviceScratch* blocks[SP_ENV_TABLES] = { &b.radiance, &b.cond_func, &b.cond_cdf, &b.cond_int,
+                                                       &b.marg_func, &b.marg_cdf, &b.cond_guide, &b.marg_guide };
+        for (int k = 0; k < SP_ENV_TABLES; ++k) {
+            dev.t[k].resize(blocks[k]->cap / 4);
+            if (blocks[k]->cap) SP_HIP(hipMemcpy(dev.t[k].data(), blocks[k]->ptr, blocks[k]->cap, hipMemcpyDeviceToHost));
+        }
+        dev.guided = b.guided;
+        std::memcpy(&dev.marg_int_bits, &r.marg_int, 4);
+        fill_env_check(out, e, dev, b.builder);
+        auto miss = [&](int table, int64_t index) {
+            if (out->mismatches++ == 0) {
+                out->first_table = table;
+                out->first_index = index;
+            }
+        };
+        for (int k = 0; k < SP_ENV_TABLES; ++k) {
+            const bool guide = k == SP_ENV_COND_GUIDE || k == SP_ENV_MARG_GUIDE;
+            if (guide && !(host.guided && s->opts.env_guide)) { // env_replay, or unguided: the resident scene holds no guides
+                if (!dev.t[k].empty()) miss(k, 0);
+                continue;
+            }
+            if (dev.t[k].size() != host.t[k].size()) {
+                miss(k, (int64_t)std::min(dev.t[k].size(), host.t[k].size()));
+                continue;
+            }
+            for (size_t w = 0; w < dev.t[k].size(); ++w)
+                if (dev.t[k][w] != host.t[k][w]) miss(k, (int64_t)w);
+        }
+        if (dev.guided != host.guided) miss(SP_ENV_SCALARS, 0);
+        if (dev.marg_int_bits != host.marg_int_bits) miss(SP_ENV_SCALARS, 1);
+        if (r.w != e.width || r.h != e.height || r.nu != out->nu || r.nv != out->nv) miss(SP_ENV_SCALARS, 2);
+        if (r.cond_bits != out->cond_bits || r.marg_bits != out->marg_bits) miss(SP_ENV_SCALARS, 3);
+        return SP_OK;
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_UNSUPPORTED, std::string("env check failed: ") + e.what());
+    }
+}
+#undef SP_TRY
+
 // ---- ray queries (sp_query.hip) -----------------------------------------------------------------
 
 // Everything sp_scene_trace_rays refuses, in the header's order; changes nothing.  The scene's
@@ -3471,9 +3954,7 @@ int sp_scene_trace_rays_host(sp_scene* s, int32_t mode, const sp_ray* h_rays, in
 int sp_scene_device_bytes(const sp_scene* s, int64_t* bytes)
 {
     if (!s || !bytes || s->device < 0) return fail(SP_ERR_STATE, "scene not uploaded");
-    int64_t b = 0;
-    for (const auto& d : s->bufs) b += (int64_t)d.cap;
-    *bytes = b;
+    *bytes = (int64_t)s->device_bytes();
     return SP_OK;
 }
 
