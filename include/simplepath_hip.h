@@ -577,8 +577,9 @@ typedef struct sp_build_params_ex {   /* zero-initialise; struct_size = sizeof *
  * partition [0, slots); the wslot_tri codes are a permutation of slot_code; every child's decoded
  * box -- fma(q, step, origin) as the walk decodes it -- contains the exact union of all primitive
  * bounds beneath that child (compared with < and >, so a NaN bound does not count); depth agrees
- * with a walk.  first_error_kind: 1 child range, 2 reached twice, 3 unreachable, 4 hole, 5 meta
- * byte, 6 leaf ranges, 7 record codes, 8 box, 9 depth.  A scene without a wide tree (stackless,
+ * with a walk; every occupied slot's lower quantised byte is <= its upper one on each axis and no
+ * scale byte is 255.  first_error_kind: 1 child range, 2 reached twice, 3 unreachable, 4 hole, 5 meta
+ * byte, 6 leaf ranges, 7 record codes, 8 box, 9 depth, 10 quantised bytes.  A scene without a wide tree (stackless,
  * no_wide_bvh, bvh_mode 1, no bounded primitive) reports records 0 and hash_nodes 0. */
 typedef struct sp_wide_check {        /* struct_size set by the caller */
     uint32_t struct_size;

@@ -147,7 +147,9 @@ __device__ __forceinline__ void camera_item(const Scene& sc, const ChunkArgs& a,
     a.L[((size_t)i * 3 + 1) * a.n_px + p] = L.g;
     a.L[((size_t)i * 3 + 2) * a.n_px + p] = L.b;
 }
-__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK) ck_camera(Scene sc, ChunkArgs a)
+// 5 waves per SIMD (96 VGPRs), where the kernel was before the walks carried two forms of the node visit
+// (sp_path.hpp SP_VISIT_PLAIN): left to itself the allocator takes 102 and drops to 4
+__global__ void __launch_bounds__(64 * WAVES_PER_BLOCK, 5) ck_camera(Scene sc, ChunkArgs a)
 {
     extern __shared__ uint32_t lds[];
     const Lds      l     = lds_setup(sc, lds, true);

@@ -995,6 +995,62 @@ __device__ __forceinline__ WideHits wide_visit(const Scene& sc, uint32_t node, c
     return r;
 }
 
+// SP_VISIT_PLAIN 1 (default): a walk whose wave holds only rays that cannot make a NaN slab distance
+// (spw::plain_ray: finite origin, finite non-zero 1 / d, limits no NaN) visits its nodes with
+// spw::visit_plain -- the same masks, nearest child and t_rest (sp_wide_visit.h states the contract)
+// in about two thirds of the instructions.  The choice is made once per walk by a wave vote, so it is
+// a scalar branch around two straight-line blocks: a lane's answer never depends on the vote, only
+// its speed.  The NAN_SAFE walks (ray queries, callers' own rays) never vote.  0: every walk visits
+// with spw::visit, the code before the plain form (A/B builds and the unit programs' other half).
+#ifndef SP_VISIT_PLAIN
+#define SP_VISIT_PLAIN 1
+#endif
+// true when every active lane's `plain` is: wave-uniform
+__device__ __forceinline__ bool wave_all_plain(bool plain)
+{
+    return __builtin_amdgcn_ballot_w64(!plain) == 0ull;
+}
+__device__ __forceinline__ bool ray_is_plain(const Ray& ray, const f3& inv, float tmin, float tmax)
+{
+    return spw::plain_ray(ray.o.x, ray.o.y, ray.o.z, inv.x, inv.y, inv.z, tmin, tmax);
+}
+// One node visit of a walk: wide_visit's fetch, then the form the walk's wave voted for (`plain` is
+// wave-uniform: a scalar branch inside spw::visit_voted).  SP_XP_VISIT doubles whichever form runs.
+template <bool NAN_SAFE>
+__device__ __forceinline__ WideHits wide_visit_voted(bool plain, const Scene& sc, uint32_t node, const Ray& ray, const f3& inv,
+                                                     float tmin, float tmax)
+{
+#if SP_VISIT_PLAIN
+    if constexpr (!NAN_SAFE) {
+        const uint4*   np = sc.wnodes + 5 * (size_t)node;
+        SP_TD(td_lines(TD_NODE, np, 80));
+#if SP_XP_DUP >= 1
+        uint4 w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3], w4 = np[4];
+        xp_dup(np, w0, w1, w2, w3, w4);
+#else
+        const uint4    w0 = np[0], w1 = np[1], w2 = np[2], w3 = np[3], w4 = np[4];
+#endif
+        const uint32_t w[20] = { w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w,
+                                 w4.x, w4.y, w4.z, w4.w };
+        spw::Visit     v = spw::visit_voted(plain, w, ray.o.x, ray.o.y, ray.o.z, inv.x, inv.y, inv.z, tmin, tmax, 0xffu);
+#if SP_XP_VISIT >= 1
+        {
+            const uint32_t   z = xp_zero();
+            const spw::Visit d = spw::visit_voted(plain, w, __uint_as_float(__float_as_uint(ray.o.x) | z), ray.o.y, ray.o.z, inv.x, inv.y,
+                                                  inv.z, tmin, tmax, 0xffu);
+            v.inner |= d.inner & z; v.leaf |= d.leaf & z; v.nearest |= d.nearest & (int)z;
+            v.t_rest = __uint_as_float(__float_as_uint(v.t_rest) | (__float_as_uint(d.t_rest) & z));
+        }
+#endif
+        WideHits r;
+        r.inner = v.inner; r.leaf = v.leaf; r.nearest = v.nearest; r.t_rest = v.t_rest;
+        r.child_base = w1.x; r.leaf_base = w1.y; r.meta_lo = w1.z; r.meta_hi = w1.w;
+        return r;
+    } else
+#endif
+        return wide_visit<NAN_SAFE>(sc, node, ray, inv, tmin, tmax);
+}
+
 __device__ __forceinline__ uint32_t key_mask(uint32_t m, uint32_t o);
 // occ (walk cache, SP_OCC_CACHE): the wide slot of the primitive that occluded this lane's previous
 // shadow ray.  It is tested first; if it occludes this ray too, the answer (an OR over every
@@ -1013,6 +1069,7 @@ __device__ __forceinline__ bool wide_any(const Scene& sc, const Ray& ray, float 
     if (occ && *occ != 0xffffffffu && prim_any(sc, *occ, ray, tmin, tmax, sc.wslot_tri)) return true;
     const f3       inv = mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
     const uint32_t o   = dir_sign_bits(ray.d);
+    const bool     plain = !NAN_SAFE && SP_VISIT_PLAIN && wave_all_plain(ray_is_plain(ray, inv, tmin, tmax)); // once per walk
     int            sp  = 0;
     uint32_t       node = 0;
     while (true) {
@@ -1022,7 +1079,7 @@ __device__ __forceinline__ bool wide_any(const Scene& sc, const Ray& ray, float 
 #else
 #define SP_WPROF_ANY
 #endif
-        const WideHits wh = wide_visit<NAN_SAFE>(sc, node, ray, inv, tmin, tmax);
+        const WideHits wh = wide_visit_voted<NAN_SAFE>(plain, sc, node, ray, inv, tmin, tmax);
         for (uint32_t m = wh.leaf; m; m &= m - 1) {
             const int      k    = __ffs(m) - 1;
             const uint32_t meta = ((k < 4 ? wh.meta_lo : wh.meta_hi) >> (8 * (k & 3))) & 0xffu;
@@ -1079,13 +1136,15 @@ __device__ __forceinline__ Hit wide_closest(const Scene& sc, const Ray& ray, flo
     const f3       inv = mk(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
     const uint32_t o   = dir_sign_bits(ray.d);
     const int      half = st.depth >> 1;
+    // once per walk; h.t only falls to distances that tri_hit and the shape tests accepted: never a NaN
+    const bool     plain = !NAN_SAFE && SP_VISIT_PLAIN && wave_all_plain(ray_is_plain(ray, inv, tmin, h.t));
     int            sp   = 0;
     uint32_t       node = 0;
     while (true) {
 #ifdef SP_WAVE_PROF
         const uint64_t t_it = __builtin_amdgcn_s_memtime(); // region 6: closest-hit walk steps
 #endif
-        const WideHits wh = wide_visit<NAN_SAFE>(sc, node, ray, inv, tmin, h.t);
+        const WideHits wh = wide_visit_voted<NAN_SAFE>(plain, sc, node, ray, inv, tmin, h.t);
         for (uint32_t m = wh.leaf; m; m &= m - 1) {
             const int      k    = __ffs(m) - 1;
             const uint32_t meta = ((k < 4 ? wh.meta_lo : wh.meta_hi) >> (8 * (k & 3))) & 0xffu;
@@ -1188,6 +1247,22 @@ __device__ __forceinline__ void mq_run(const Scene& sc, Stack st, uint32_t* m, i
     mq_sync();
     const int      half = st.depth >> 1;
     const uint8_t* qs   = reinterpret_cast<const uint8_t*>(m + L::Q);
+    // The plain vote (SP_VISIT_PLAIN), once per pass over every posted query, since a lane walks other
+    // lanes' queries: the rays as posted, 1 / d as `load` computes it, the limits the walks start with
+    // (a closest-hit query's t_max only falls to accepted hit distances afterwards).
+    bool plain_q = true;
+    if (SP_VISIT_PLAIN)
+        for (int i = q; i < total; i += __popcll(act)) { // dealt over the lanes present
+            const uint32_t e  = qs[i];
+            const int      ow = (int)(e & 63u);
+            const bool     an = ANY_ONLY || (e & 128u) != 0u;
+            const f3       po = mq_f3(m, L::O, ow), pd = mq_f3(m, an ? L::D3 : L::D1, ow);
+            float          pmax = k_infinite;
+            if (an) pmax = any_tmax ? mq_f(m, L::AMAX + ow) : k_infinite;
+            else if constexpr (!ANY_ONLY) pmax = __uint_as_float((uint32_t)(*mq_best<L>(m, ow) >> 32));
+            plain_q &= spw::plain_ray(po.x, po.y, po.z, 1.0f / pd.x, 1.0f / pd.y, 1.0f / pd.z, mq_f(m, (an ? L::T3 : L::T1) + ow), pmax);
+        }
+    const bool plain = SP_VISIT_PLAIN && wave_all_plain(plain_q);
     // the lane's walk: query (owner, any), node to visit, its stack [bot, sp)
     Ray      ray;
     f3       inv  = mk(0, 0, 0);
@@ -1241,7 +1316,7 @@ __device__ __forceinline__ void mq_run(const Scene& sc, Stack st, uint32_t* m, i
                 }
             }
             if (has_node) {
-                const WideHits wh    = wide_visit(sc, node, ray, inv, tmin, tmax);
+                const WideHits wh    = wide_visit_voted<false>(plain, sc, node, ray, inv, tmin, tmax);
                 bool           found = false;
                 Hit            h;
                 h.t = tmax; h.code = 0xffffffffu; h.beta = h.gamma = 0.0f; h.slot = 0xffffffffu;

@@ -790,6 +790,10 @@ WideCheck check_wide(const WideBvh& wide, const std::vector<int32_t>& prim_order
         const int      s     = f.slot++;
         const uint32_t imask = w[3] >> 24;
         const uint32_t meta  = (w[6 + s / 4] >> (8 * (s % 4))) & 0xffu;
+        if (s == 0 && ((w[3] & 0xffu) == 0xffu || ((w[3] >> 8) & 0xffu) == 0xffu || ((w[3] >> 16) & 0xffu) == 0xffu)) bad(WIDE_ERR_QUANT, f.rec);
+        if (((imask >> s) & 1u) || meta != 0)
+            for (int a = 0; a < 3; ++a)
+                if (((w[8 + 2 * a + s / 4] >> (8 * (s % 4))) & 0xffu) > ((w[14 + 2 * a + s / 4] >> (8 * (s % 4))) & 0xffu)) { bad(WIDE_ERR_QUANT, f.rec); break; }
         if ((imask >> s) & 1u) {
             const uint64_t c = (uint64_t)w[4] + (uint32_t)s;
             if (c >= nrec) { bad(WIDE_ERR_CHILD_RANGE, f.rec); continue; }

@@ -224,7 +224,8 @@ void refit_wide(WideBvh& wide, const std::vector<PrimBounds>& slot_bounds);
 // bounds (sp_wide_check): what is wrong is counted in `errors`, the first finding kept.
 enum WideError {
     WIDE_ERR_NONE = 0, WIDE_ERR_CHILD_RANGE = 1, WIDE_ERR_VISITED_TWICE = 2, WIDE_ERR_UNREACHABLE = 3, WIDE_ERR_HOLE = 4,
-    WIDE_ERR_META = 5, WIDE_ERR_SLOT_PARTITION = 6, WIDE_ERR_RECORDS = 7, WIDE_ERR_BOX = 8, WIDE_ERR_DEPTH = 9
+    WIDE_ERR_META = 5, WIDE_ERR_SLOT_PARTITION = 6, WIDE_ERR_RECORDS = 7, WIDE_ERR_BOX = 8, WIDE_ERR_DEPTH = 9,
+    WIDE_ERR_QUANT = 10 // what spw::visit_plain relies on (sp_wide_visit.h): qlo <= qhi on occupied slots, scale bytes <= 254
 };
 struct WideCheck {
     int64_t  records = 0, holes = 0, slots = 0;

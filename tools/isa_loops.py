@@ -3,7 +3,9 @@
 instruction to the loop LLVM's comments place its basic block in ("This Loop Header: Depth=d",
 "in Loop: Header=BBx_y").
 
-Usage: python3 tools/isa_loops.py <kernel.s> [loop-header | all]   (with a header: its opcode histogram; all: every loop, not the 30 largest)
+Usage: python3 tools/isa_loops.py <kernel.s> [loop-header | all | blocks]   (with a header: its opcode histogram; all: every loop, not the 30 largest;
+blocks: every basic block that decodes a wide node's bytes -- 40 or more v_cvt_f32_ubyte*, a block of eight of spw::visit or
+spw::visit_plain -- with its loop, its v_max3 / v_min3 count and the canonicalising v_max_f32 x, x it holds, DESIGN.md §30)
 The DirectLighting kernel's ISA: hipcc --offload-arch=gfx950 <the Makefile's flags> -S
 --offload-device-only -c simplepath_amd/csrc/hip/sp_mega_direct.hip, then the lines of
 sp_render_kernel<6, 4>.
@@ -40,8 +42,41 @@ def blocks(lines):
         yield cur, s.split()[0]
 
 
+def visit_blocks(lines):
+    cur = None
+    out = []
+    for l in lines:
+        s = l.strip()
+        if re.match(r"^\.LBB\d+_\d+:|^; %bb\.\d+:", s):
+            cur = {"label": s.split(":")[0].lstrip("; ."), "loop": "-", "c": collections.Counter()}
+            out.append(cur)
+        if cur is not None and (s.startswith(";") or s.startswith(".LBB")):
+            m = re.search(r"Header=(BB\d+_\d+)", s)
+            if m and cur["loop"] == "-":
+                cur["loop"] = m.group(1)
+            continue
+        if cur is None or not s or s.startswith(".") or s.endswith(":"):
+            continue
+        op, c = s.split()[0], cur["c"]
+        c["n"] += 1
+        for key, pre in (("valu", "v_"), ("s_nop", "s_nop"), ("ubyte", "v_cvt_f32_ubyte"), ("v_cmp", "v_cmp"), ("v_cndmask", "v_cndmask"),
+                         ("max3/min3", ("v_max3_f32", "v_min3_f32")), ("max/min", ("v_max_f32", "v_min_f32")), ("scratch", "scratch_")):
+            if op.startswith(pre):
+                c[key] += 1
+        if op.startswith("s_") and not op.startswith("s_nop"):
+            c["salu"] += 1
+        a = [x.strip(",") for x in s.split()[1:4]]
+        if op.startswith("v_max_f32") and len(a) == 3 and a[1] == a[2]:
+            c["canonicalise"] += 1
+    for b in out:
+        if b["c"]["ubyte"] >= 40:
+            print(b["label"], "in loop", b["loop"], dict(b["c"]))
+
+
 def main(path, header=None):
     lines = open(path).read().split("\n")
+    if header == "blocks":
+        return visit_blocks(lines)
     if header and header != "all":
         c = collections.Counter(op for loop, op in blocks(lines) if loop == header)
         for op, n in c.most_common(50):
