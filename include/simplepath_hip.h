@@ -915,6 +915,125 @@ int  sp_scene_radiance_rays(sp_scene* scene, const sp_radiance_query* query, flo
 int  sp_scene_radiance_rays_host(sp_scene* scene, const sp_radiance_query* query /* d_rays ignored */,
                                  const sp_radiance_ray* h_rays, float* h_out, sp_render_stats* stats /* may be NULL */);
 
+/* ---- feature buffers on the render's own camera samples -------------------------------------
+ * Two calls on a resident scene.  sp_scene_camera_rays exports the camera rays a render integrates;
+ * sp_scene_features reduces first-hit features over them, per pixel, in the kernel that makes the
+ * rays: the guide images a denoiser or compositor expects beside a Monte-Carlo frame (albedo,
+ * shading normal, depth, coverage, ids), antialiased exactly as the frame is.
+ *
+ * The camera sample.  Sample i of pixel (x, y) is the reference's RSequenceSampler position
+ * (main.cpp:67, math/Sampler.h:158) through PerspectiveCamera::generate_ray_impl
+ * (Cameras/Camera.h:119): origin = the camera's p, direction normalised by sp::rsqrt.  It depends on
+ * the pixel, the sample index and the camera only -- not on the integrator, the tile list or the
+ * pipeline -- and is, bit for bit, the ray sp_render_tiles integrates for that sample.
+ *
+ * Tiles: the forms of sp_render_tiles -- a host list (checked, copied before return), a device
+ * list (neither; an id outside the frame gives empty pixels), or both NULL for every tile.  One
+ * lane owns one pixel, one wave one list slot; `lane` below is the pixel's Morton index in its tile,
+ * as in the tile-packed image.
+ *
+ * Camera override: `camera`, when given, replaces the scene's camera for this call only.  It is
+ * carried by value in the launch, as the views of sp_render_views are: the scene's camera is neither
+ * read nor changed.  Its film size must be the scene's image size and its floats finite.
+ *
+ * sp_scene_camera_rays writes, for samples [first_sample, first_sample + num_samples), the record
+ * d_rays[(slot * num_samples + s) * 64 + lane] = the ray of sample first_sample + s of that pixel,
+ * with tmin = 0.001f and tmax = FLT_MAX (the integrators' RayLimits).  A lane outside the image
+ * writes an all-zero record, which sp_scene_trace_rays answers as a miss without a walk.  The
+ * records go to sp_scene_trace_rays as they are, and their o and d to sp_scene_radiance_rays.
+ *
+ * sp_scene_features: each pixel's lane loops over its samples i = 0 .. n - 1 and intersects the
+ * camera ray of each with the geometry, by the render's own closest-hit walk with the integrators'
+ * limits.  GEOMETRY ONLY, as a ray query: lights are not intersected, so a sphere light in front of
+ * geometry is not in the buffers.  n is samples_per_pixel, or that slot's entry of tile_samples
+ * (host, copied before return) / d_tile_samples (device) when one of them is given -- what
+ * sp_adaptive_tile_samples returns after adaptive rounds.
+ *
+ * Let H be the samples that hit, in sample order.  All arithmetic is float32 without contraction;
+ * a sum takes its first term as it is and adds the others in order.
+ *   d_ids       4 x int32 per pixel: kind (SP_PRIM_*), index and material of SAMPLE 0's hit as a ray
+ *               query reports them, or -1, -1, -1 when sample 0 misses; the fourth word is |H|
+ *   d_coverage  1 float: (float)|H| / (float)n
+ *   d_depth     1 float: (t_0 + t_1 + ...) over H / (float)|H|; directions are unit vectors, so t
+ *               is the distance from the camera origin
+ *   d_normal    3 floats: the sum over H of the shading normal (what sp_scene_trace_rays' d_normals
+ *               holds) / (float)|H|; not renormalised
+ *   d_albedo    3 floats: the sum over H of a(material) / (float)|H|, a(m)[c] =
+ *               lambert_albedo[c] * 3.14159274f (sp_material_desc holds the albedo over pi); for
+ *               SP_MAT_CLEARCOAT the lambert_albedo of its base material
+ * |H| == 0, n == 0 or a pixel outside the image: every float is +0 and the ids are -1, -1, -1, 0.
+ * Layout: tile-packed like the image, [slot][lane][channels].  Each of the five pointers is
+ * optional, at least one must be given, and work that only an absent output needs is skipped (no
+ * hit is finished when neither normal nor albedo is wanted).  Equal-distance ties resolve as in a
+ * render of this residency; t does not depend on the walk.
+ *
+ * Validation comes first and changes nothing, in this order: null scene or params; struct_size (and
+ * that of stats when given) and reserved words; num_tiles < 0 (and a sample range that ends past
+ * 2^32); the tile-list rules of sp_render_tiles; both tile_samples and d_tile_samples; a camera with
+ * another film size or a non-finite value; no output pointer; a device pointer that is misaligned
+ * (16 bytes for d_rays and d_ids, 4 for the others) -- all SP_ERR_ARG; then a scene that is not
+ * resident, SP_ERR_STATE.  num_tiles == 0 (and num_samples == 0 for the rays) succeeds and launches
+ * nothing.  A BVH whose stacks do not fit the LDS is SP_ERR_UNSUPPORTED as for a render.
+ *
+ * Ordering and locking as sp_scene_trace_rays: the scene's lock; `stream` waits for the previous
+ * call on the scene; with stats == NULL the call only enqueues.  Device lists and outputs must stay
+ * valid until the work has run.  With stats the call waits and fills them.  The calls see what is
+ * resident (a moved mesh, edited materials), leave progress objects valid and keep no memory on the
+ * scene beyond the scratch a render uses.
+ *
+ * The _host forms take host arrays for the outputs (no alignment is asked of them): they allocate
+ * device buffers, copy, run, wait and copy back.  The C++ header (simplepath_amd.hpp) needs no
+ * wrapper for these calls: the structs are used as they are. */
+#define SP_HAS_FEATURES 1
+
+typedef struct sp_camera_ray_params {  /* zero-initialise; struct_size = sizeof */
+    uint32_t              struct_size;       /* a size the library does not know => SP_ERR_ARG */
+    uint32_t              first_sample;      /* the sample index of record s = 0 */
+    uint32_t              num_samples;
+    int32_t               reserved0;         /* must be 0 */
+    const int32_t*        tile_ids;          /* as sp_render_params: host list, or */
+    const int32_t*        d_tile_ids;        /* device list, or both NULL = every tile */
+    int64_t               num_tiles;
+    const sp_camera_desc* camera;            /* HOST, optional: this call's camera */
+    void*                 stream;            /* hipStream_t, NULL = default stream */
+    int32_t               reserved[4];       /* must be 0 */
+} sp_camera_ray_params;                      /* 72 bytes */
+
+typedef struct sp_feature_params {     /* zero-initialise; struct_size = sizeof */
+    uint32_t              struct_size;       /* a size the library does not know => SP_ERR_ARG */
+    uint32_t              samples_per_pixel; /* n of every slot, unless per-tile counts are given */
+    const int32_t*        tile_ids;          /* as sp_render_params: host list, or */
+    const int32_t*        d_tile_ids;        /* device list, or both NULL = every tile */
+    int64_t               num_tiles;
+    const uint32_t*       tile_samples;      /* HOST, one count per slot, or */
+    const uint32_t*       d_tile_samples;    /* DEVICE, or both NULL = samples_per_pixel */
+    const sp_camera_desc* camera;            /* HOST, optional: this call's camera */
+    void*                 stream;            /* hipStream_t, NULL = default stream */
+    int32_t*              d_ids;             /* DEVICE (the _host form: host), 16-byte aligned; 4 words per pixel */
+    float*                d_coverage;        /* 1 float per pixel */
+    float*                d_depth;           /* 1 float per pixel */
+    float*                d_normal;          /* 3 floats per pixel */
+    float*                d_albedo;          /* 3 floats per pixel */
+    int32_t               reserved[4];       /* must be 0 */
+} sp_feature_params;                         /* 120 bytes */
+
+typedef struct sp_feature_stats {      /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  launches;                 /* kernel launches issued (0 when there was nothing to do) */
+    uint64_t camera_rays;              /* features: rays walked (pixels inside the image x their n);
+                                          camera rays: records written */
+    uint64_t hits;                     /* features: the sum of |H| over the pixels; camera rays: 0 */
+    float    kernel_ms;                /* HIP-event time of the kernel */
+    int32_t  stack_depth;              /* LDS traversal-stack words per lane of the closest-hit walk */
+} sp_feature_stats;                    /* 32 bytes */
+
+/* d_rays: DEVICE, num_tiles * num_samples * 64 records, 16-byte aligned */
+int  sp_scene_camera_rays(sp_scene* scene, const sp_camera_ray_params* params, sp_ray* d_rays, sp_feature_stats* stats /* may be NULL */);
+int  sp_scene_camera_rays_host(sp_scene* scene, const sp_camera_ray_params* params, sp_ray* h_rays, sp_feature_stats* stats /* may be NULL */);
+int  sp_scene_features(sp_scene* scene, const sp_feature_params* params, sp_feature_stats* stats /* may be NULL */);
+/* the five output pointers are host arrays; waits for the work */
+int  sp_scene_features_host(sp_scene* scene, const sp_feature_params* params, sp_feature_stats* stats /* may be NULL */);
+
 /* ---- relighting: light, material and sky edits -------------------------------------------------
  * Three calls change what a look-dev session changes most, without a new upload: the materials,
  * the light list, and an image environment light (its pixels, its max_radiance, its rotation).  The

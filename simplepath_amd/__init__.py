@@ -26,7 +26,7 @@ __all__ = [
     "render_tiles_device", "tiles_to_image", "write_pfm", "string_to_integrator_type", "INTEGRATORS",
     "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
     "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays", "camera_look_at", "render_views", "render_views_device",
-    "RADIANCE_RAY_DTYPE", "make_radiance_rays", "pixel_seed",
+    "RADIANCE_RAY_DTYPE", "make_radiance_rays", "pixel_seed", "FEATURE_IDS_DTYPE", "FEATURE_OUTPUTS",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -43,6 +43,11 @@ def string_to_integrator_type(s: str) -> int:
 RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("tmin", "<f4"), ("d", "<f4", (3,)), ("tmax", "<f4")])
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<i4"), ("index", "<i4"), ("material", "<i4"),
                           ("beta", "<f4"), ("gamma", "<f4"), ("reserved", "<u4", (2,))])
+# sp_scene_features' d_ids: sample 0's hit as a ray query reports it, and the pixel's hit count |H|
+FEATURE_IDS_DTYPE = np.dtype([("kind", "<i4"), ("index", "<i4"), ("material", "<i4"), ("hits", "<i4")])
+# the five feature buffers: per pixel shape and dtype, in sp_feature_params order
+FEATURE_OUTPUTS = {"ids": ((64,), FEATURE_IDS_DTYPE), "coverage": ((64,), np.float32), "depth": ((64,), np.float32),
+                   "normal": ((64, 3), np.float32), "albedo": ((64, 3), np.float32)}
 K_RAY_EPSILON = float(np.float32(0.001))      # RayLimits::m_t_min (math/Ray.h:17)
 K_INFINITE = float(np.finfo(np.float32).max)  # RayLimits::m_t_max: k_infinite_distance
 
@@ -491,6 +496,120 @@ class Scene:
         st = _abi.sp_render_stats()
         check(lib().sp_scene_radiance_rays(self._h, C.byref(q), C.c_void_p(out_ptr), C.byref(st)))
         return _stats(st)
+
+    # ---- feature buffers on the render's own camera samples (SP_HAS_FEATURES)
+    def _tile_args(self, p, tile_ids, d_tile_ids=0, num_tiles=0, camera=None, stream=None):
+        """tile list, camera and stream of sp_camera_ray_params / sp_feature_params; returns what
+        must stay alive for the call and the slot count"""
+        keep = None
+        n = (self.width + 7) // 8 * ((self.height + 7) // 8)
+        if tile_ids is not None:
+            keep = np.ascontiguousarray(tile_ids, dtype=np.int32)
+            p.tile_ids = keep.ctypes.data_as(C.POINTER(C.c_int32))
+            p.num_tiles = n = keep.size
+        elif d_tile_ids:
+            p.d_tile_ids = C.c_void_p(d_tile_ids)
+            p.num_tiles = n = int(num_tiles)
+        if camera is not None:
+            p.camera = C.pointer(camera)
+        p.stream = stream
+        return keep, n
+
+    @staticmethod
+    def _feature_stats(call, *args, stats: bool):
+        if not stats:
+            check(call(*args, None))
+            return None
+        st = _abi.sp_feature_stats()
+        st.struct_size = C.sizeof(_abi.sp_feature_stats)
+        check(call(*args, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _abi.sp_feature_stats._fields_ if k != "struct_size"}
+
+    def _camera_ray_params(self, first_sample, num_samples, **tile_args):
+        p = _abi.sp_camera_ray_params()
+        p.struct_size = C.sizeof(_abi.sp_camera_ray_params)
+        p.first_sample = int(first_sample)
+        p.num_samples = int(num_samples)
+        return (p,) + self._tile_args(p, **tile_args)
+
+    def camera_rays(self, tile_ids=None, first_sample: int = 0, num_samples: int = 1, camera=None) -> np.ndarray:
+        """The camera rays a render integrates (sp_scene_camera_rays_host): a RAY_DTYPE array
+        [slots, num_samples, 64] whose record [slot, s, lane] is the ray of sample first_sample + s
+        of that pixel (lane: the pixel's Morton index in its tile, as in the tile-packed image), with
+        the integrators' limits.  Lanes outside the image are all-zero records, which trace()
+        answers as a miss.  tile_ids None: every tile.  camera: a sp_camera_desc for this call only
+        (the scene's camera is neither read nor changed)."""
+        p, keep, n = self._camera_ray_params(first_sample, num_samples, tile_ids=tile_ids, camera=camera)
+        rays = np.zeros((n, int(num_samples), 64), dtype=RAY_DTYPE)
+        check(lib().sp_scene_camera_rays_host(self._h, C.byref(p), C.c_void_p(rays.ctypes.data) if rays.size else None, None))
+        return rays
+
+    def camera_rays_device(self, rays_ptr: int, tile_ids=None, first_sample: int = 0, num_samples: int = 1, camera=None,
+                           stream=None, stats: bool = False, d_tile_ids: int = 0, num_tiles: int = 0):
+        """camera_rays into a device buffer (sp_scene_camera_rays), e.g. a [slots, num_samples, 64, 8]
+        float32 torch tensor's data_ptr() (16-byte aligned, as any torch allocation is).  tile_ids: a
+        host list, or d_tile_ids / num_tiles a device list, or neither for every tile.  With
+        stats=False the call is only enqueued on `stream` (returns None); with stats=True it waits and
+        returns a dict of sp_feature_stats."""
+        p, keep, n = self._camera_ray_params(first_sample, num_samples, tile_ids=tile_ids, d_tile_ids=d_tile_ids,
+                                             num_tiles=num_tiles, camera=camera, stream=stream)
+        return self._feature_stats(lib().sp_scene_camera_rays, self._h, C.byref(p), C.c_void_p(rays_ptr or None), stats=stats)
+
+    def _feature_params(self, samples, tile_samples=None, d_tile_samples=0, **tile_args):
+        p = _abi.sp_feature_params()
+        p.struct_size = C.sizeof(_abi.sp_feature_params)
+        p.samples_per_pixel = int(samples)
+        keep, n = self._tile_args(p, **tile_args)
+        counts = None
+        if tile_samples is not None:
+            counts = np.ascontiguousarray(tile_samples, dtype=np.uint32)
+            if counts.shape != (n,):
+                raise ValueError(f"tile_samples holds {counts.shape} counts for {n} tile slots")
+            p.tile_samples = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        elif d_tile_samples:
+            p.d_tile_samples = C.c_void_p(d_tile_samples)
+        return p, (keep, counts), n
+
+    def features(self, samples: int, tile_ids=None, tile_samples=None, camera=None, outputs=FEATURE_OUTPUTS, stats: bool = False):
+        """First-hit feature buffers on the render's own camera samples (sp_scene_features_host):
+        per pixel, over its samples 0 .. n - 1 and the samples H among them that hit geometry
+        (lights are not intersected), a dict of tile-packed arrays
+          "ids"       [slots, 64] FEATURE_IDS_DTYPE: kind, index, material of sample 0's hit (-1: it
+                      misses) and hits = |H|
+          "coverage"  [slots, 64] float32: |H| / n
+          "depth"     [slots, 64] float32: mean distance over H
+          "normal"    [slots, 64, 3] float32: mean shading normal over H (not renormalised)
+          "albedo"    [slots, 64, 3] float32: mean diffuse albedo over H (a clearcoat's base's)
+        with +0 and (-1, -1, -1, 0) where nothing was hit.  n is `samples`, or tile_samples[slot] when
+        given (Progressive.tile_samples() after adaptive rounds).  outputs: which of the five to
+        compute.  camera: a sp_camera_desc for this call only.  tiles_to_image unpacks normal
+        and albedo.  With stats=True returns (dict, dict of sp_feature_stats)."""
+        outputs = tuple(outputs)
+        if not outputs or any(o not in FEATURE_OUTPUTS for o in outputs):
+            raise ValueError(f"outputs: some of {FEATURE_OUTPUTS}")
+        p, keep, n = self._feature_params(samples, tile_samples, tile_ids=tile_ids, camera=camera)
+        res = {}
+        for name in outputs:
+            shape, dtype = FEATURE_OUTPUTS[name]
+            res[name] = np.zeros((max(n, 1),) + shape, dtype=dtype)
+            setattr(p, "d_" + name, C.c_void_p(res[name].ctypes.data))
+        st = self._feature_stats(lib().sp_scene_features_host, self._h, C.byref(p), stats=stats)
+        res = {k: v[:n] for k, v in res.items()}
+        return (res, st) if stats else res
+
+    def features_device(self, samples: int, ids_ptr: int = 0, coverage_ptr: int = 0, depth_ptr: int = 0, normal_ptr: int = 0,
+                        albedo_ptr: int = 0, tile_ids=None, tile_samples=None, camera=None, stream=None, stats: bool = False,
+                        d_tile_ids: int = 0, num_tiles: int = 0, d_tile_samples: int = 0):
+        """features into device buffers (sp_scene_features), e.g. torch tensors' data_ptr():
+        ids_ptr [slots, 64, 4] int32, coverage_ptr and depth_ptr [slots, 64] float32, normal_ptr and
+        albedo_ptr [slots, 64, 3] float32; any may be 0 (not computed), not all.  tile_samples: host
+        counts, or d_tile_samples a device pointer to one uint32 per slot.  With stats=False the call is
+        only enqueued on `stream` (returns None); host lists are copied before it returns."""
+        p, keep, n = self._feature_params(samples, tile_samples, d_tile_samples, tile_ids=tile_ids, d_tile_ids=d_tile_ids,
+                                          num_tiles=num_tiles, camera=camera, stream=stream)
+        p.d_ids, p.d_coverage, p.d_depth = ids_ptr or None, coverage_ptr or None, depth_ptr or None
+        p.d_normal, p.d_albedo = normal_ptr or None, albedo_ptr or None
+        return self._feature_stats(lib().sp_scene_features, self._h, C.byref(p), stats=stats)
 
     def bvh_info(self):
         d, n, s = C.c_int32(), C.c_int64(), C.c_int64()

@@ -242,6 +242,27 @@ class sp_radiance_query(C.Structure):
                 ("reserved0", C.c_int32), ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class sp_camera_ray_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("first_sample", C.c_uint32), ("num_samples", C.c_uint32),
+                ("reserved0", C.c_int32), ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p),
+                ("num_tiles", C.c_int64), ("camera", C.POINTER(sp_camera_desc)), ("stream", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class sp_feature_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("samples_per_pixel", C.c_uint32),
+                ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
+                ("tile_samples", C.POINTER(C.c_uint32)), ("d_tile_samples", C.c_void_p),
+                ("camera", C.POINTER(sp_camera_desc)), ("stream", C.c_void_p),
+                ("d_ids", C.c_void_p), ("d_coverage", C.c_void_p), ("d_depth", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_albedo", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class sp_feature_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_int32), ("camera_rays", C.c_uint64), ("hits", C.c_uint64),
+                ("kernel_ms", C.c_float), ("stack_depth", C.c_int32)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -328,6 +349,11 @@ SIGNATURES = {
     "sp_scene_radiance_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_radiance_query), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_scene_radiance_rays_host": (C.c_int, [C.c_void_p, C.POINTER(sp_radiance_query), C.c_void_p, C.c_void_p,
                                               C.POINTER(sp_render_stats)]),
+    "sp_scene_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(sp_camera_ray_params), C.c_void_p, C.POINTER(sp_feature_stats)]),
+    "sp_scene_camera_rays_host": (C.c_int, [C.c_void_p, C.POINTER(sp_camera_ray_params), C.c_void_p,
+                                            C.POINTER(sp_feature_stats)]),
+    "sp_scene_features": (C.c_int, [C.c_void_p, C.POINTER(sp_feature_params), C.POINTER(sp_feature_stats)]),
+    "sp_scene_features_host": (C.c_int, [C.c_void_p, C.POINTER(sp_feature_params), C.POINTER(sp_feature_stats)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

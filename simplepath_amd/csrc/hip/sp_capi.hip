@@ -10,6 +10,7 @@
 #include "sp_finish.hpp"
 #include "sp_refit.hpp"
 #include "sp_query.hpp"
+#include "sp_features.hpp"
 #include "sp_envbuild.hpp"
 #include "../common/sp_refit.h"
 #include "../common/sp_sah.h"
@@ -3948,6 +3949,274 @@ int sp_scene_trace_rays_host(sp_scene* s, int32_t mode, const sp_ray* h_rays, in
         return trace_rays_host_impl(s, mode, h_rays, num_rays, h_hits, h_normals, h_occluded, stats);
     } catch (const std::exception& e) {
         return fail(SP_ERR_HIP, std::string("ray query failed: ") + e.what());
+    }
+}
+
+// ---- feature buffers (SP_HAS_FEATURES; sp_features.hip) ------------------------------------------
+
+// What the two calls share of their parameters: the tile list and the optional camera.
+struct FeatureCommon {
+    const int32_t*        tile_ids;
+    const int32_t*        d_tile_ids;
+    int64_t               num_tiles;
+    const sp_camera_desc* camera;
+};
+
+// The shared refusals between "negative counts" and "no output pointer"; fills the tile list.  The
+// tile count is the host scene's (the resident one's is equal), so the rules hold before any upload.
+static int validate_feature_common(const sp_scene* s, const FeatureCommon& c, TileList& tiles)
+{
+    if (c.tile_ids && c.d_tile_ids) return fail(SP_ERR_ARG, "give tile_ids (host) or d_tile_ids (device), not both");
+    sp_tile_count(s->host->image_width, s->host->image_height, &tiles.total);
+    tiles.listed = c.tile_ids || c.d_tile_ids;
+    tiles.n      = tiles.listed ? c.num_tiles : tiles.total;
+    if (int rc = check_tile_list(tiles, c.tile_ids)) return rc;
+    if (c.camera) {
+        if (c.camera->film_width != s->host->image_width || c.camera->film_height != s->host->image_height)
+            return fail(SP_ERR_ARG, "the camera's film size is not the scene's image size");
+        if (!camera_finite(*c.camera)) return fail(SP_ERR_ARG, "the camera's transform is not finite");
+    }
+    return SP_OK;
+}
+
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+static int check_feature_stats(const sp_feature_stats* stats)
+{
+    if (stats && stats->struct_size != sizeof(sp_feature_stats))
+        return fail(SP_ERR_ARG, "sp_feature_stats.struct_size is not this library's");
+    return SP_OK;
+}
+
+// Everything sp_scene_camera_rays refuses, in the header's order; changes nothing.  The scene's lock
+// is held (s->device is read last).  device_pointers: the alignment rule of a device buffer.
+static int validate_camera_rays(const sp_scene* s, const sp_camera_ray_params* p, const sp_ray* rays, const sp_feature_stats* stats,
+                                bool device_pointers, TileList& tiles)
+{
+    if (p->struct_size != sizeof(sp_camera_ray_params)) return fail(SP_ERR_ARG, "sp_camera_ray_params.struct_size is not this library's");
+    if (int rc = check_feature_stats(stats)) return rc;
+    if (p->reserved0 != 0) return fail(SP_ERR_ARG, "sp_camera_ray_params.reserved must be 0");
+    for (int32_t r : p->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_camera_ray_params.reserved must be 0");
+    if (p->num_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
+    if ((uint64_t)p->first_sample + p->num_samples > ((uint64_t)1 << 32)) return fail(SP_ERR_ARG, "the sample range ends past 2^32");
+    if (int rc = validate_feature_common(s, FeatureCommon{ p->tile_ids, p->d_tile_ids, p->num_tiles, p->camera }, tiles)) return rc;
+    if (tiles.n > 0 && p->num_samples > 0 && !rays) return fail(SP_ERR_ARG, "no output pointer");
+    if (device_pointers && misaligned(rays, 16)) return fail(SP_ERR_ARG, "d_rays must be 16-byte aligned");
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_scene_camera_rays");
+    return SP_OK;
+}
+
+// the resident scene with this call's camera (by value in the launch)
+static spd::Scene feature_scene(const sp_scene* s, const sp_camera_desc* camera)
+{
+    spd::Scene sc = s->dev;
+    if (camera) sc.camera = from_desc(camera->transform);
+    return sc;
+}
+
+static void feature_stats_begin(const sp_scene* s, sp_feature_stats* stats)
+{
+    if (!stats) return;
+    *stats             = sp_feature_stats{};
+    stats->struct_size = sizeof(sp_feature_stats);
+    stats->stack_depth = s->dev.stack_words;
+}
+
+static int camera_rays_impl(sp_scene* s, const sp_camera_ray_params* p, sp_ray* d_rays, sp_feature_stats* stats, bool device_pointers)
+{
+    TileList tiles;
+    if (int rc = validate_camera_rays(s, p, d_rays, stats, device_pointers, tiles)) return rc;
+    feature_stats_begin(s, stats);
+    if (tiles.n == 0 || p->num_samples == 0) return SP_OK;
+    const int64_t items = tiles.n * (int64_t)p->num_samples; // (tiles.n < 2^31: the ids are int32)
+    if (items > (int64_t)INT32_MAX * 4) return fail(SP_ERR_UNSUPPORTED, "more (tile, sample) items than one launch takes");
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch&    r      = s->scratch;
+    const hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    // the previous call on this scene (a render, a refit's successor, a query) comes first
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    spd::CameraRayArgs a{};
+    a.tile_ids = p->d_tile_ids;
+    if (p->tile_ids)
+        if (int rc = stage_ids(s, p->tile_ids, tiles.n, stream, a.tile_ids)) return rc;
+    a.num_tiles    = tiles.n;
+    a.tiles_x      = (s->dev.width + 7) / 8;
+    a.first_sample = p->first_sample;
+    a.num_samples  = p->num_samples;
+    a.rays         = d_rays;
+    SP_HIP(hipEventRecord(r.ev0, stream));
+    SP_HIP(spd::launch_camera_rays(feature_scene(s, p->camera), a, stream));
+    if (int rc = end_call(s, stream)) return rc;
+    if (!stats) return SP_OK; // stream order: only enqueued
+    SP_HIP(hipEventSynchronize(r.ev1));
+    SP_HIP(hipEventElapsedTime(&stats->kernel_ms, r.ev0, r.ev1));
+    stats->launches    = 1;
+    stats->camera_rays = (uint64_t)items * 64;
+    return SP_OK;
+}
+
+int sp_scene_camera_rays(sp_scene* s, const sp_camera_ray_params* p, sp_ray* d_rays, sp_feature_stats* stats)
+{
+    if (!s || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // calls on one scene run one at a time (sp_scene::mu)
+    try {
+        return camera_rays_impl(s, p, d_rays, stats, true);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_camera_rays failed: ") + e.what());
+    }
+}
+
+// the host form with the scene's lock held: the same refusals in the same order on the host array
+// as given, then a device buffer of its own around the device form (trace_rays_host_impl's pattern)
+static int camera_rays_host_impl(sp_scene* s, const sp_camera_ray_params* p, sp_ray* h_rays, sp_feature_stats* stats)
+{
+    TileList tiles;
+    if (int rc = validate_camera_rays(s, p, h_rays, stats, false, tiles)) return rc;
+    SP_HIP(hipSetDevice(s->device));
+    const size_t  bytes = (size_t)tiles.n * p->num_samples * 64 * sizeof(sp_ray);
+    DeviceScratch d_rays;
+    if (bytes) SP_HIP(d_rays.reserve(bytes));
+    sp_camera_ray_params dp = *p;
+    dp.stream               = nullptr; // with the blocking copy below, as render_to_host
+    if (int rc = camera_rays_impl(s, &dp, d_rays.as<sp_ray>(), stats, true)) return rc;
+    if (bytes) SP_HIP(hipMemcpy(h_rays, d_rays.ptr, bytes, hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_scene_camera_rays_host(sp_scene* s, const sp_camera_ray_params* p, sp_ray* h_rays, sp_feature_stats* stats)
+{
+    if (!s || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // residency is decided, and kept, under the scene's lock
+    try {
+        return camera_rays_host_impl(s, p, h_rays, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_camera_rays_host failed: ") + e.what());
+    }
+}
+
+// Everything sp_scene_features refuses, in the header's order; changes nothing (validate_camera_rays)
+static int validate_features(const sp_scene* s, const sp_feature_params* p, const sp_feature_stats* stats, bool device_pointers,
+                             TileList& tiles)
+{
+    if (p->struct_size != sizeof(sp_feature_params)) return fail(SP_ERR_ARG, "sp_feature_params.struct_size is not this library's");
+    if (int rc = check_feature_stats(stats)) return rc;
+    for (int32_t r : p->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_feature_params.reserved must be 0");
+    if (p->num_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
+    if (int rc = validate_feature_common(s, FeatureCommon{ p->tile_ids, p->d_tile_ids, p->num_tiles, p->camera }, tiles)) return rc;
+    if (p->tile_samples && p->d_tile_samples) return fail(SP_ERR_ARG, "give tile_samples (host) or d_tile_samples (device), not both");
+    if (!p->d_ids && !p->d_coverage && !p->d_depth && !p->d_normal && !p->d_albedo) return fail(SP_ERR_ARG, "no output pointer");
+    if (device_pointers) {
+        if (misaligned(p->d_ids, 16)) return fail(SP_ERR_ARG, "d_ids must be 16-byte aligned");
+        if (misaligned(p->d_coverage, 4) || misaligned(p->d_depth, 4) || misaligned(p->d_normal, 4) || misaligned(p->d_albedo, 4) ||
+            misaligned(p->d_tile_samples, 4) || misaligned(p->d_tile_ids, 4))
+            return fail(SP_ERR_ARG, "d_coverage, d_depth, d_normal, d_albedo and the device lists must be 4-byte aligned");
+    }
+    if (s->device < 0) return fail(SP_ERR_STATE, "sp_scene_upload must be called before sp_scene_features");
+    return SP_OK;
+}
+
+// after validate_features, with the scene's lock held
+static int features_impl(sp_scene* s, const sp_feature_params* p, sp_feature_stats* stats, const TileList& tiles)
+{
+    feature_stats_begin(s, stats);
+    if (tiles.n == 0) return SP_OK;
+    const size_t lds_bytes = spd::feature_lds_bytes(s->dev);
+    if (lds_bytes > 160 * 1024) return fail(SP_ERR_UNSUPPORTED, "BVH too deep for the LDS traversal stack");
+    SP_HIP(hipSetDevice(s->device));
+    RenderScratch&    r      = s->scratch;
+    const hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    // the previous call on this scene (a render, a refit's successor, a query) comes first
+    if (r.done_rec) SP_HIP(hipStreamWaitEvent(stream, r.ev_done, 0));
+    spd::FeatureArgs a{};
+    a.tile_ids     = p->d_tile_ids;
+    a.tile_samples = p->d_tile_samples;
+    // host lists go through one staging buffer of the ring: [tile ids][sample counts]
+    if (p->tile_ids || p->tile_samples) {
+        const size_t         n = (size_t)tiles.n;
+        std::vector<int32_t> both;
+        if (p->tile_ids) both.insert(both.end(), p->tile_ids, p->tile_ids + n);
+        if (p->tile_samples) both.insert(both.end(), reinterpret_cast<const int32_t*>(p->tile_samples),
+                                         reinterpret_cast<const int32_t*>(p->tile_samples) + n);
+        const int32_t* d_both = nullptr;
+        if (int rc = stage_ids(s, both.data(), (int64_t)both.size(), stream, d_both)) return rc;
+        if (p->tile_ids) a.tile_ids = d_both;
+        if (p->tile_samples) a.tile_samples = reinterpret_cast<const uint32_t*>(d_both + (p->tile_ids ? n : 0));
+    }
+    a.num_tiles = tiles.n;
+    a.tiles_x   = (s->dev.width + 7) / 8;
+    a.spp       = p->samples_per_pixel;
+    a.ids       = reinterpret_cast<int4*>(p->d_ids);
+    a.coverage  = p->d_coverage;
+    a.depth     = p->d_depth;
+    a.normal    = p->d_normal;
+    a.albedo    = p->d_albedo;
+    if (stats) { // counted only when asked for: words 5 and 6 of the render counters, which every call clears for itself
+        a.counters = r.counters.as<unsigned long long>() + 5;
+        SP_HIP(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), stream));
+    }
+    SP_HIP(hipEventRecord(r.ev0, stream));
+    SP_HIP(spd::launch_features(feature_scene(s, p->camera), a, lds_bytes, stream));
+    if (int rc = end_call(s, stream)) return rc;
+    if (!stats) return SP_OK; // stream order: only enqueued
+    SP_HIP(hipEventSynchronize(r.ev1));
+    unsigned long long c[2] = { 0, 0 };
+    SP_HIP(hipMemcpy(c, a.counters, sizeof(c), hipMemcpyDeviceToHost));
+    SP_HIP(hipEventElapsedTime(&stats->kernel_ms, r.ev0, r.ev1));
+    stats->launches    = 1;
+    stats->camera_rays = c[0];
+    stats->hits        = c[1];
+    return SP_OK;
+}
+
+int sp_scene_features(sp_scene* s, const sp_feature_params* p, sp_feature_stats* stats)
+{
+    if (!s || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // calls on one scene run one at a time (sp_scene::mu)
+    try {
+        TileList tiles;
+        if (int rc = validate_features(s, p, stats, true, tiles)) return rc;
+        return features_impl(s, p, stats, tiles);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_features failed: ") + e.what());
+    }
+}
+
+// the host form with the scene's lock held: the same refusals in the same order on the host arrays
+// as given, then device buffers of its own around the device form (trace_rays_host_impl's pattern)
+static int features_host_impl(sp_scene* s, const sp_feature_params* p, sp_feature_stats* stats)
+{
+    TileList tiles;
+    if (int rc = validate_features(s, p, stats, false, tiles)) return rc;
+    SP_HIP(hipSetDevice(s->device));
+    const size_t      px = (size_t)tiles.n * 64;
+    void* const       host[5]  = { p->d_ids, p->d_coverage, p->d_depth, p->d_normal, p->d_albedo };
+    const size_t      bytes[5] = { px * 16, px * 4, px * 4, px * 12, px * 12 };
+    DeviceScratch     dev[5];
+    for (int k = 0; k < 5; ++k)
+        if (host[k]) SP_HIP(dev[k].reserve(std::max<size_t>(bytes[k], 16)));
+    sp_feature_params dp = *p;
+    dp.d_ids      = dev[0].as<int32_t>();
+    dp.d_coverage = dev[1].as<float>();
+    dp.d_depth    = dev[2].as<float>();
+    dp.d_normal   = dev[3].as<float>();
+    dp.d_albedo   = dev[4].as<float>();
+    dp.stream     = nullptr; // with the blocking copies below, as render_to_host
+    if (int rc = features_impl(s, &dp, stats, tiles)) return rc;
+    for (int k = 0; k < 5; ++k)
+        if (host[k] && bytes[k]) SP_HIP(hipMemcpy(host[k], dev[k].ptr, bytes[k], hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_scene_features_host(sp_scene* s, const sp_feature_params* p, sp_feature_stats* stats)
+{
+    if (!s || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(s->mu); // residency is decided, and kept, under the scene's lock
+    try {
+        return features_host_impl(s, p, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_scene_features_host failed: ") + e.what());
     }
 }
 
