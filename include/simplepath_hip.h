@@ -1034,6 +1034,134 @@ int  sp_scene_features(sp_scene* scene, const sp_feature_params* params, sp_feat
 /* the five output pointers are host arrays; waits for the work */
 int  sp_scene_features_host(sp_scene* scene, const sp_feature_params* params, sp_feature_stats* stats /* may be NULL */);
 
+/* ---- denoising: the edge-avoiding a-trous wavelet filter on tile-packed frames -------------------
+ * A scene-free object: the filter is an image operator and reads nothing of a scene.  It consumes
+ * what sp_render_tiles and sp_scene_features write -- tile-packed [slot][lane][channels], lane = the
+ * pixel's Morton index in its 8x8 tile, tile id = ty * tiles_x + tx -- in place on the device, in
+ * stream order.  A 5x5 B3-spline kernel is applied with steps 1, 2, 4, ...; colour, normal, depth
+ * and coverage differences stop it at edges; the albedo is divided out before and multiplied back
+ * after, so textures and material colour are not blurred.
+ *
+ * THE RULE.  All arithmetic is float32 with no contraction, in the operand order written.  p is a
+ * pixel inside the image that belongs to a listed tile slot; its inputs are c_p[3] (colour), a_p[3]
+ * (albedo), n_p[3] (normal), z_p (depth), k_p (coverage).
+ *
+ * Prepare.  With SP_DENOISE_DEMODULATE (needs d_albedo and d_coverage), per channel
+ *     s = (k_p * a_p[ch]) + (1.0f - k_p)
+ *     m_p[ch] = s > albedo_floor ? s : albedo_floor          (a NaN gives the floor)
+ *     x0_p[ch] = c_p[ch] / m_p[ch]
+ * without the flag x0_p = c_p and m is unused.
+ *     g_p = 1.0f / (sigma_depth * (z_p > depth_floor ? z_p : depth_floor))
+ *
+ * Level i = 0 .. iterations - 1, constants computed once on the host in float32:
+ *     step s = 1 << i;  sc = sigma_color * 2^-i (exact scaling);  inv_c = 1.0f / (sc * sc)
+ *     inv_n = 1.0f / (sigma_normal * sigma_normal);  inv_k = 1.0f / (sigma_coverage * sigma_coverage)
+ * Taps (dx, dy) in {-2..2}^2, dy the outer loop from -2, dx the inner loop from -2; the tap pixel is
+ * q = (x + dx*s, y + dy*s).  A tap is skipped when q is outside the image or q's tile is not in the
+ * list.  h = {1/16, 1/4, 3/8, 1/4, 1/16}, h2 = h[dx+2] * h[dy+2] (exact).  The four edge terms:
+ *     d = x_q - x_p per channel;  ec = ((d0*d0 + d1*d1) + d2*d2) * inv_c
+ *     d = n_q - n_p;              en = ((d0*d0 + d1*d1) + d2*d2) * inv_n
+ *     dz = (z_q - z_p) * g_p;     ed = dz * dz
+ *     dk = k_q - k_p;             ek = (dk * dk) * inv_k
+ * A term whose guide pointer is NULL contributes +0 (every term is >= 0 or NaN, so the bits of the
+ * sum are those of the sum without it).
+ *     e = ((ec + en) + ed) + ek;   w = h2 * expf(-e)   (glibc's expf, bit for bit: lm_expf)
+ * The tap counts only if w > 0 (NaN and 0 fail the comparison).  acc[ch] and W start at +0; for
+ * each counted tap, in tap order, acc[ch] = acc[ch] + w * x_q[ch] and W = W + w.  Then
+ *     x(i+1)_p[ch] = W > 0 ? acc[ch] / W : x(i)_p[ch]
+ * Consequences: a NaN or infinite colour never spreads to its neighbours (its taps have e = NaN or
+ * +inf, so w is NaN or 0), and a non-finite centre pixel passes through unchanged (none of its taps
+ * counts, so W = 0).
+ *
+ * Finish.  out_p[ch] = x(L)_p[ch] * m_p[ch] with demodulation, x(L)_p[ch] without.  Lanes of a
+ * listed tile that lie outside the image write +0.
+ *
+ * Parameters.  iterations 1 .. 8; sigma_color finite and > 0; sigma_normal, sigma_depth and
+ * sigma_coverage finite and > 0 wherever their guide is given (not looked at otherwise);
+ * albedo_floor and depth_floor finite and >= 0, 0 meaning 0.01f and 1e-3f (conventions, not
+ * measurements).
+ *
+ * THE OBJECT.  sp_denoiser_create takes the device, the frame size and the tile list in the three
+ * forms of sp_render_tiles: a host list (checked: an id out of range or a repeated id is SP_ERR_ARG;
+ * copied before return), a device list, or neither for every tile.  It touches no device: the
+ * object's memory -- two ping-pong planes of 16 bytes per pixel slot (x and z), a packed guide
+ * record of 16 bytes per pixel slot (n and k), its own copy of the list, and the inverse map
+ * slot_of_tile[tiles_x * tiles_y] (-1: absent) built by a small kernel -- is allocated and filled
+ * by the object's first run, on that run's stream, ahead of its kernels.  A device list is read
+ * then and not afterwards: it must hold the ids until the first run has executed.  In a device list
+ * an id outside the frame makes that slot's outputs +0, and a repeated id is served to taps from
+ * its lowest slot (atomicMin): every tap, the centre one included, reads q through the map, while
+ * x_p, n_p, z_p, k_p are the slot's own; the result is deterministic.
+ * sp_denoiser_device_bytes is what the object holds once it has run.
+ *
+ * sp_denoiser_run: d_color and d_out are required, [num_tiles][64][3] floats; d_albedo and d_normal
+ * [num_tiles][64][3], d_depth and d_coverage [num_tiles][64], each optional.  d_out may equal
+ * d_color; d_out may overlap no input in any other way.  The call is enqueued on `stream`.  It
+ * waits only for the object's own previous run (the scratch is reused); ORDERING AGAINST THE CALLS
+ * THAT PRODUCE THE INPUTS IS ORDINARY STREAM ORDER: enqueue sp_render_tiles, sp_scene_features and
+ * this call on one stream, or order the streams with events.  Inputs and output must stay valid
+ * until the work has run.  With stats == NULL the call only enqueues; with stats it waits and
+ * fills them.  Launches: one prepare kernel, one per level, the finish fused into the last level
+ * (the first run adds the map's).  sp_denoiser_run_host takes host arrays in the same fields (no
+ * alignment is asked of them), allocates device buffers, copies, runs, waits and copies back.
+ * Calls on one object run one at a time (the object's lock).
+ *
+ * Validation comes first and changes nothing, in this order: null arguments; struct_size values
+ * (that of stats when given), reserved words and unknown flags; counts (width or height < 1, device
+ * < 0, num_tiles < 0 or above 2^31 - 1) and the tile-list rules; iterations out of range, then a
+ * sigma or a floor out of range; a missing d_color or d_out, then the demodulate flag without
+ * d_albedo or d_coverage; a device pointer not 4-byte aligned, then a forbidden overlap -- all
+ * SP_ERR_ARG with a message naming the field.  Only then device errors, SP_ERR_HIP.  num_tiles == 0
+ * succeeds and launches nothing. */
+#define SP_HAS_DENOISE 1
+#define SP_DENOISE_DEMODULATE 1            /* sp_denoise_params.flags */
+#define SP_DENOISE_MAX_ITERATIONS 8
+
+typedef struct sp_denoiser sp_denoiser;
+
+typedef struct sp_denoiser_params {    /* zero-initialise; struct_size = sizeof */
+    uint32_t       struct_size;        /* a size the library does not know => SP_ERR_ARG */
+    int32_t        device;
+    int32_t        width, height;      /* the frame, in pixels */
+    const int32_t* tile_ids;           /* as sp_render_params: host list, or */
+    const int32_t* d_tile_ids;         /* device list, or both NULL = every tile */
+    int64_t        num_tiles;
+    int32_t        reserved[4];        /* must be 0 */
+} sp_denoiser_params;                  /* 56 bytes */
+
+typedef struct sp_denoise_params {     /* zero-initialise; struct_size = sizeof */
+    uint32_t     struct_size;          /* a size the library does not know => SP_ERR_ARG */
+    int32_t      iterations;           /* 1 .. SP_DENOISE_MAX_ITERATIONS */
+    int32_t      flags;                /* SP_DENOISE_DEMODULATE or 0; anything else SP_ERR_ARG */
+    int32_t      reserved0;            /* must be 0 */
+    const float* d_color;              /* DEVICE (the _host form: host), 3 floats per pixel */
+    const float* d_albedo;             /* 3 floats per pixel, optional */
+    const float* d_normal;             /* 3 floats per pixel, optional */
+    const float* d_depth;              /* 1 float per pixel, optional */
+    const float* d_coverage;           /* 1 float per pixel, optional */
+    float*       d_out;                /* 3 floats per pixel; may equal d_color */
+    float        sigma_color, sigma_normal, sigma_depth, sigma_coverage;
+    float        albedo_floor, depth_floor; /* 0: 0.01f and 1e-3f */
+    void*        stream;               /* hipStream_t, NULL = default stream */
+    int32_t      reserved[4];          /* must be 0 */
+} sp_denoise_params;                   /* 112 bytes */
+
+typedef struct sp_denoise_stats {      /* struct_size set by the caller */
+    uint32_t struct_size;
+    int32_t  launches;                 /* kernel launches issued (0 when there was nothing to do) */
+    uint64_t pixels;                   /* pixels inside the image, over the listed slots */
+    uint64_t taps;                     /* counted taps (w > 0), summed over levels and pixels */
+    float    kernel_ms;                /* HIP-event time of the run's kernels */
+    int32_t  reserved;
+} sp_denoise_stats;                    /* 32 bytes */
+
+int  sp_denoiser_create(const sp_denoiser_params* params, sp_denoiser** out);
+void sp_denoiser_free(sp_denoiser* denoiser);
+int  sp_denoiser_device_bytes(const sp_denoiser* denoiser, int64_t* out);
+int  sp_denoiser_run(sp_denoiser* denoiser, const sp_denoise_params* params, sp_denoise_stats* stats /* may be NULL */);
+/* the six buffer pointers are host arrays; waits for the work */
+int  sp_denoiser_run_host(sp_denoiser* denoiser, const sp_denoise_params* params, sp_denoise_stats* stats /* may be NULL */);
+
 /* ---- relighting: light, material and sky edits -------------------------------------------------
  * Three calls change what a look-dev session changes most, without a new upload: the materials,
  * the light list, and an image environment light (its pixels, its max_radiance, its rotation).  The

@@ -27,6 +27,7 @@ __all__ = [
     "SimplePathError", "k_tile_dimension", "rsqrt_table", "set_rsqrt_table", "Progressive", "PIXEL_STATE_DTYPE", "PIXEL_NOISE_DTYPE", "AdaptiveResult",
     "RAY_DTYPE", "RAY_HIT_DTYPE", "make_rays", "camera_look_at", "render_views", "render_views_device",
     "RADIANCE_RAY_DTYPE", "make_radiance_rays", "pixel_seed", "FEATURE_IDS_DTYPE", "FEATURE_OUTPUTS",
+    "Denoiser", "DENOISE_GUIDES",
 ]
 
 k_tile_dimension = 8  # base/Tile.h:10
@@ -999,6 +1000,137 @@ class Progressive:
         keep = c if c.size else np.zeros(1, dtype=np.uint32)
         check(lib().sp_adaptive_import(self._h, C.c_void_p(a.ctypes.data), a.size,
                                        keep.ctypes.data_as(C.POINTER(C.c_uint32)), c.size))
+
+
+# the denoiser's optional guide buffers: floats per pixel, in sp_denoise_params order
+DENOISE_GUIDES = {"albedo": 3, "normal": 3, "depth": 1, "coverage": 1}
+
+
+class Denoiser:
+    """Edge-avoiding a-trous wavelet filter on tile-packed frames (sp_denoiser; the rule is in
+    include/simplepath_hip.h): a 5x5 B3-spline kernel at steps 1, 2, 4, ... that colour, normal, depth
+    and coverage differences stop at edges, with the albedo divided out before and multiplied back
+    after.  Scene-free: it takes the frame size and the tile list a render used, and the buffers
+    render_tiles and Scene.features write, as they are.
+
+        with Denoiser.for_scene(scene) as dn:
+            noisy, _ = render_tiles(scene, "direct_lighting", 8)
+            clean = dn.run(noisy, **scene.features(8))
+            img = tiles_to_image(scene.width, scene.height, clean)
+
+    tile_ids: a host list (no repeats), or d_tile_ids / num_tiles a device list, or neither for every
+    tile.  Holds 48 bytes of device memory per pixel slot from its first run until close()."""
+
+    def __init__(self, width: int, height: int, tile_ids: Optional[Sequence[int]] = None, d_tile_ids: int = 0,
+                 num_tiles: int = 0, device: int = 0):
+        p = _abi.sp_denoiser_params()
+        p.struct_size = C.sizeof(_abi.sp_denoiser_params)
+        p.device, p.width, p.height = int(device), int(width), int(height)
+        self.num_tiles = (int(width) + 7) // 8 * ((int(height) + 7) // 8)
+        keep = None
+        if tile_ids is not None:
+            keep = np.ascontiguousarray(np.asarray(tile_ids), dtype=np.int32)
+            p.tile_ids = keep.ctypes.data_as(C.POINTER(C.c_int32))
+            p.num_tiles = self.num_tiles = keep.size
+        elif d_tile_ids:
+            p.d_tile_ids = C.c_void_p(d_tile_ids)
+            p.num_tiles = self.num_tiles = int(num_tiles)
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        check(lib().sp_denoiser_create(C.byref(p), C.byref(self._h)))
+
+    @classmethod
+    def for_scene(cls, scene: Scene, tile_ids: Optional[Sequence[int]] = None, device: int = 0) -> "Denoiser":
+        """a denoiser for the scene's frame size"""
+        return cls(scene.width, scene.height, tile_ids=tile_ids, device=device)
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h and _abi._lib is not None:
+            _abi._lib.sp_denoiser_free(h)
+        self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    @property
+    def device_bytes(self) -> int:
+        b = C.c_int64()
+        check(lib().sp_denoiser_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    @staticmethod
+    def _params(iterations, sigma_color, sigma_normal, sigma_depth, sigma_coverage, albedo_floor, depth_floor, demodulate,
+                stream=None):
+        p = _abi.sp_denoise_params()
+        p.struct_size = C.sizeof(_abi.sp_denoise_params)
+        p.iterations = int(iterations)
+        p.flags = _abi.SP_DENOISE_DEMODULATE if demodulate else 0
+        p.sigma_color, p.sigma_normal, p.sigma_depth = float(sigma_color), float(sigma_normal), float(sigma_depth)
+        p.sigma_coverage, p.albedo_floor, p.depth_floor = float(sigma_coverage), float(albedo_floor), float(depth_floor)
+        p.stream = stream
+        return p
+
+    @staticmethod
+    def _stats(call, h, p, stats: bool):
+        if not stats:
+            check(call(h, C.byref(p), None))
+            return None
+        st = _abi.sp_denoise_stats()
+        st.struct_size = C.sizeof(_abi.sp_denoise_stats)
+        check(call(h, C.byref(p), C.byref(st)))
+        return {k: getattr(st, k) for k in ("launches", "pixels", "taps", "kernel_ms")}
+
+    def run(self, color, albedo=None, normal=None, depth=None, coverage=None, iterations: int = 5, sigma_color: float = 0.6,
+            sigma_normal: float = 0.3, sigma_depth: float = 0.2, sigma_coverage: float = 0.4, albedo_floor: float = 0.0,
+            depth_floor: float = 0.0, demodulate: bool = True, stats: bool = False, ids=None):
+        """Denoise host arrays (sp_denoiser_run_host): color [slots, 64, 3] float32 as render_tiles
+        returns it, and any of albedo, normal [slots, 64, 3], depth, coverage [slots, 64] as
+        Scene.features returns them -- `**scene.features(n)` passes them all (its ids are not
+        used).  A guide left out takes no part in the weights.  demodulate divides the albedo out
+        before filtering and needs albedo and coverage (SimplePathError without them: pass False).
+        Returns the tile-packed image [slots, 64, 3] (tiles_to_image unpacks it), with stats=True
+        (image, dict of sp_denoise_stats)."""
+        n = self.num_tiles
+        given = {"color": color, "albedo": albedo, "normal": normal, "depth": depth, "coverage": coverage}
+        p = self._params(iterations, sigma_color, sigma_normal, sigma_depth, sigma_coverage, albedo_floor, depth_floor,
+                         demodulate)
+        keep = {}
+        for name, v in given.items():
+            if v is None:
+                continue
+            ch = 3 if name == "color" else DENOISE_GUIDES[name]
+            keep[name] = np.ascontiguousarray(v, dtype=np.float32)
+            if keep[name].size != n * 64 * ch:
+                raise ValueError(f"{name} holds {keep[name].shape} floats for {n} tile slots of 64 x {ch}")
+            setattr(p, "d_" + name, C.c_void_p(keep[name].ctypes.data) if n else None)
+        out = np.zeros((max(n, 1), 64, 3), dtype=np.float32)
+        p.d_out = C.c_void_p(out.ctypes.data) if n else None
+        st = self._stats(lib().sp_denoiser_run_host, self._h, p, stats)
+        return (out[:n], st) if stats else out[:n]
+
+    def run_device(self, color_ptr: int, out_ptr: int, albedo_ptr: int = 0, normal_ptr: int = 0, depth_ptr: int = 0,
+                   coverage_ptr: int = 0, iterations: int = 5, sigma_color: float = 0.6, sigma_normal: float = 0.3,
+                   sigma_depth: float = 0.2, sigma_coverage: float = 0.4, albedo_floor: float = 0.0, depth_floor: float = 0.0,
+                   demodulate: bool = True, stream=None, stats: bool = False):
+        """run on device buffers (sp_denoiser_run), e.g. torch tensors' data_ptr(): out_ptr may equal
+        color_ptr.  With stats=False the call is only enqueued on `stream` (returns None), after the
+        calls that were enqueued there before it: render, features and denoise on one stream need no
+        host wait in between.  With stats=True it waits and returns a dict of sp_denoise_stats."""
+        p = self._params(iterations, sigma_color, sigma_normal, sigma_depth, sigma_coverage, albedo_floor, depth_floor,
+                         demodulate, stream)
+        p.d_color, p.d_out = color_ptr or None, out_ptr or None
+        p.d_albedo, p.d_normal, p.d_depth, p.d_coverage = albedo_ptr or None, normal_ptr or None, depth_ptr or None, coverage_ptr or None
+        return self._stats(lib().sp_denoiser_run, self._h, p, stats)
 
 
 def tiles_to_image(width: int, height: int, tiles: np.ndarray, tile_ids: Optional[np.ndarray] = None) -> np.ndarray:

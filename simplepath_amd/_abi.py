@@ -263,6 +263,29 @@ class sp_feature_stats(C.Structure):
                 ("kernel_ms", C.c_float), ("stack_depth", C.c_int32)]
 
 
+class sp_denoiser_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
+SP_DENOISE_DEMODULATE = 1
+
+
+class sp_denoise_params(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("flags", C.c_int32), ("reserved0", C.c_int32),
+                ("d_color", C.c_void_p), ("d_albedo", C.c_void_p), ("d_normal", C.c_void_p), ("d_depth", C.c_void_p),
+                ("d_coverage", C.c_void_p), ("d_out", C.c_void_p),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_coverage", C.c_float), ("albedo_floor", C.c_float), ("depth_floor", C.c_float),
+                ("stream", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class sp_denoise_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("launches", C.c_int32), ("pixels", C.c_uint64), ("taps", C.c_uint64),
+                ("kernel_ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class sp_progress_params(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32),
                 ("tile_ids", C.POINTER(C.c_int32)), ("d_tile_ids", C.c_void_p), ("num_tiles", C.c_int64),
@@ -354,6 +377,11 @@ SIGNATURES = {
                                             C.POINTER(sp_feature_stats)]),
     "sp_scene_features": (C.c_int, [C.c_void_p, C.POINTER(sp_feature_params), C.POINTER(sp_feature_stats)]),
     "sp_scene_features_host": (C.c_int, [C.c_void_p, C.POINTER(sp_feature_params), C.POINTER(sp_feature_stats)]),
+    "sp_denoiser_create": (C.c_int, [C.POINTER(sp_denoiser_params), C.POINTER(C.c_void_p)]),
+    "sp_denoiser_free": (None, [C.c_void_p]),
+    "sp_denoiser_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "sp_denoiser_run": (C.c_int, [C.c_void_p, C.POINTER(sp_denoise_params), C.POINTER(sp_denoise_stats)]),
+    "sp_denoiser_run_host": (C.c_int, [C.c_void_p, C.POINTER(sp_denoise_params), C.POINTER(sp_denoise_stats)]),
     "sp_render_tiles": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.c_void_p, C.POINTER(sp_render_stats)]),
     "sp_render_tiles_host": (C.c_int, [C.c_void_p, C.POINTER(sp_render_params), C.POINTER(C.c_float),
                                        C.POINTER(sp_render_stats)]),

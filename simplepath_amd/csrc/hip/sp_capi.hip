@@ -11,6 +11,7 @@
 #include "sp_refit.hpp"
 #include "sp_query.hpp"
 #include "sp_features.hpp"
+#include "sp_denoise.hpp"
 #include "sp_envbuild.hpp"
 #include "../common/sp_refit.h"
 #include "../common/sp_sah.h"
@@ -4217,6 +4218,272 @@ int sp_scene_features_host(sp_scene* s, const sp_feature_params* p, sp_feature_s
         return features_host_impl(s, p, stats);
     } catch (const std::exception& e) {
         return fail(SP_ERR_HIP, std::string("sp_scene_features_host failed: ") + e.what());
+    }
+}
+
+// ---- denoising (SP_HAS_DENOISE; sp_denoise.hip) ---------------------------------------------------
+
+// A scene-free object: the frame, the tile list and the scratch the filter's launches share.  The
+// device is first touched by the first run (prepare_denoiser), so creation validates without one.
+struct sp_denoiser {
+    std::mutex           mu;          // calls on one object run one at a time
+    int32_t              device = 0, width = 0, height = 0, tiles_x = 0, tiles_y = 0;
+    int64_t              n = 0;       // tile slots
+    bool                 listed = false;
+    std::vector<int32_t> host_ids;    // a host list's copy (the first run's upload reads it)
+    const int32_t*       d_user_ids = nullptr; // a device list, read by the first run
+    bool                 ready = false;
+    DeviceScratch        ids, map, plane[2], guide, counters;
+    Events<>             ev0, ev1, ev_done;
+    bool                 done_rec = false;
+
+    int64_t total() const { return (int64_t)tiles_x * tiles_y; }
+    size_t  planned_bytes() const
+    {
+        if (n == 0) return 0;
+        return (size_t)n * 64 * 16 * 3 + (listed ? (size_t)n * 4 : 0) + (size_t)total() * 4 + 2 * sizeof(unsigned long long);
+    }
+};
+
+int sp_denoiser_create(const sp_denoiser_params* p, sp_denoiser** out)
+{
+    if (!p || !out) return fail(SP_ERR_ARG, "null argument");
+    if (p->struct_size != sizeof(sp_denoiser_params)) return fail(SP_ERR_ARG, "sp_denoiser_params.struct_size is not this library's");
+    for (int32_t r : p->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_denoiser_params.reserved must be 0");
+    if (p->device < 0) return fail(SP_ERR_ARG, "device < 0");
+    if (p->width < 1 || p->height < 1) return fail(SP_ERR_ARG, "width or height < 1");
+    if (p->num_tiles < 0) return fail(SP_ERR_ARG, "num_tiles < 0");
+    if (p->num_tiles > INT32_MAX) return fail(SP_ERR_ARG, "num_tiles above 2^31 - 1");
+    const int64_t tiles_x = ((int64_t)p->width + 7) / 8, tiles_y = ((int64_t)p->height + 7) / 8;
+    if (tiles_x * tiles_y > INT32_MAX) return fail(SP_ERR_ARG, "width x height: more tiles than an id can name");
+    if (p->tile_ids && p->d_tile_ids) return fail(SP_ERR_ARG, "give tile_ids (host) or d_tile_ids (device), not both");
+    TileList t;
+    t.total  = tiles_x * tiles_y;
+    t.listed = p->tile_ids || p->d_tile_ids;
+    t.n      = t.listed ? p->num_tiles : t.total;
+    if (int rc = check_tile_list(t, p->tile_ids)) return rc;
+    if (p->tile_ids) {
+        std::vector<bool> seen((size_t)t.total, false);
+        for (int64_t i = 0; i < t.n; ++i) {
+            if (seen[(size_t)p->tile_ids[i]]) return fail(SP_ERR_ARG, "tile_ids holds a repeated id");
+            seen[(size_t)p->tile_ids[i]] = true;
+        }
+    }
+    if (misaligned(p->d_tile_ids, 4)) return fail(SP_ERR_ARG, "d_tile_ids must be 4-byte aligned");
+    try {
+        sp_denoiser* d = new sp_denoiser;
+        d->device      = p->device;
+        d->width       = p->width;
+        d->height      = p->height;
+        d->tiles_x     = (int32_t)tiles_x;
+        d->tiles_y     = (int32_t)tiles_y;
+        d->n           = t.n;
+        d->listed      = t.listed;
+        d->d_user_ids  = p->d_tile_ids;
+        if (p->tile_ids) d->host_ids.assign(p->tile_ids, p->tile_ids + t.n);
+        *out = d;
+        return SP_OK;
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_denoiser_create failed: ") + e.what());
+    }
+}
+
+void sp_denoiser_free(sp_denoiser* d)
+{
+    if (!d) return;
+    if (d->ready) {
+        (void)hipSetDevice(d->device);
+        if (d->done_rec) (void)hipEventSynchronize(d->ev_done); // queued work still uses the scratch
+    }
+    delete d;
+}
+
+int sp_denoiser_device_bytes(const sp_denoiser* d, int64_t* out)
+{
+    if (!d || !out) return fail(SP_ERR_ARG, "null argument");
+    *out = (int64_t)d->planned_bytes();
+    return SP_OK;
+}
+
+static bool sigma_ok(float s) { return std::isfinite(s) && s > 0.0f; }
+static bool floor_ok(float f) { return std::isfinite(f) && f >= 0.0f; }
+
+// [p, p + bytes) and [q, q + bytes_q) share a byte
+static bool ranges_overlap(const void* p, size_t bytes, const void* q, size_t bytes_q)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + bytes_q && b < a + bytes;
+}
+
+// Everything sp_denoiser_run refuses, in the header's order; changes nothing
+static int validate_denoise(const sp_denoiser* d, const sp_denoise_params* p, const sp_denoise_stats* stats, bool device_pointers)
+{
+    if (p->struct_size != sizeof(sp_denoise_params)) return fail(SP_ERR_ARG, "sp_denoise_params.struct_size is not this library's");
+    if (stats && stats->struct_size != sizeof(sp_denoise_stats)) return fail(SP_ERR_ARG, "sp_denoise_stats.struct_size is not this library's");
+    if (p->reserved0 != 0) return fail(SP_ERR_ARG, "sp_denoise_params.reserved must be 0");
+    for (int32_t r : p->reserved)
+        if (r != 0) return fail(SP_ERR_ARG, "sp_denoise_params.reserved must be 0");
+    if (p->flags & ~SP_DENOISE_DEMODULATE) return fail(SP_ERR_ARG, "sp_denoise_params.flags: unknown flag");
+    if (p->iterations < 1 || p->iterations > SP_DENOISE_MAX_ITERATIONS) return fail(SP_ERR_ARG, "iterations must be 1 .. 8");
+    if (!sigma_ok(p->sigma_color)) return fail(SP_ERR_ARG, "sigma_color must be finite and > 0");
+    if (p->d_normal && !sigma_ok(p->sigma_normal)) return fail(SP_ERR_ARG, "sigma_normal must be finite and > 0");
+    if (p->d_depth && !sigma_ok(p->sigma_depth)) return fail(SP_ERR_ARG, "sigma_depth must be finite and > 0");
+    if (p->d_coverage && !sigma_ok(p->sigma_coverage)) return fail(SP_ERR_ARG, "sigma_coverage must be finite and > 0");
+    if (!floor_ok(p->albedo_floor)) return fail(SP_ERR_ARG, "albedo_floor must be finite and >= 0");
+    if (!floor_ok(p->depth_floor)) return fail(SP_ERR_ARG, "depth_floor must be finite and >= 0");
+    if (d->n > 0 && !p->d_color) return fail(SP_ERR_ARG, "d_color is missing");
+    if (d->n > 0 && !p->d_out) return fail(SP_ERR_ARG, "d_out is missing");
+    if ((p->flags & SP_DENOISE_DEMODULATE) && (!p->d_albedo || !p->d_coverage))
+        return fail(SP_ERR_ARG, "SP_DENOISE_DEMODULATE needs d_albedo and d_coverage");
+    if (device_pointers && (misaligned(p->d_color, 4) || misaligned(p->d_albedo, 4) || misaligned(p->d_normal, 4) ||
+                            misaligned(p->d_depth, 4) || misaligned(p->d_coverage, 4) || misaligned(p->d_out, 4)))
+        return fail(SP_ERR_ARG, "d_color, d_albedo, d_normal, d_depth, d_coverage and d_out must be 4-byte aligned");
+    const size_t px = (size_t)d->n * 64 * sizeof(float);
+    if (p->d_out != p->d_color && ranges_overlap(p->d_out, px * 3, p->d_color, px * 3))
+        return fail(SP_ERR_ARG, "d_out overlaps d_color without being equal to it");
+    if (ranges_overlap(p->d_out, px * 3, p->d_albedo, px * 3) || ranges_overlap(p->d_out, px * 3, p->d_normal, px * 3) ||
+        ranges_overlap(p->d_out, px * 3, p->d_depth, px) || ranges_overlap(p->d_out, px * 3, p->d_coverage, px))
+        return fail(SP_ERR_ARG, "d_out overlaps d_albedo, d_normal, d_depth or d_coverage");
+    return SP_OK;
+}
+
+// The first run's share: the object's memory, its copy of the list and the inverse map, on `stream`
+static int prepare_denoiser(sp_denoiser* d, hipStream_t stream, int& launches)
+{
+    if (d->ready) return SP_OK;
+    const size_t slots = (size_t)d->n * 64;
+    for (DeviceScratch& pl : d->plane) SP_HIP(pl.reserve(slots * 16));
+    SP_HIP(d->guide.reserve(slots * 16));
+    SP_HIP(d->map.reserve((size_t)d->total() * 4));
+    SP_HIP(d->counters.reserve(2 * sizeof(unsigned long long)));
+    for (hipEvent_t* e : { &d->ev0[0], &d->ev1[0], &d->ev_done[0] })
+        if (!*e) SP_HIP(hipEventCreate(e));
+    if (d->listed) {
+        SP_HIP(d->ids.reserve((size_t)d->n * 4));
+        if (!d->host_ids.empty()) { // (the object keeps the vector: the source outlives the copy, no host wait)
+            SP_HIP(hipMemcpyAsync(d->ids.ptr, d->host_ids.data(), (size_t)d->n * 4, hipMemcpyHostToDevice, stream));
+        } else {
+            SP_HIP(hipMemcpyAsync(d->ids.ptr, d->d_user_ids, (size_t)d->n * 4, hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    SP_HIP(hipMemsetAsync(d->map.ptr, 0xff, (size_t)d->total() * 4, stream)); // -1: absent
+    SP_HIP(spd::launch_denoise_map(d->ids.as<int32_t>(), d->n, (int32_t)d->total(), d->map.as<int32_t>(), stream));
+    ++launches;
+    d->ready = true;
+    return SP_OK;
+}
+
+// after validate_denoise, with the object's lock held
+static int denoise_impl(sp_denoiser* d, const sp_denoise_params* p, sp_denoise_stats* stats)
+{
+    if (stats) {
+        *stats             = sp_denoise_stats{};
+        stats->struct_size = sizeof(sp_denoise_stats);
+    }
+    if (d->n == 0) return SP_OK;
+    SP_HIP(hipSetDevice(d->device));
+    const hipStream_t stream = static_cast<hipStream_t>(p->stream);
+    // the object's previous run comes first: it uses the same scratch
+    if (d->done_rec) SP_HIP(hipStreamWaitEvent(stream, d->ev_done, 0));
+    int launches = 0;
+    if (int rc = prepare_denoiser(d, stream, launches)) return rc;
+    spd::DenoiseArgs a{};
+    a.tile_ids     = d->listed ? d->ids.as<int32_t>() : nullptr;
+    a.slot_of_tile = d->map.as<int32_t>();
+    a.num_tiles    = d->n;
+    a.tiles_x      = d->tiles_x;
+    a.tiles_y      = d->tiles_y;
+    a.width        = d->width;
+    a.height       = d->height;
+    a.color        = p->d_color;
+    a.albedo       = p->d_albedo;
+    a.normal       = p->d_normal;
+    a.depth        = p->d_depth;
+    a.coverage     = p->d_coverage;
+    a.out          = p->d_out;
+    a.plane[0]     = d->plane[0].as<float4>();
+    a.plane[1]     = d->plane[1].as<float4>();
+    a.guide        = d->guide.as<float4>();
+    a.sigma_depth  = p->sigma_depth;
+    a.depth_floor  = p->depth_floor == 0.0f ? spdn::k_depth_floor : p->depth_floor;
+    a.albedo_floor = p->albedo_floor == 0.0f ? spdn::k_albedo_floor : p->albedo_floor;
+    a.demodulate   = (p->flags & SP_DENOISE_DEMODULATE) ? 1 : 0;
+    if (stats) { // counted only when asked for
+        a.counters = d->counters.as<unsigned long long>();
+        SP_HIP(hipMemsetAsync(a.counters, 0, 2 * sizeof(unsigned long long), stream));
+    }
+    SP_HIP(hipEventRecord(d->ev0, stream));
+    SP_HIP(spd::launch_denoise_prepare(a, stream));
+    for (int i = 0; i < p->iterations; ++i) {
+        const spdn::Level L = spdn::level_constants(i, p->sigma_color, p->sigma_normal, p->sigma_coverage, p->d_normal != nullptr,
+                                                    p->d_coverage != nullptr);
+        SP_HIP(spd::launch_denoise_level(a, L, i, p->iterations, stream));
+    }
+    launches += 1 + p->iterations;
+    SP_HIP(hipEventRecord(d->ev1, stream));
+    SP_HIP(hipEventRecord(d->ev_done, stream));
+    d->done_rec = true;
+    if (!stats) return SP_OK; // stream order: only enqueued
+    SP_HIP(hipEventSynchronize(d->ev1));
+    unsigned long long c[2] = { 0, 0 };
+    SP_HIP(hipMemcpy(c, a.counters, sizeof(c), hipMemcpyDeviceToHost));
+    SP_HIP(hipEventElapsedTime(&stats->kernel_ms, d->ev0, d->ev1));
+    stats->launches = launches;
+    stats->pixels   = c[0];
+    stats->taps     = c[1];
+    return SP_OK;
+}
+
+int sp_denoiser_run(sp_denoiser* d, const sp_denoise_params* p, sp_denoise_stats* stats)
+{
+    if (!d || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(d->mu);
+    try {
+        if (int rc = validate_denoise(d, p, stats, true)) return rc;
+        return denoise_impl(d, p, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_denoiser_run failed: ") + e.what());
+    }
+}
+
+// the host form with the object's lock held: the same refusals in the same order on the host arrays
+// as given, then device buffers of its own around the device form (features_host_impl's pattern)
+static int denoise_host_impl(sp_denoiser* d, const sp_denoise_params* p, sp_denoise_stats* stats)
+{
+    if (int rc = validate_denoise(d, p, stats, false)) return rc;
+    if (d->n == 0) return denoise_impl(d, p, stats);
+    SP_HIP(hipSetDevice(d->device));
+    const size_t      px       = (size_t)d->n * 64 * sizeof(float);
+    const float*      host[5]  = { p->d_color, p->d_albedo, p->d_normal, p->d_depth, p->d_coverage };
+    const size_t      bytes[5] = { px * 3, px * 3, px * 3, px, px };
+    DeviceScratch     dev[5];
+    for (int k = 0; k < 5; ++k)
+        if (host[k]) {
+            SP_HIP(dev[k].reserve(bytes[k]));
+            SP_HIP(hipMemcpy(dev[k].ptr, host[k], bytes[k], hipMemcpyHostToDevice));
+        }
+    sp_denoise_params dp = *p;
+    dp.d_color    = dev[0].as<float>();
+    dp.d_albedo   = dev[1].as<float>();
+    dp.d_normal   = dev[2].as<float>();
+    dp.d_depth    = dev[3].as<float>();
+    dp.d_coverage = dev[4].as<float>();
+    dp.d_out      = dev[0].as<float>(); // in place: d_out may equal d_color
+    dp.stream     = nullptr;            // with the blocking copies around it, as render_to_host
+    if (int rc = denoise_impl(d, &dp, stats)) return rc;
+    SP_HIP(hipMemcpy(p->d_out, dev[0].ptr, bytes[0], hipMemcpyDeviceToHost));
+    return SP_OK;
+}
+
+int sp_denoiser_run_host(sp_denoiser* d, const sp_denoise_params* p, sp_denoise_stats* stats)
+{
+    if (!d || !p) return fail(SP_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(d->mu);
+    try {
+        return denoise_host_impl(d, p, stats);
+    } catch (const std::exception& e) {
+        return fail(SP_ERR_HIP, std::string("sp_denoiser_run_host failed: ") + e.what());
     }
 }
 
