@@ -875,6 +875,16 @@ static MS lam_sample(const sp_material_desc* m, Mt* rng)
     r.props = P_DIFFUSE | P_REFLECTIVE;
     return r;
 }
+/* BxDF::rho of the microfacet lobe with 16 samples, as get_selection_weights calls it */
+static C3 mf_rho16(const sp_material_desc* m, V3 wo, Mt* rng)
+{
+    C3 r = c3(0, 0, 0);
+    for (unsigned i = 0; i < 16u; ++i) {
+        MS s = mf_sample(m, wo, rng);
+        if (s.pdf > 0.0f) r = cadd(r, cdivf(cmulf(s.color, fabsf(s.dir.y)), s.pdf));
+    }
+    return cdivf(r, (float)16u);
+}
 /* OneSampleMaterial::get_selection_weights (materials/Material.h:546) */
 static int weights(const sp_material_desc* m, V3 wo, Mt* rng, float* w)
 {
@@ -885,12 +895,7 @@ static int weights(const sp_material_desc* m, V3 wo, Mt* rng, float* w)
         w[0] = w[0] / sum;
         return 1;
     }
-    C3 r = c3(0, 0, 0);
-    for (unsigned i = 0; i < 16u; ++i) {
-        MS s = mf_sample(m, wo, rng);
-        if (s.pdf > 0.0f) r = cadd(r, cdivf(cmulf(s.color, fabsf(s.dir.y)), s.pdf));
-    }
-    r = cdivf(r, (float)16u);
+    C3 r = mf_rho16(m, wo, rng);
     w[0] = lum(r);
     sum += w[0];
     w[1] = lum(cmulf(albedo(m), PI_F));
@@ -1494,11 +1499,72 @@ static sp_material_desc unit_material(float ax, float ay, float ior)
     return m;
 }
 
+/* The stream-fed layer.  A row that draws starts with seed, skip: the stream is seeded and `skip`
+ * words are discarded; after the function the row's last two output words are the number of
+ * words the function consumed and one further canonical draw (the state it leaves behind).
+ * Material record, 26 words: kind, albedo, microfacet_r, alpha_x, alpha_y, ior, sample_visible_area,
+ * coat_ior, coat_color, then the base record of a clearcoat (kind .. sample_visible_area, 11 words).
+ * Light record, 37 words: kind, radiance, object_to_world, world_to_object, normal_to_world. */
+enum { ROW_MAT = 26, ROW_LIGHT = 37 };
+static void row_record(const uint32_t* w, sp_material_desc* m)
+{
+    memset(m, 0, sizeof *m);
+    m->kind = (int32_t)w[0]; m->base = -1;
+    for (int i = 0; i < 3; ++i) { m->lambert_albedo[i] = w2f(w[1 + i]); m->microfacet_r[i] = w2f(w[4 + i]); }
+    m->alpha_x = w2f(w[7]); m->alpha_y = w2f(w[8]); m->microfacet_ior = w2f(w[9]);
+    m->sample_visible_area = (int32_t)w[10];
+}
+static void row_materials(const uint32_t* w, sp_material_desc mats[2])
+{
+    row_record(w, &mats[0]);
+    row_record(w + 15, &mats[1]);
+    mats[0].coat_ior = w2f(w[11]);
+    for (int i = 0; i < 3; ++i) mats[0].coat_color[i] = w2f(w[12 + i]);
+    if (mats[0].kind == SP_MAT_CLEARCOAT) mats[0].base = 1;
+}
+static void row_light(const uint32_t* w, sp_light_desc* l)
+{
+    memset(l, 0, sizeof *l);
+    l->kind = (int32_t)w[0]; l->image = -1;
+    for (int i = 0; i < 3; ++i) l->radiance[i] = w2f(w[1 + i]);
+    float* dst[3] = { l->object_to_world.vx, l->world_to_object.vx, l->normal_to_world.vx };
+    for (int i = 0; i < 12; ++i) { dst[0][i] = w2f(w[4 + i]); dst[1][i] = w2f(w[16 + i]); }
+    for (int i = 0; i < 9; ++i) dst[2][i] = w2f(w[28 + i]);
+}
+static void ms2w(uint32_t* o, const MS* s)
+{
+    o[0] = f2w(s->color.r); o[1] = f2w(s->color.g); o[2] = f2w(s->color.b);
+    v2w(o + 3, s->dir); o[6] = f2w(s->pdf); o[7] = (uint32_t)s->props;
+}
+/* The image the env_* units work against: built by env_build from the caller's pixels
+ * (orc_unit_env), kept until the next call.  orc_unit_env_cdf copies its marginal (nv + 1) and
+ * conditional (nv * (nu + 1)) cdf tables out, for rows that sit on their entries. */
+static OEnv g_unit_env;
+static int  g_unit_env_set = 0;
+int orc_unit_env(const sp_env_image* img)
+{
+    if (!img || img->width < 1 || img->height < 1 || !img->pixels) return -1;
+    if (g_unit_env_set) env_free(&g_unit_env);
+    env_build(img, &g_unit_env);
+    g_unit_env_set = 1;
+    return 0;
+}
+int orc_unit_env_cdf(float* marg, float* cond)
+{
+    if (!g_unit_env_set) return -1;
+    const OEnv* e = &g_unit_env;
+    memcpy(marg, e->mcdf, (size_t)(e->nv + 1) * sizeof(float));
+    memcpy(cond, e->ccdf, (size_t)e->nv * (size_t)(e->nu + 1) * sizeof(float));
+    return 0;
+}
+
 enum { U_EXPF, U_LOGF, U_SINF, U_COSF, U_ERFF, U_ACOSF, U_ATANF, U_FMOD1, U_ROUNDF, U_SINCOSF, U_SINCOSF_BOUNDED,
        U_POWF, U_ATAN2F, U_POWF_UNIT, U_DIV, U_SQRT, U_FMA, U_MULADD, U_SQRT_UNIT, U_DOT, U_CROSS, U_DOP1,
        U_RSQRTSS, U_RSQRT_REF, U_FRESNEL, U_ERFINV, U_BECK11, U_BECK11_PRE, U_UNIFORM_SPHERE, U_UNIFORM_HEMISPHERE,
        U_CONCENTRIC_DISK, U_COSINE_HEMISPHERE, U_ONB_OF_UNIT, U_BECK_D, U_BECK_LAMBDA, U_BECK_PDF, U_MF_EVAL, U_MF_PDF,
-       U_SPHERICAL_PHI, U_RAY_OFFSET, U_TRI_HIT, U_SPHERE_T, U_PLANE_T, U_BOX_HIT, U_COUNT };
+       U_SPHERICAL_PHI, U_RAY_OFFSET, U_TRI_HIT, U_SPHERE_T, U_PLANE_T, U_BOX_HIT,
+       U_RHO16, U_GLOSSY_WEIGHTS, U_MF_SAMPLE, U_MATERIAL_SAMPLE, U_MATERIAL_EVAL, U_MATERIAL_PDF,
+       U_SPHERE_PDF, U_LIGHT_SAMPLE, U_LIGHT_PDF, U_ENV_SAMPLE, U_ENV_PDF, U_ENV_RADIANCE, U_SERVE_RHO, U_COUNT };
 static const struct { const char* name; int k, m; } unit_fns[U_COUNT] = {
     { "expf", 1, 1 }, { "logf", 1, 1 }, { "sinf", 1, 1 }, { "cosf", 1, 1 }, { "erff", 1, 1 }, { "acosf", 1, 1 },
     { "atanf", 1, 1 }, { "fmod1", 1, 1 }, { "roundf", 1, 1 }, { "sincosf", 1, 2 }, { "sincosf_bounded", 1, 2 },
@@ -1509,6 +1575,10 @@ static const struct { const char* name; int k, m; } unit_fns[U_COUNT] = {
     { "cosine_hemisphere", 2, 3 }, { "onb_of_unit", 3, 9 }, { "beck_D", 5, 1 }, { "beck_lambda", 5, 1 },
     { "beck_pdf", 8, 1 }, { "mf_eval", 9, 3 }, { "mf_pdf", 8, 1 }, { "spherical_phi", 3, 1 }, { "ray_offset", 6, 1 },
     { "tri_hit", 17, 4 }, { "sphere_t", 20, 2 }, { "plane_t", 20, 2 }, { "box_hit", 14, 1 },
+    { "rho16", 31, 5 }, { "glossy_weights", 31, 4 }, { "mf_sample", 31, 10 }, { "material_sample", 34, 10 },
+    { "material_eval", 37, 5 }, { "material_pdf", 37, 3 },
+    { "sphere_pdf", 40, 1 }, { "light_sample", 45, 9 }, { "light_pdf", 43, 1 },
+    { "env_sample", 2, 7 }, { "env_pdf", 3, 1 }, { "env_radiance", 3, 3 }, { "serve_rho", 35, 12 },
 };
 
 /* words per row of `function`: inputs in *k, outputs in *m; -1 for an unknown name */
@@ -1529,7 +1599,7 @@ int orc_unit(const char* function, const uint32_t* in, int64_t n, uint32_t* out)
     for (int64_t r = 0; r < n; ++r) {
         const uint32_t* w = in + r * k;
         uint32_t*       o = out + r * m;
-        float           x[20];
+        float           x[48];
         for (int i = 0; i < k; ++i) x[i] = w2f(w[i]);
         memset(o, 0, (size_t)m * 4);
         switch (fn) {
@@ -1609,6 +1679,118 @@ int orc_unit(const char* function, const uint32_t* in, int64_t n, uint32_t* out)
             for (int i = 0; i < 3; ++i) { nd.lo[i] = x[i]; nd.hi[i] = x[3 + i]; }
             Ray ray = { w2v(w + 6), w2v(w + 9) };
             o[0] = (uint32_t)box_p(&nd, &ray, x[12], x[13]);
+            break;
+        }
+        case U_RHO16: case U_GLOSSY_WEIGHTS: case U_MF_SAMPLE: case U_MATERIAL_SAMPLE: case U_MATERIAL_EVAL:
+        case U_MATERIAL_PDF: { /* seed, skip, material record, then the directions */
+            sp_material_desc mats[2];
+            sp_scene_desc    d;
+            Mt               rng;
+            row_materials(w + 2, mats);
+            memset(&d, 0, sizeof d);
+            d.materials = mats;
+            mt_seed(&rng, w[0]);
+            for (uint32_t i = 0; i < w[1]; ++i) mt_next(&rng);
+            const int       p0 = rng.p;
+            const uint32_t* v  = w + 2 + ROW_MAT;
+            if (fn == U_RHO16) { /* the estimate inside get_selection_weights */
+                C3 r = mf_rho16(&mats[0], w2v(v), &rng);
+                o[0] = f2w(r.r); o[1] = f2w(r.g); o[2] = f2w(r.b);
+            } else if (fn == U_GLOSSY_WEIGHTS) {
+                float wt[2];
+                weights(&mats[0], w2v(v), &rng, wt);
+                o[0] = f2w(wt[0]); o[1] = f2w(wt[1]);
+            } else if (fn == U_MF_SAMPLE) {
+                MS s = mf_sample(&mats[0], w2v(v), &rng);
+                ms2w(o, &s);
+            } else if (fn == U_MATERIAL_SAMPLE) { /* n, wo */
+                MS s = mat_sample(&d, 0, w2v(v + 3), w2v(v), &rng);
+                ms2w(o, &s);
+            } else if (fn == U_MATERIAL_EVAL) { /* n, wo, wi */
+                C3 c = mat_eval(&d, 0, w2v(v + 3), w2v(v + 6), w2v(v), &rng);
+                o[0] = f2w(c.r); o[1] = f2w(c.g); o[2] = f2w(c.b);
+            } else {
+                o[0] = f2w(mat_pdf(&d, 0, w2v(v + 3), w2v(v + 6), w2v(v), &rng));
+            }
+            o[m - 2] = (uint32_t)((rng.p - p0 + 624) % 312); /* every function here consumes fewer than 312 words */
+            o[m - 1] = f2w(canonical(&rng));
+            break;
+        }
+        case U_SPHERE_PDF: { sp_light_desc l; row_light(w, &l); o[0] = f2w(sphere_pdf(&l, w2v(w + ROW_LIGHT))); break; }
+        case U_LIGHT_SAMPLE: { /* light record, observer, its normal, u -> L, pdf, direction, tmin, tmax */
+            sp_light_desc l;
+            OScene        sc;
+            row_light(w, &l);
+            memset(&sc, 0, sizeof sc);
+            P2 u  = { x[ROW_LIGHT + 6], x[ROW_LIGHT + 7] };
+            LS ls = light_sample(&sc, &l, w2v(w + ROW_LIGHT), w2v(w + ROW_LIGHT + 3), u);
+            o[0] = f2w(ls.L.r); o[1] = f2w(ls.L.g); o[2] = f2w(ls.L.b); o[3] = f2w(ls.pdf);
+            v2w(o + 4, ls.ray.d); o[7] = f2w(ls.tmin); o[8] = f2w(ls.tmax);
+            break;
+        }
+        case U_LIGHT_PDF: { /* Light::pdf (Lights/Light.h:54): the sphere's pdf, or the uniform sphere's */
+            sp_light_desc l;
+            row_light(w, &l);
+            o[0] = f2w(l.kind == SP_LIGHT_SPHERE ? sphere_pdf(&l, w2v(w + ROW_LIGHT)) : UNIFORM_SPHERE_PDF);
+            break;
+        }
+        case U_ENV_SAMPLE: { /* u -> L, pdf, wi: Light::sample of an image light, without the ray's limits */
+            if (!g_unit_env_set) return -1;
+            sp_light_desc l;
+            OScene        sc;
+            memset(&l, 0, sizeof l);
+            memset(&sc, 0, sizeof sc);
+            l.kind = SP_LIGHT_IMAGE_ENVIRONMENT; l.image = 0;
+            sc.envs = &g_unit_env;
+            P2 u  = { x[0], x[1] };
+            LS ls = light_sample(&sc, &l, v3(0, 0, 0), v3(0, 1, 0), u);
+            o[0] = f2w(ls.L.r); o[1] = f2w(ls.L.g); o[2] = f2w(ls.L.b); o[3] = f2w(ls.pdf); v2w(o + 4, ls.ray.d);
+            break;
+        }
+        case U_ENV_PDF: if (!g_unit_env_set) return -1; o[0] = f2w(env_pdf(&g_unit_env, w2v(w))); break;
+        case U_ENV_RADIANCE: {
+            if (!g_unit_env_set) return -1;
+            C3 c = env_radiance(&g_unit_env, w2v(w));
+            o[0] = f2w(c.r); o[1] = f2w(c.g); o[2] = f2w(c.b);
+            break;
+        }
+        case U_SERVE_RHO: { /* one lane's request of the wave-served estimates (tests/cpp/device_units.hip serve_kernel):
+                             * seed, skip, material record, n, wo, flags (1 the light's eval / pdf / sample sites, 2 the
+                             * bounce's own sample, 4 the lane is absent).  The estimates are `weights` at the positions
+                             * the reference's call sites reach them at. */
+            const uint32_t flags = w[34];
+            if (flags & 4u) break;
+            sp_material_desc mats[2];
+            Mt               rng;
+            row_materials(w + 2, mats);
+            mt_seed(&rng, w[0]);
+            for (uint32_t i = 0; i < w[1]; ++i) mt_next(&rng);
+            const int               coat = mats[0].kind == SP_MAT_CLEARCOAT;
+            const sp_material_desc* base = &mats[coat ? 1 : 0];
+            Onb   ob = onb_from_v(w2v(w + 28));
+            V3    wl = to_onb(&ob, w2v(w + 31));
+            float wt[2];
+            if (flags & 2u) { /* Material::sample of the bounce: a clearcoat's pick, then the estimate, then three words */
+                Mt  snap = rng;
+                int spec = 0;
+                if (coat) spec = canonical(&rng) < fresnel(wl.y, 1.0f, mats[0].coat_ior);
+                if (spec) rng = snap;
+                else {
+                    weights(base, wl, &rng, wt);
+                    o[0] = 1u; o[1] = f2w(wt[0]); o[2] = f2w(wt[1]); o[3] = (uint32_t)((rng.p - snap.p + 624) % 312);
+                    for (int i = 0; i < 3; ++i) mt_next(&rng);
+                }
+            }
+            next2(&rng); /* the light's sample */
+            const int p0 = rng.p;
+            if (flags & 1u) { /* Material::eval, ::pdf, ::sample (Integrator.cpp:505-519) */
+                weights(base, wl, &rng, wt); o[4] = f2w(wt[0]); o[5] = f2w(wt[1]);
+                weights(base, wl, &rng, wt); o[6] = f2w(wt[0]); o[7] = f2w(wt[1]);
+                if (coat) canonical(&rng);
+                weights(base, wl, &rng, wt); o[8] = f2w(wt[0]); o[9] = f2w(wt[1]);
+            }
+            o[10] = (uint32_t)((rng.p - p0 + 624) % 312);
+            o[11] = f2w(canonical(&rng));
             break;
         }
         default: return -1;

@@ -22,6 +22,13 @@ Row formats (32-bit words, floats as their bits):
     sphere_t, plane_t  world_to_object (vx, vy, vz, p), o3, d3, tmin, tmax -> flag, t
     box_hit  lo3, hi3, o3, d3, tmin, tmax -> flag
     stream  seed, seeding, 200 steps -> count, the values drawn   (section f below)
+    the stream-fed layer (rho16 .. material_pdf: seed, skip, a material record, directions -> the words,
+    the stream words consumed, one further draw; the light units) and the image environment light
+    against small images: sections g and h below, which state their row formats
+
+Kernel option sets.  sp_path.hpp is compiled under five sets of options (tests/cpp/Makefile SET_*);
+the evaluator is built once per set, and the stream and the units that own a generator (DRAWING)
+run in every set that compiles them.
 
 NaN rule.  For every lm_* function, fmod1, round_f and rsqrtss_emulated the header restates the x86
 result explicitly: all bits are compared for every input, NaN inputs and NaN results included
@@ -37,6 +44,8 @@ and ordinary arguments side by side, and no row count is a multiple of 64.
 from __future__ import annotations
 
 import ctypes as C
+import os as _os
+import re as _re
 from collections import namedtuple
 
 import numpy as np
@@ -72,7 +81,7 @@ FRINGES = {
     "erfinv": [0x3f7fb848],
 }
 
-Spec = namedtuple("Spec", "k m oracle rule table nan_exempt rows")
+Spec = namedtuple("Spec", "k m oracle rule table nan_exempt rows image", defaults=(None,))  # image: a key of IMAGES (section h)
 
 
 def _rng(name: str) -> np.random.Generator:
@@ -405,11 +414,14 @@ def _rows_beck11_pre():
     return _finish("beck11_pre", [same, rnd], 7)
 
 
+U_TOP = np.float32(1.0 - 2.0 ** -24)
+U_SPECIALS = np.array([0.0, 2.0 ** -24, 0.25, 0.5, 0.75, U_TOP, 0.5 - 2.0 ** -25, 0.5 + 2.0 ** -24, 1e-6], dtype=np.float32)
+
+
 def _u2_rows(name):
     def build():
         g = _rng("u2")  # the four sampling maps run the same rows
-        top = np.float32(1.0 - 2.0 ** -24)
-        sp = np.array([0.0, 2.0 ** -24, 0.25, 0.5, 0.75, top, 0.5 - 2.0 ** -25, 0.5 + 2.0 ** -24, 1e-6], dtype=np.float32)
+        top, sp = U_TOP, U_SPECIALS
         a, b = np.meshgrid(sp, sp, indexing="ij")
         n = 1 << 16
         u = np.minimum(g.uniform(0, 1, (N_RANDOM, 2)).astype(np.float32), top)
@@ -789,6 +801,417 @@ def stream_expected(variant: str, r: np.ndarray) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------ g. the stream-fed layer
+# Rows that draw: seed, skip, a material record (ROW_MAT words), then directions.  Output: the
+# function's words, the number of stream words it consumed, one further next1D.
+#   material record  kind, albedo3, microfacet_r3, alpha_x, alpha_y, ior, sample_visible_area,
+#                    coat_ior, coat_color3, base record (kind .. sample_visible_area, 11 words)
+#   rho16 (and rho16_served)             + local wo -> rgb
+#   glossy_weights (and weights_served)  + local wo -> w0, w1
+#   mf_sample, mf_sample_pre             + local wo -> colour3, dir3, pdf, props
+#   material_sample  + n, wo -> colour3, dir3, pdf, props     (world form)
+#   material_eval    + n, wo, wi -> rgb       material_pdf  + n, wo, wi -> pdf
+# Lights (no draws): a light record (ROW_LIGHT words: kind, radiance3, object_to_world 12,
+# world_to_object 12, normal_to_world 9), the observer, then
+#   sphere_pdf  -> pdf      light_pdf  + wi -> pdf
+#   light_sample  + the observer's normal, u2 -> L3, pdf, direction3, tmin, tmax
+# sample_visible_area is 1 in every row: the scene parser sets nothing else (sp_scene.cpp blank_material).
+ROW_MAT, ROW_LIGHT = 26, 37
+N_DRAW = 1 << 16
+IORS = [1.5, 1.33, 2.4, 1.0, 0.7]
+COAT_IORS = [1.5, 1.0, 0.8]
+MAT_LAMBERTIAN, MAT_GLOSSY, MAT_CLEARCOAT = 0, 1, 2
+LIGHT_SPHERE, LIGHT_ENVIRONMENT = 0, 1
+SPHERE_PDF_SWITCH = 1.0 / 0.00068523     # sphere_pdf's small-angle form below sin^2 = 0.00068523: squared distance above this
+ONE_ULP = np.nextafter(np.float32(1), np.float32(2))
+
+
+def _skips(g, n) -> np.ndarray:
+    """Stream positions: anywhere in the first two generations (even and odd); every start from
+    312 - 33 to 312 + 1, so the 32 words of an estimate straddle the boundary in every way at both
+    parities; exactly 0 and 311; the same around the second boundary."""
+    c = np.arange(n) % 8
+    s = g.integers(0, 2 * MT_N + 80, n)
+    s = np.where(c == 0, g.integers(MT_N - 33, MT_N + 2, n), s)
+    s = np.where(c == 1, g.integers(2 * MT_N - 33, 2 * MT_N + 2, n), s)
+    s = np.where(c == 2, np.where(g.integers(0, 2, n) == 0, 0, MT_N - 1), s)
+    s = np.where(c == 3, g.integers(MT_N - 3, MT_N + 1, n), s)     # 309 .. 312: the coat's draw, a sample's pair at the boundary
+    return s.astype(np.uint32)
+
+
+def _records(g, n, kinds) -> np.ndarray:
+    """n material records without a coat (11 words): float columns as bits."""
+    kind = np.asarray(kinds)[g.integers(0, len(kinds), n)]
+    i = np.arange(n)
+    # albedo classes: zero in 1 of 32 (with it the weights are rho / rho, a NaN whenever the estimate is
+    # 0 or infinite, about one such row in 80: thinned for the NaN cap), above 1 in 1 of 8
+    ac, rc = g.integers(0, 32, n), g.integers(0, 8, n)
+    alb = g.uniform(0.02, 1.0, (n, 3)) / np.pi                     # ordinary (albedo / pi)
+    alb = np.where(((ac >= 1) & (ac <= 4))[:, None], g.uniform(1.0, 4.0, (n, 3)), alb)   # above 1
+    R = g.uniform(0.05, 1.0, (n, 3)).astype(np.float32)            # coloured: rc 5, 6, 7
+    R[rc <= 1] = 1.0                                               # grey, the scene files' own
+    R[rc == 2] = 0.5                                               # grey
+    near = rc == 3                                                 # one channel an ulp off grey: no shortcut
+    R[near] = 1.0
+    R[near, i[near] % 3] = ONE_ULP
+    R[rc == 4] = 0.0                                               # a black microfacet colour
+    # a zero albedo; where the other lobe is black too (or there is none) `weights` divides 0 by 0:
+    # those rows are thinned to 1 in 64 for the NaN cap
+    lone = (kind == MAT_LAMBERTIAN) | (rc == 4)
+    zero = (ac == 0) & (~lone | (i % 64 == 0))
+    alb = np.where(zero[:, None], 0.0, alb)
+    ax, ay = _alpha_columns(g, n)
+    ior = np.array(IORS, dtype=np.float32)[g.integers(0, len(IORS), n)]
+    return np.concatenate([kind.astype(np.uint32)[:, None], f2u(alb.astype(np.float32)), f2u(R), f2u(ax)[:, None],
+                           f2u(ay)[:, None], f2u(ior)[:, None], np.ones((n, 1), np.uint32)], axis=1)
+
+
+def _materials(g, n, kinds) -> np.ndarray:
+    """n full records (ROW_MAT words).  A clearcoat's own lobes are unused (zero); its base is a
+    Lambertian or a glossy record."""
+    top = _records(g, n, [k for k in kinds if k != MAT_CLEARCOAT])
+    base = _records(g, n, [MAT_LAMBERTIAN, MAT_GLOSSY])
+    coat = (g.integers(0, 3, n) == 0) if MAT_CLEARCOAT in kinds else np.zeros(n, bool)
+    top[coat, 0] = MAT_CLEARCOAT
+    cior = np.array(COAT_IORS, dtype=np.float32)[g.integers(0, len(COAT_IORS), n)]
+    ccol = np.where((g.integers(0, 2, n) == 0)[:, None], 1.0, g.uniform(0.1, 1.0, (n, 3))).astype(np.float32)
+    return np.concatenate([top, f2u(cior)[:, None], f2u(ccol), base], axis=1)
+
+
+def _local_wo(g, n) -> np.ndarray:
+    """Local outgoing directions: _shading_dirs (both hemispheres), DIR_SPECIALS, wo.y = +0 and -0
+    (nothing is drawn), |wo.y| down to 1e-38."""
+    wo = _shading_dirs(g, n)
+    k = np.arange(n) % 512   # the grazing classes give the reference infinities and NaNs: rare, for the NaN cap
+    wo = np.where((k == 1)[:, None], DIR_SPECIALS[g.integers(0, len(DIR_SPECIALS), n)], wo)
+    th = g.uniform(0, 2 * np.pi, n)
+    ring = np.stack([np.cos(th), np.zeros(n), np.sin(th)], axis=1).astype(np.float32)
+    ring[:, 1] = np.where(g.integers(0, 2, n) == 0, np.float32(0.0), np.float32(-0.0))
+    wo = np.where((k % 256 == 2)[:, None], ring, wo)   # with a zero albedo on top, wo.y = 0 leaves `weights` 0 / 0
+    tiny = ring.copy()
+    tiny[:, 1] = (10.0 ** g.uniform(-38, -6, n) * np.where(g.integers(0, 2, n) == 0, 1.0, -1.0)).astype(np.float32)
+    wo = np.where((k == 3)[:, None], tiny, wo)
+    return wo.astype(np.float32)
+
+
+def _local_pairs(g, n):
+    """wo as _local_wo; wi: any direction, -wo, wo, a special, the hemisphere opposite to wo."""
+    wo, wi = _local_wo(g, n), _shading_dirs(g, n)
+    j = np.arange(n) % 64
+    wi = np.where((j == 5)[:, None], -wo, wi)
+    wi = np.where((j == 6)[:, None], wo, wi)
+    wi = np.where((j == 7)[:, None], DIR_SPECIALS[g.integers(0, len(DIR_SPECIALS), n)], wi)
+    opp = wi.copy()
+    opp[:, 1] = -np.copysign(np.abs(wi[:, 1]), wo[:, 1])
+    wi = np.where(((j >= 8) & (j < 12))[:, None], opp, wi)
+    return wo, wi.astype(np.float32)
+
+
+def _to_world(g, n, *local):
+    """A shading normal per row and the local directions in its frame.  Half the rows: n = (0, 1, 0),
+    whose frame (onb_of_unit) is the exact permutation local = (-w.z, w.y, w.x), so every special
+    value of the local directions survives; the others: a random normal of length 1, 0.37 or 3."""
+    nrm = _unit_vectors(g, n).astype(np.float64)
+    a = np.cross(nrm, _unit_vectors(g, n))
+    a /= np.linalg.norm(a, axis=1, keepdims=True)
+    b = np.cross(nrm, a)
+    even = (g.integers(0, 2, n) == 0)[:, None]
+    out = []
+    for l in local:
+        exact = np.stack([l[:, 2], l[:, 1], -l[:, 0]], axis=1)
+        rot = (l[:, :1] * a + l[:, 1:2] * nrm + l[:, 2:] * b).astype(np.float32)
+        out.append(np.where(even, exact, rot).astype(np.float32))
+    length = np.array([1.0, 1.0, 0.37, 3.0])[g.integers(0, 4, n)][:, None]
+    nw = np.where(even, np.float32([0, 1, 0]), (nrm * length).astype(np.float32)).astype(np.float32)
+    return [nw] + out
+
+
+def _draw_head(g, n, kinds):
+    seed = g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    return np.concatenate([seed[:, None], _skips(g, n)[:, None], _materials(g, n, kinds)], axis=1)
+
+
+def _rows_local_draw():
+    g = _rng("local_draw")  # rho16, glossy_weights, mf_sample and their other forms run the same rows
+    n = N_DRAW
+    return _finish("local_draw", [np.concatenate([_draw_head(g, n, [MAT_GLOSSY]), f2u(_local_wo(g, n))], axis=1)], 31)
+
+
+def _rows_material(name):
+    def build():
+        g = _rng("material")  # material_sample, material_eval and material_pdf run the same records and directions
+        n = N_DRAW
+        head = _draw_head(g, n, [MAT_LAMBERTIAN, MAT_GLOSSY, MAT_CLEARCOAT])
+        nw, wo, wi = _to_world(g, n, *_local_pairs(g, n))
+        cols = [head, f2u(nw), f2u(wo)] + ([] if name == "material_sample" else [f2u(wi)])
+        return _finish("material", [np.concatenate(cols, axis=1)], 34 if name == "material_sample" else 37)
+    return build
+
+
+# serve_rho (rrnee set): 64 consecutive rows are one wave, each row one lane's request:
+#   seed, skip, material record, n, wo, flags -> served?, wA0, wA1, words of the bounce's site,
+#   wE0, wE1, wP0, wP1, wS0, wS1, words of the light's three sites, one further next1D
+# flags: 1 wants the light's eval / pdf / sample estimates, 2 wants the bounce's own sample's, 4 the lane
+# is absent (it leaves before the call).  Wave classes, by wave index % 8:
+#   0 every lane wants both (256 requests for 64 lanes: the deal loop runs four times)
+#   1 one lane only        2 lanes 0 and 63 only       3 half the lanes absent, the others want at random
+#   4 wants at random, nobody absent                   5 48 lanes absent, the 16 others want both (64 requests for 16)
+#   6 every lane wants both, at positions whose estimates straddle the generation boundary
+#   7 wants and absences at random
+# In classes 0, 4 and 6 the lanes with lane % 16 == 5 have wo.y == 0 (dc 0: nothing drawn); a third of
+# the owners are clearcoats.  Every material has a glossy lobe, as material_has_rho demands of an owner.
+SERVE_WAVES = 512
+WANT_B, WANT_A, ABSENT = 1, 2, 4
+
+
+def _rows_serve_rho():
+    g = _rng("serve_rho")
+    n = SERVE_WAVES * 64
+    mat = _materials(g, n, [MAT_GLOSSY, MAT_CLEARCOAT])
+    mat[:, 15] = MAT_GLOSSY                                   # a coat's base: glossy
+    nw, wo = _to_world(g, n, _local_wo(g, n))
+    lane, wave = np.arange(n) % 64, np.arange(n) // 64
+    cls = wave % 8
+    rnd = g.integers(0, 4, n)
+    flags = np.where(cls == 0, 3, rnd)
+    one = g.integers(0, 64, SERVE_WAVES)[wave]
+    flags = np.where(cls == 1, np.where(lane == one, 1 + 2 * (wave // 8 % 2), 0), flags)
+    flags = np.where(cls == 2, np.where((lane == 0) | (lane == 63), 3, 0), flags)
+    flags = np.where((cls == 3) & (g.integers(0, 2, n) == 0), ABSENT, flags)
+    perm = np.argsort(g.random((SERVE_WAVES, 64)), axis=1).ravel()   # a random rank per lane of each wave
+    flags = np.where(cls == 5, np.where(perm < 48, ABSENT, 3), flags)
+    flags = np.where(cls == 6, 3, flags)
+    flags = np.where((cls == 7) & (g.integers(0, 4, n) == 0), ABSENT, flags)
+    skip = _skips(g, n)
+    skip = np.where(cls == 6, g.integers(MT_N - 110, MT_N + 1, n), skip).astype(np.uint32)
+    dc0 = np.isin(cls, (0, 4, 6)) & (lane % 16 == 5)
+    th = g.uniform(0, 2 * np.pi, n)
+    flat = np.stack([np.cos(th), np.where(g.integers(0, 2, n) == 0, 0.0, -0.0), np.sin(th)], axis=1).astype(np.float32)
+    nw = np.where(dc0[:, None], np.float32([0, 1, 0]), nw)
+    wo = np.where(dc0[:, None], flat, wo)
+    ordinary = f2u(np.full(3, 0.2, np.float32))               # with nothing drawn a zero albedo leaves 0 / 0: not here
+    mat[dc0, 1:4] = ordinary
+    mat[dc0, 16:19] = ordinary
+    seed = g.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    r = np.concatenate([seed[:, None], skip[:, None], mat, f2u(nw), f2u(wo), flags.astype(np.uint32)[:, None]], axis=1)
+    return np.ascontiguousarray(r.astype(np.uint32))
+
+
+def _light_records(g, n):
+    """Light records and observers in the light's object space -> (records [n, 37], observers in world space).
+    Transforms as _affines kinds 1 and 2, identity where the observer sits within 32 ulps of the sphere."""
+    c = np.arange(n) % 8                                 # observer class
+    tk = np.where(c == 2, 0, 1 + (np.arange(n) // 8) % 2)
+    w2o = np.where((tk == 0)[:, None], _affines(g, n, 0), np.where((tk == 1)[:, None], _affines(g, n, 1), _affines(g, n, 2)))
+    A = np.transpose(w2o[:, :9].astype(np.float64).reshape(n, 3, 3), (0, 2, 1))     # x' = A x + p
+    Ai = np.linalg.inv(A)
+    o2w = np.concatenate([np.transpose(Ai, (0, 2, 1)).reshape(n, 9), -np.einsum("nij,nj->ni", Ai, w2o[:, 9:].astype(np.float64))], axis=1)
+    nrm = A.reshape(n, 9)                                # columns of inverse(o2w.linear) transposed = rows of A
+    d = _unit_vectors(g, n).astype(np.float64)
+    r = g.uniform(1.05, 30.0, n)                                                   # outside
+    r = np.where(c == 1, g.uniform(0.0, 0.95, n), r)                               # inside
+    sw = np.sqrt(SPHERE_PDF_SWITCH) * (1.0 + 10.0 ** g.uniform(-7, -2, n) * np.where(g.integers(0, 2, n) == 0, 1.0, -1.0))
+    r = np.where((c == 3) | (c == 4), sw, r)                                       # both sides of the small-angle switch
+    obj = d * r[:, None]
+    obs = _obj_to_world(w2o, obj).astype(np.float32)
+    # on the unit sphere (identity transform: object space is world space): the float32 unit vector
+    # stretched in steps of 2^-24, so dot(o, o) takes the values within some ulps of 1 on both sides
+    near = (_unit_vectors(g, n).astype(np.float64) * (1.0 + g.integers(-16, 17, n)[:, None] * 2.0 ** -24)).astype(np.float32)
+    obs = np.where((c == 2)[:, None], near, obs)
+    kind = np.where(np.arange(n) % 4 == 3, LIGHT_ENVIRONMENT, LIGHT_SPHERE).astype(np.uint32)
+    rad = g.uniform(0.1, 50.0, (n, 3)).astype(np.float32)
+    rad[np.arange(n) % 16 == 5] = 0.0                                              # black radiance
+    rec = np.concatenate([kind[:, None], f2u(rad), f2u(o2w.astype(np.float32)), f2u(w2o), f2u(nrm.astype(np.float32))], axis=1)
+    return rec, obs
+
+
+def _rows_light(name):
+    def build():
+        g = _rng("light")  # sphere_pdf, light_sample and light_pdf run the same lights and observers
+        n = N_DRAW
+        rec, obs = _light_records(g, n)
+        on = _unit_vectors(g, n)
+        u = np.minimum(g.uniform(0, 1, (n, 2)).astype(np.float32), U_TOP)
+        sp = U_SPECIALS[g.integers(0, U_SPECIALS.size, (n, 2))]
+        u = np.where((np.arange(n) % 8 == 6)[:, None], sp, u)                      # the special values of _u2_rows, crossed
+        wi = _unit_vectors(g, n)
+        tail = {"sphere_pdf": [], "light_sample": [f2u(on), f2u(u)], "light_pdf": [f2u(wi)]}[name]
+        return _finish("light", [np.concatenate([rec, f2u(obs)] + tail, axis=1)], ROW_LIGHT + 3 + sum(t.shape[1] for t in tail))
+    return build
+
+
+# ------------------------------------------------------------------ h. the image environment light
+# env_sample  u2 -> L3, pdf, wi3      env_pdf  wi3 -> pdf      env_radiance  dir3 -> rgb
+# against one of IMAGES; `<unit>_replay` is the same function without the guide tables.  A unit's
+# name carries its image: env_sample@a16.  The evaluator gets the image as a file (image_words) and
+# builds the tables with the upload's host builder; the oracle builds its own from the same pixels.
+IMAGE_NAMES = ("a16", "b64", "zero16")
+ENV_MAX_RADIANCE = np.float32(100.0)
+
+
+def image(name: str) -> dict:
+    """16 x 8 and 64 x 32 images of dim texels with a zero row, a zero column, one texel thousands of
+    times brighter and one above max_radiance (b64: a block of zeros too, and a rotated, scaled light);
+    zero16 is all zero."""
+    g = _rng("image/" + name)
+    w, h = {"a16": (16, 8), "b64": (64, 32), "zero16": (16, 8)}[name]
+    px = g.uniform(0.005, 0.02, (h, w, 3)).astype(np.float32)
+    l2w = np.eye(3)
+    if name == "zero16":
+        px[:] = 0
+    else:
+        px[h // 3, :, :] = 0
+        px[:, w // 4, :] = 0
+        px[1, 2] = (40, 50, 30)
+        px[h - 2, w - 3] = (900, 200, 100)
+    if name == "b64":
+        px[10:14, 20:41] = 0
+        q, _ = np.linalg.qr(g.normal(size=(3, 3)))
+        l2w = q * np.array([1.0, 2.0, 0.5])
+    l2w32 = l2w.astype(np.float32)
+    w2l32 = np.linalg.inv(l2w32.astype(np.float64)).astype(np.float32)
+    # sp_linear holds columns: vx, vy, vz
+    return dict(w=w, h=h, pixels=np.ascontiguousarray(px), max_radiance=ENV_MAX_RADIANCE,
+                l2w=np.ascontiguousarray(l2w32.T).ravel(), w2l=np.ascontiguousarray(w2l32.T).ravel())
+
+
+def image_words(name: str) -> np.ndarray:
+    im = image(name)
+    return np.concatenate([np.array([im["w"], im["h"]], np.uint32), f2u([im["max_radiance"]]), f2u(im["l2w"]), f2u(im["w2l"]),
+                           f2u(im["pixels"]).ravel()])
+
+
+class _EnvImage(C.Structure):  # include/simplepath_hip.h sp_env_image
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("pixels", C.POINTER(C.c_float)), ("max_radiance", C.c_float),
+                ("reserved", C.c_int32), ("light_to_world", C.c_float * 9), ("world_to_light", C.c_float * 9)]
+
+
+def oracle_set_image(variant: str, name: str):
+    from tests import _oracle
+    L, im = _oracle.load(variant), image(name)
+    d = _EnvImage(im["w"], im["h"], im["pixels"].ctypes.data_as(C.POINTER(C.c_float)), float(im["max_radiance"]), 0,
+                  (C.c_float * 9)(*im["l2w"].tolist()), (C.c_float * 9)(*im["w2l"].tolist()))
+    L.orc_unit_env.restype = C.c_int
+    L.orc_unit_env.argtypes = [C.POINTER(_EnvImage)]
+    assert L.orc_unit_env(C.byref(d)) == 0
+    return L, im
+
+
+def env_cdfs(name: str):
+    """The oracle's own marginal [nv + 1] and conditional [nv, nu + 1] cdf tables of an image."""
+    L, im = oracle_set_image("glibc", name)
+    nu, nv = 2 * im["w"], 2 * im["h"]
+    marg, cond = np.zeros(nv + 1, np.float32), np.zeros((nv, nu + 1), np.float32)
+    L.orc_unit_env_cdf.restype = C.c_int
+    L.orc_unit_env_cdf.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    assert L.orc_unit_env_cdf(marg.ctypes.data_as(C.POINTER(C.c_float)), cond.ctypes.data_as(C.POINTER(C.c_float))) == 0
+    return marg, cond
+
+
+def _around(vals) -> np.ndarray:
+    """Each value of [0, 1) and its two neighbours, as floats kept inside [0, 1 - 2^-24]."""
+    b = f2u(np.asarray(vals, np.float32)).astype(np.int64)
+    b = np.concatenate([b - 1, b, b + 1])
+    return u2f(np.clip(b, 0, int(f2u([U_TOP])[0])).astype(np.uint32))
+
+
+def guide_bits(n: int) -> int:  # sp_envmap.cpp guide_bits
+    b = 0
+    while (1 << b) < n and b < 16:
+        b += 1
+    return b
+
+
+def _rows_env_sample(img):
+    def build():
+        im = image(img)
+        nu, nv = 2 * im["w"], 2 * im["h"]
+        marg, cond = env_cdfs(img)
+        g = _rng("env_sample/" + img)
+        rnd = lambda n: np.minimum(g.uniform(0, 1, n).astype(np.float32), U_TOP)  # noqa: E731
+        a, b = np.meshgrid(U_SPECIALS, U_SPECIALS, indexing="ij")                  # 0 and 1 - 2^-24 among them
+        parts = [np.stack([rnd(1 << 14), rnd(1 << 14)], axis=1), np.stack([a.ravel(), b.ravel()], axis=1)]
+        my = np.tile(_around(marg[:nv]), 4)                                        # u.y on the marginal's entries
+        parts.append(np.stack([rnd(my.size), my], axis=1))
+        for v in range(nv):  # u.y inside row v's interval, u.x on that row's entries
+            lo, hi = (marg[v - 1] if v else np.float32(0)), marg[v]
+            uy = np.float32((np.float64(lo) + np.float64(hi)) / 2)
+            if lo <= uy < hi:
+                ux = _around(cond[v, :nu])
+                parts.append(np.stack([ux, np.full(ux.size, uy, np.float32)], axis=1))
+        for bits in sorted({guide_bits(nu), guide_bits(nv)}):                      # the guides' bucket edges
+            e = _around(np.arange(1 << bits, dtype=np.float64) / (1 << bits))
+            parts += [np.stack([e, rnd(e.size)], axis=1), np.stack([rnd(e.size), e], axis=1), np.stack([e, e], axis=1)]
+        return _finish("env_sample/" + img, [f2u(p.astype(np.float32)) for p in parts], 2)
+    return build
+
+
+def _rows_env_dirs(img):
+    def build():
+        im = image(img)
+        w, h = im["w"], im["h"]
+        g = _rng("env_dirs/" + img)  # env_pdf and env_radiance run the same directions
+        # texel borders of the nearest-neighbour fetch and of the pdf's bins, the poles and phi = 0 = 2 pi
+        # among them: every quarter step of the 2w x 2h grid, and the same angles a few ulps off
+        th = np.pi * np.arange(0, 2 * h + 0.25, 0.25) / (2 * h)
+        ph = 2 * np.pi * np.arange(0, 2 * w + 0.25, 0.25) / (2 * w)
+        T, P = (x.ravel() for x in np.meshgrid(th, ph, indexing="ij"))
+        grid = np.stack([np.sin(T) * np.cos(P), np.cos(T), np.sin(T) * np.sin(P)], axis=1).astype(np.float32)
+        jit = u2f((f2u(grid).astype(np.int64) + g.integers(-2, 3, grid.shape)).astype(np.uint32))
+        jit = np.where(grid == 0, grid, jit)
+        ax = np.array([[0, 1, 0], [0, -1, 0], [1, 0, 0], [1, 0, -0.0], [-1, 0, 0], [-1, 0, -0.0], [1, 0, 1e-45], [1, 0, -1e-45],
+                       [1, 0, 1e-8], [1, 0, -1e-8], [0, 0, 1], [0, 0, -1], [1e-30, 1, 0], [0, 1, -1e-30], [0.6, 0.8, -0.0]], dtype=np.float32)
+        local = np.concatenate([_unit_vectors(g, 1 << 14), grid, jit, ax]).astype(np.float64)
+        l2w = im["l2w"].astype(np.float64).reshape(3, 3).T                          # columns vx, vy, vz
+        world = np.where(np.allclose(l2w, np.eye(3)), local, local @ l2w.T).astype(np.float32)
+        return _finish("env_dirs/" + img, [f2u(world)], 3)
+    return build
+
+
+# (no env_pdf of the all-zero image: the reference divides its zero function by its zero integral,
+# a NaN in every row, which the NaN cap does not admit; env_sample's pdf of it is 0 and is compared)
+ENV_UNITS = {f"{fn}{form}@{img}": (fn, img) for img in IMAGE_NAMES for fn in ("env_sample", "env_pdf", "env_radiance")
+             for form in ("", "_replay") if (fn, img) != ("env_pdf", "zero16")}
+
+
+def device_name(name: str) -> str:
+    """The name the evaluator knows a unit by (a unit's image is an argument, not part of the name)."""
+    return name.split("@")[0]
+
+
+# ------------------------------------------------------------------ the kernel option sets
+# tests/cpp/Makefile states each set once (SET_<name> := -D...), beside the translation units it
+# mirrors, and builds one evaluator per set.
+_ROOT = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+
+
+def option_sets() -> dict:
+    """{set: {macro: value}} as tests/cpp/Makefile states them."""
+    sets = {}
+    for line in open(_os.path.join(_ROOT, "tests", "cpp", "Makefile")):
+        m = _re.match(r"SET_(\w+)\s*:=\s*(.*)$", line)
+        if m:
+            sets[m.group(1)] = {k: int(v) for k, v in _re.findall(r"-D(\w+)=(-?\d+)", m.group(2))}
+            assert len(sets[m.group(1)]) == len(m.group(2).split()), line
+    return sets
+
+
+# read when this module is imported: a SET_ line of the Makefile that is not a list of -DNAME=integer
+# flags fails the import (the assert in option_sets), and with it every test of the unit modules
+OPTION_SETS = option_sets()
+# units that exist in some sets only: the served forms need SP_SERVE_RHO
+ONLY_IN = {"rho16_served": ("rrnee",), "weights_served": ("rrnee",), "serve_rho": ("rrnee",)}
+WHOLE_WAVES = ("stream", "serve_rho")  # units whose rows are whole waves of 64; every other row count is off the multiples
+
+
+def evaluator(option_set: str) -> str:
+    return _os.path.join(_ROOT, "tests", "cpp", "_build", "device_units" + ("" if option_set == "default" else "_" + option_set))
+
+
+def units_of(option_set: str) -> list:
+    return [n for n in FUNCTIONS if option_set in ONLY_IN.get(n, (option_set,))]
+
+
 # ------------------------------------------------------------------ the table
 FUNCTIONS = {
     # a. libm: all bits
@@ -837,7 +1260,32 @@ FUNCTIONS = {
     "box_hit": Spec(14, 1, "box_hit", CLASS, None, False, _rows_box_hit),
     # f. the pixel stream (no orc_unit entry: the expectation is orc_mt_stream, stream_expected)
     "stream": Spec(2 + STREAM_STEPS, STREAM_OUT, None, ALL, None, False, _rows_stream),
+    # g. the stream-fed layer; mf_sample_pre and the served forms are compared with the same reference
+    # words as the form they restate
+    "rho16": Spec(31, 5, "rho16", CLASS, "packed", False, _rows_local_draw),
+    "rho16_served": Spec(31, 5, "rho16", CLASS, "packed", False, _rows_local_draw),
+    "glossy_weights": Spec(31, 4, "glossy_weights", CLASS, "packed", False, _rows_local_draw),
+    "weights_served": Spec(31, 4, "glossy_weights", CLASS, "packed", False, _rows_local_draw),
+    "mf_sample": Spec(31, 10, "mf_sample", CLASS, "packed", False, _rows_local_draw),
+    "mf_sample_pre": Spec(31, 10, "mf_sample", CLASS, "packed", False, _rows_local_draw),
+    "material_sample": Spec(34, 10, "material_sample", CLASS, "packed", False, _rows_material("material_sample")),
+    "material_eval": Spec(37, 5, "material_eval", CLASS, "packed", False, _rows_material("material_eval")),
+    "material_pdf": Spec(37, 3, "material_pdf", CLASS, "packed", False, _rows_material("material_pdf")),
+    "serve_rho": Spec(2 + ROW_MAT + 7, 12, "serve_rho", CLASS, "packed", False, _rows_serve_rho),
+    "sphere_pdf": Spec(40, 1, "sphere_pdf", CLASS, None, False, _rows_light("sphere_pdf")),
+    "light_sample": Spec(45, 9, "light_sample", CLASS, "packed", False, _rows_light("light_sample")),
+    "light_pdf": Spec(43, 1, "light_pdf", CLASS, None, False, _rows_light("light_pdf")),
+    # h. the image environment light: per image, the guided and the replayed lookup against the same reference words
+    **{name: {"env_sample": Spec(2, 7, "env_sample", CLASS, "packed", False, _rows_env_sample(img), img),
+              "env_pdf": Spec(3, 1, "env_pdf", CLASS, "packed", False, _rows_env_dirs(img), img),
+              "env_radiance": Spec(3, 3, "env_radiance", CLASS, "packed", False, _rows_env_dirs(img), img)}[fn]
+       for name, (fn, img) in ENV_UNITS.items()},
 }
+
+# the units that own a generator (section g's rows that draw): with the stream, the ones that read a kernel option
+DRAWING = ("rho16", "rho16_served", "glossy_weights", "weights_served", "mf_sample", "mf_sample_pre", "material_sample",
+           "material_eval", "material_pdf", "serve_rho")
+STREAM_FED = DRAWING + ("sphere_pdf", "light_sample", "light_pdf") + tuple(ENV_UNITS)  # sections g and h
 
 # Named exceptions: argument classes in which the device knowingly differs from
 # the reference and no valid scene can reach.  Their rows are counted, printed and left out of the
@@ -858,7 +1306,7 @@ def rows(name: str) -> np.ndarray:
     """The input rows of one function: uint32 [n, k]."""
     r = FUNCTIONS[name].rows()
     assert r.dtype == np.uint32 and r.ndim == 2 and r.shape[1] == FUNCTIONS[name].k
-    assert (r.shape[0] % 64 != 0) != (name == "stream")  # a partial last wave; the stream: whole waves
+    assert (r.shape[0] % 64 != 0) != (name in WHOLE_WAVES)  # a partial last wave; the stream and serve_rho: whole waves
     return r
 
 
@@ -878,6 +1326,8 @@ def oracle_unit(variant: str, name: str, r: np.ndarray) -> np.ndarray:
     from tests import _oracle
     spec = FUNCTIONS[name]
     L = _oracle.load(variant)
+    if spec.image:
+        oracle_set_image(variant, spec.image)
     L.orc_unit.restype = C.c_int
     L.orc_unit.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_int64, C.POINTER(C.c_uint32)]
     r = np.ascontiguousarray(r, dtype=np.uint32)
